@@ -6,7 +6,7 @@ Metric (BASELINE.json): eBWT symbols/s processed by detect+score, arrays residen
 N=1 (default `python bench.py`): BASELINE.json configs[2], the largest single-GPU configuration -- synthetic S of
 10^9 symbols, 10^6 reads x 5000 genomes (5 GB table), alpha=16, EBWT=0 (8 B/symbol), generator of SURVEY.md 8d
 (seed 42, identical on CPU and GPU).  A step = one fused pass: scan + score + the finished score table (cleared or
-rebuilt every step).  The same JSON line carries, under "also", configs[1] (10^8, 10^5 x 500, EBWT=1), the
+rebuilt every step).  With --full the same JSON line carries, under "also", configs[1] (10^8, 10^5 x 500, EBWT=1), the
 "clustered" generator on that shape, and an N = 10^10 single-GPU pass (10^6 x 1000 table) -- the one-GPU point
 of the scaling series.
 
@@ -15,7 +15,7 @@ collection of 10^10 symbols (10^6 reads x 1000 genomes, EBWT=0) cut into contigu
 with a read-ahead halo; a step = every rank's pass over its range + the ONE exchange of the path, a reduce-scatter of
 the per-rank uint8 tables (sum modulo 256, by read-row blocks) issued through the C ABI (lime_comm_*: RCCL
 ncclReduceScatter(ncclUint8, ncclSum)); the step ends when the exchange has completed (exposed -- what a single pass
-pays).  The same invocation repeats the series three more times: `also.overlapped` (the exchange of step k under the scan of
+pays).  With --full the same invocation repeats the series three more times: `also.overlapped` (the exchange of step k under the scan of
 step k+1, two table buffers -- what the four passes of LiME_paired.sh allow), `also.sparse_exchange` (owner-partitioned
 exchange of the update records instead of whole tables) and `also.auto` (whichever of the two a probe pass says moves fewer
 bytes); every entry carries the slowest rank's parts of a pass and the exchange's own time, and the line carries RCCL's
@@ -24,9 +24,13 @@ configs[2] per GPU.
 
 Prints ONE JSON line on rank 0 (the driver's contract) with two extra objects:
   roofline     HBM bound: algorithmic bytes (8 or 9 B/symbol x symbols per launch) / average duration of the scan
-               kernel k_scan measured with HIP events on its stream; also the whole pass
-  cpu_baseline the reference's own OpenMP programs (oracle/_ref, kind "reference") on a bounded sample of the
+               kernel k_scan measured with HIP events on its stream over the timed steps; also the whole pass
+  cpu_baseline (--full) the reference's own OpenMP programs (oracle/_ref, kind "reference") on a bounded sample of the
                same workload, all host cores and one thread, with the reference's own timer lines
+
+A plain run (no --full) sets up, warms up, times --steps steps and prints the line: no secondary workloads or series, no
+single-pass medians, no CPU baseline.  --dump-outputs DIR (one GPU) writes what the last timed step handed its caller as
+.npy files (table_outputs): identical arguments give identical inputs, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -68,7 +72,7 @@ WORKLOADS = {
 }
 
 
-# the secondary workloads of a default run, the largest arrays and record pools first (what they allocate is reused by everything after them)
+# the secondary workloads of a --full run, the largest arrays and record pools first (what they allocate is reused by everything after them)
 ALSO_ORDER = ("c5_clustered", "n1e10_clustered", "c5_shape", "n1e10", "c4_shape", "c2", "c2_clustered", "text_tiled", "text_spread")
 
 
@@ -77,6 +81,32 @@ def describe(wl, n_total, world):
             f": {n_total} symbols, {wl['nr']} reads x {wl['ng']} genomes "
             f"({wl['nr'] * wl['ng'] / 1e9:.2f} GB table), alpha={ALPHA}, EBWT={wl['ebwt']} ({8 + wl['ebwt']} B/symbol) -- {wl['what']}"
             + (f"; cut into {world} position ranges" if world > 1 else ""))
+
+
+DUMP_CELLS = 1 << 21            # --dump-outputs: the most block sums, and the table cells sampled (40 MB in all)
+
+
+def table_outputs(torch, table, cells, n_clusters, max_len):
+    """What a pass hands its caller -- the uint8 table (first `cells` bytes of `table`) and its counters -- as float arrays of at most
+    40 MB, whatever the table's size: `stats` = (n_clusters, max_len); `table_block_sums` = the flat table cut into at most DUMP_CELLS
+    equal blocks (the last one shorter), each summed, so that every cell counts; `table_sample` = the cells at `table_sample_pos`,
+    at most DUMP_CELLS positions drawn with SEED (all of them for a smaller table)."""
+    import numpy as np
+    flat = table[:cells]
+    blk = -(-cells // min(DUMP_CELLS, cells))
+    n_whole = cells // blk
+    rows = max(1, (64 << 20) // blk)           # 64 MB of the table per reduction (the sum widens every byte to 8)
+    sums = [flat[lo * blk:min(n_whole, lo + rows) * blk].view(-1, blk).sum(dim=1) for lo in range(0, n_whole, rows)]
+    if n_whole * blk < cells:
+        sums.append(flat[n_whole * blk:].sum().view(1))
+    if cells <= DUMP_CELLS:
+        pos = np.arange(cells, dtype=np.int64)
+    else:
+        pos = np.unique(np.random.default_rng(SEED).integers(0, cells, size=DUMP_CELLS, dtype=np.int64))
+    sample = flat[torch.from_numpy(pos).to(flat.device)]
+    return {"stats": np.array([n_clusters, max_len], dtype=np.float64),
+            "table_block_sums": torch.cat(sums).cpu().numpy().astype(np.float64),
+            "table_sample": sample.cpu().numpy().astype(np.float32), "table_sample_pos": pos.astype(np.float64)}
 
 
 def cpu_baseline(wl, lcp_t, da_t, eb_t, n, sample_n, full=True):
@@ -209,9 +239,11 @@ def reference_outputs_match(td, base, wl, lcp_t, da_t, eb_t, n, beta):
     return out
 
 
-def run_pass_series(torch, lime_amd, ldist, wl, n_total, steps, warmup, world, rank, dev, comm, overlap, exchange="dense", options=None):
+def run_pass_series(torch, lime_amd, ldist, wl, n_total, steps, warmup, world, rank, dev, comm, overlap, exchange="dense", options=None,
+                    single_passes=True, dump=False):
     """K timed steps of the workload on this rank's position range; returns (seconds, per-step parts, stats, n_own).
-    options: lime_set_option knobs for the series' context (the A/B scripts under tools/; bench.py itself passes none)."""
+    options: lime_set_option knobs for the series' context (the A/B scripts under tools/; bench.py itself passes none).
+    single_passes: time single passes after the timed steps (one GPU; pass_ms_each).  dump: res["outputs"] = table_outputs of the last timed step (one GPU)."""
     lo, hi, hi_halo = ldist.shard_ranges(n_total, world)[rank]
     n_own, n_avail = hi - lo, hi_halo - lo
     ctx = lime_amd.Context(dev.index)
@@ -348,9 +380,16 @@ def run_pass_series(torch, lime_amd, ldist, wl, n_total, steps, warmup, world, r
     ex_timing[0] = False
     exchange_ms = sum(a.elapsed_time(b) for a, b in ex_events) / len(ex_events) if ex_events else None
     parts, launches = ctx.get_timing_ex()
+    outputs = None
+    if dump:
+        assert world == 1, "dump: one GPU only"
+        s, rc = ctx.stats(stream)              # the pass is final once lime_get_stats has returned
+        if rc:
+            sys.exit(f"scan failed: rc={rc}")
+        outputs = table_outputs(torch, sims[0], wl["nr"] * wl["ng"], int(s.n_clusters), int(s.max_len))
     # the same passes once more, one at a time (HIP events around each): median and minimum next to the mean of the timed region
     each = []
-    if world == 1:
+    if world == 1 and single_passes:
         for _ in range(max(10, steps) if n_total <= 2_000_000_000 else max(5, steps)):
             step()
             p1, _n = ctx.get_timing_ex()
@@ -365,7 +404,8 @@ def run_pass_series(torch, lime_amd, ldist, wl, n_total, steps, warmup, world, r
     each.sort()
     res = {"exchange": exchange, "dt": dt, "parts": parts, "exchange_ms": exchange_ms, "cold": cold, "flags": int(s.flags),
            "pass_ms_each": {"n": len(each), "median": each[len(each) // 2], "min": each[0], "max": each[-1]} if each else None, "launches": launches, "n_own": n_own, "n_clusters": int(s.n_clusters), "max_len": int(s.max_len),
-           "updates": int(s.n_updates), "binned": bool(s.wave_records_max > 0), "wave_records_max": int(s.wave_records_max), "lcp": lcp, "da": da, "eb": eb}
+           "updates": int(s.n_updates), "binned": bool(s.wave_records_max > 0), "wave_records_max": int(s.wave_records_max), "lcp": lcp, "da": da, "eb": eb,
+           "outputs": outputs}
     ctx.close()
     return res
 
@@ -440,10 +480,16 @@ def main():
                          "auto = whichever moves fewer bytes for this workload (decided from a probe pass)")
     ap.add_argument("--no-probe", action="store_true", help="profiling runs only (tools/profile.sh): no sampled density probe in front of the first pass -- it is a "
                     "short launch of the same k_scan instance and would pull the kernel's average in a trace 5 %% below that of a pass")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads")
+    ap.add_argument("--full", action="store_true", help="besides the headline: single-pass medians, the cpu_baseline leg and the secondary workloads "
+                    "(N>1: the overlapped, sparse and auto series)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the secondary workloads")
     ap.add_argument("--cpu-sample", type=int, default=200_000_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="one GPU: write the last timed step's outputs to DIR/<name>.npy (table_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    also_on, cpu_on = args.full and not args.no_also, args.full and not args.no_cpu
 
     # The library reads its tuning / test knobs from the environment only under LIME_TEST_HOOKS=1 (lime_init): with that set -- or with another
     # build of the library (LIME_LIB), or ANY LIME_* variable this script does not know -- what is measured is not the release path
@@ -461,6 +507,8 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus and world == 1 and args.gpus > 1:
         sys.exit("bench.py --gpus N>1 must be launched with torch.distributed.run (one rank per GPU)")
+    if args.dump_outputs and world > 1:
+        sys.exit("bench.py --dump-outputs runs on one GPU only")
     if not torch.cuda.is_available():
         sys.exit("bench.py needs an MI355X: there is no CPU path")
     # rehearsal hook for a one-GPU box (not used by the driver): LIME_BENCH_BACKEND=gloo runs the N>1 control flow
@@ -497,10 +545,10 @@ def main():
     def lib_need(w, n_sym):
         return int(n_sym * ((0.25 if w["mode"] != 0 else 0.13) * 16 + 0.3)) + (2 << 30)
     planned = [(wl, n_total // world)]
-    if world == 1 and not args.no_also:
+    if world == 1 and also_on:
         planned += [(WORKLOADS[k_], WORKLOADS[k_]["n"]) for k_ in ALSO_ORDER if k_ != wname]
     reserve_bytes = max(lib_need(w_, n_) for w_, n_ in planned)
-    if world == 1 and not args.no_also:
+    if world == 1 and also_on:
         reserve_bytes = max(reserve_bytes, lib_need(WORKLOADS["c4_shape"], WORKLOADS["c4_shape"]["n"]) + WORKLOADS["c4_shape"]["nr"] * WORKLOADS["c4_shape"]["ng"])
     t_res = time.perf_counter()
     lime_amd.reserve(reserve_bytes)
@@ -509,7 +557,12 @@ def main():
                     "what": "lime_reserve at start-up: one block for the library's record pools / binned records / scratch of every workload of the run; "
                             "`cold` passes below carve from it (cold.alloc_ms is what they still spent in the allocator)"}
     r = run_pass_series(torch, lime_amd, ldist, wl, n_total, args.steps, args.warmup, world, rank, dev, comm, overlap=False, exchange=args.exchange,
-                        options={"no_probe": "1"} if args.no_probe else None)
+                        options={"no_probe": "1"} if args.no_probe else None, single_passes=args.full, dump=bool(args.dump_outputs))
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name_, a_ in r["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name_ + ".npy"), a_)
     dt, n_clusters, max_len = r["dt"], r["n_clusters"], r["max_len"]
     if world > 1:
         dt = comm.max_float(dt)
@@ -540,7 +593,7 @@ def main():
         out = {
             "metric": "eBWT symbols/s processed (ClusterLCP+ClusterBWT_DA)", "value": n_total * args.steps / dt, "unit": "symbols/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "u8", "data": "synthetic", "full": args.full,
             "config": {"workload": describe(wl, n_total, world), "symbols_total": n_total,
                        "sharding": ((f"position ranges x{world}; tables combined by one uint8 reduce-scatter per step through the C ABI "
                                      f"(RCCL), exposed (the step waits for it)") if r["exchange"] == "dense" else
@@ -560,7 +613,7 @@ def main():
                          "pass_ms_each": r.get("pass_ms_each"), "cold": r.get("cold"),
                          "pass_parts_ms": r["parts"], "pass_parts_ms_slowest_rank": slow_parts, "exchange_ms_slowest_rank": slow_ex},
         }
-    if world == 1 and rank == 0 and not args.no_cpu:
+    if world == 1 and rank == 0 and cpu_on:
         try:
             out["cpu_baseline"] = cpu_baseline(wl, r["lcp"], r["da"], r["eb"], r["n_own"], args.cpu_sample)
         except Exception as e:   # a missing baseline must not hide the GPU number
@@ -580,7 +633,7 @@ def main():
         if free_b < (4 << 30):
             torch.cuda.empty_cache()
 
-    if not args.no_also:
+    if also_on:
         also = {}
         if world == 1:
             # (the workloads with the largest arrays first: torch's cached blocks are reused by everything after them)

@@ -122,9 +122,9 @@ def test_two_ranks_exchange_update_records_and_build_their_blocks(tmp_path):
 
 
 def test_bench_control_flow_with_two_ranks():
-    """bench.py --gpus 2 (strong scaling of a small collection, exposed and overlapped exchange) under the rehearsal backend"""
+    """bench.py --gpus 2 --full (strong scaling of a small collection, exposed and overlapped exchange) under the rehearsal backend"""
     r = _torchrun(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c2", "--scaling", "strong",
-                   "--n-total", "30000000"], {"LIME_BENCH_BACKEND": "gloo"}, bench=True)
+                   "--n-total", "30000000", "--full"], {"LIME_BENCH_BACKEND": "gloo"}, bench=True)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
