@@ -370,6 +370,53 @@ int lime_classify(uint32_t n_files, const char *const *inputs, int binary, uint3
                   uint64_t counts[4]);
 const char *lime_classify_error(void);
 
+/* ---- read assignment from lists resident in HBM ------------------------------------------ *
+ * One read's decision: type 'C' / 'U' / 'A' / 'H' (classified, not classified, ambiguous, higher rank), the taxon ('C', 'H'),
+ * the similarity written next to it, and the rule that decided (0 = U; 1, 2, 3 as in lime_classify.cpp). 12 bytes. */
+typedef struct { uint32_t taxon; float sim; uint8_t type; uint8_t rule; uint8_t pad[2]; } lime_verdict_t;
+
+/* One collection's clusterChoose result left in HBM (ctx-owned, opaque): row_max u8[n_reads], row_off u64[n_reads + 1], the pairs
+ * (ascending idRef inside each row) and the norm / beta it was made with -- what lime_choose_pairs_dev / lime_fused_choose_dev return
+ * on the host, which are now "make the lists, copy them out".  Any number may live at once (four for a paired-end sample); each is
+ * released by lime_lists_free, or by lime_shutdown of its ctx (not both).  These calls synchronise `stream`. */
+typedef struct lime_lists lime_lists;
+int lime_choose_lists_dev(lime_ctx *ctx, const uint8_t *d_sim, uint32_t n_reads, uint32_t n_refs, uint32_t norm, float beta,
+                          lime_lists **out, void *stream);
+int lime_fused_choose_lists_dev(lime_ctx *ctx, const uint32_t *d_lcp, const uint32_t *d_da, const uint8_t *d_ebwt, uint64_t n,
+                                uint32_t n_reads, uint32_t n_refs, uint32_t alpha, uint32_t norm, float beta, lime_lists **out,
+                                lime_stats_t *stats, void *stream);
+/* the same from host arrays or mapped files (registered with lime_register_file: read with pread()), staged through pinned memory */
+int lime_fused_choose_lists(lime_ctx *ctx, const uint32_t *lcp, const uint32_t *da, const uint8_t *ebwt, uint64_t n,
+                            uint32_t n_reads, uint32_t n_refs, uint32_t alpha, uint32_t norm, float beta, lime_lists **out,
+                            lime_stats_t *stats);
+/* host copies: row_max[n_reads], row_off[n_reads + 1] (caller's), *pairs library-allocated (lime_free; NULL when there are none) */
+int lime_lists_get(const lime_lists *lists, uint8_t *row_max, uint64_t *row_off, lime_pair_t **pairs, uint64_t *n_pairs);
+int lime_lists_info(const lime_lists *lists, uint32_t *n_reads, uint64_t *n_pairs, uint32_t *norm, float *beta);
+void lime_lists_free(lime_lists *lists);
+
+/* The lineage file (';'-separated, a header line; Classify.cpp:32-85) at taxRank `rank` (0 = genome .. 6), with the higher ranks'
+ * columns when higher != 0 (the HIGHER=1 build; needs rank >= 1).  Host only; the device copy is made by the first device
+ * classification that uses it.  A file with other than n_targ genomes: LIME_ERR_ARG ("poor taxonomy information").
+ * Errors of lime_taxonomy_load, lime_classify_mem and lime_write_classification: lime_classify_error(). */
+typedef struct lime_taxonomy lime_taxonomy;
+int  lime_taxonomy_load(const char *path, int rank, int higher, uint32_t n_targ, lime_taxonomy **out);
+void lime_taxonomy_free(lime_taxonomy *tx);
+
+/* Classify (Classify.cpp:503-690, the decision of lime_classify) on the device over 2 (single-end) or 4 (paired-end, the
+ * script's F, F_RC, R, R_RC order) lists of one ctx: one verdict per read into the host array verdicts[n_reads] (12 bytes per read
+ * cross PCIe); counts = {C, U, A, H}.  binary != 0: the values the BIN=1 build reads (float(k) / norm), else the .res.txt ones (%.5f).
+ * LIME_ERR_ARG (lime_last_error) for n_lists other than 2 / 4, lists with different n_reads, a taxonomy of another n_targ and an
+ * idRef >= n_targ.  Synchronises `stream`.  One taxonomy may serve contexts on several threads and devices (its device copy is made
+ * on first use, per device, under a lock; calls that use it on different devices take turns). */
+int lime_classify_lists_dev(lime_ctx *ctx, uint32_t n_lists, const lime_lists *const *lists, uint32_t n_targ,
+                            const lime_taxonomy *tx, int binary, lime_verdict_t *verdicts, uint64_t counts[4], void *stream);
+/* The same decision on the host over lists held in memory (lime_lists_get's copies): the CPU reference of the device path. */
+int lime_classify_mem(uint32_t n_files, const uint8_t *const *row_max, const uint64_t *const *row_off, const lime_pair_t *const *pairs,
+                      const uint32_t *norms, const float *betas, int binary, uint32_t n_reads, uint32_t n_targ,
+                      const lime_taxonomy *tx, lime_verdict_t *verdicts, uint64_t counts[4]);
+/* The classification file of lime_classify (header, "C,read,taxon,sim" lines, same float formatting) from verdicts. */
+int lime_write_classification(const char *path, const lime_verdict_t *verdicts, uint32_t n_reads);
+
 #ifdef __cplusplus
 }
 #endif

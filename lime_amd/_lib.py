@@ -103,6 +103,17 @@ SYMBOLS = {
     "lime_score_choose_multi": (_i, [_i, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _u32, _u32, C.c_float, _vp, _vp, _pp, _pu64]),
     "lime_write_res_txt_pairs": (_i, [C.c_char_p, _vp, _vp, _vp, _u32, _u32, C.c_float]),
     "lime_write_res_bin_pairs": (_i, [C.c_char_p, C.c_char_p, _vp, _vp, _vp, _u32, _u32, C.c_float]),
+    "lime_choose_lists_dev": (_i, [_vp, _vp, _u32, _u32, _u32, C.c_float, _pp, _vp]),
+    "lime_fused_choose_lists_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _u32, C.c_float, _pp, C.POINTER(Stats), _vp]),
+    "lime_fused_choose_lists": (_i, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _u32, C.c_float, _pp, C.POINTER(Stats)]),
+    "lime_lists_get": (_i, [_vp, _vp, _vp, _pp, _pu64]),
+    "lime_lists_info": (_i, [_vp, C.POINTER(_u32), _pu64, C.POINTER(_u32), C.POINTER(C.c_float)]),
+    "lime_lists_free": (None, [_vp]),
+    "lime_taxonomy_load": (_i, [C.c_char_p, _i, _i, _u32, _pp]),
+    "lime_taxonomy_free": (None, [_vp]),
+    "lime_classify_lists_dev": (_i, [_vp, _u32, _vp, _u32, _vp, _i, _vp, _vp, _vp]),
+    "lime_classify_mem": (_i, [_u32, _vp, _vp, _vp, _vp, _vp, _i, _u32, _u32, _vp, _vp, _vp]),
+    "lime_write_classification": (_i, [C.c_char_p, _vp, _u32]),
 }
 
 _LIB = None
@@ -132,6 +143,12 @@ def load():
 def check(rc):
     if rc != LIME_OK:
         raise LimeError(rc, load().lime_last_error().decode(errors="replace"))
+
+
+def check_cls(rc):
+    """the host-side read-assignment calls (taxonomy, lime_classify_mem, lime_write_classification) report in lime_classify_error"""
+    if rc != LIME_OK:
+        raise LimeError(rc, load().lime_classify_error().decode(errors="replace"))
 
 
 def hip_memcpy_d2d(dst, src, nbytes):

@@ -15,7 +15,10 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Cluster, LimeError, Stats, check  # noqa: F401
+from ._lib import Cluster, LimeError, Stats, check, check_cls  # noqa: F401
+
+# lime_verdict_t: one read's classification (type C/U/A/H as a byte, rule 0 = U, 1, 2, 3)
+VERDICT = np.dtype([("taxon", "<u4"), ("sim", "<f4"), ("type", "u1"), ("rule", "u1"), ("pad", "u1", (2,))])
 
 
 class _LibBuf:
@@ -39,6 +42,7 @@ class Context:
         h = C.c_void_p()
         check(self.lib.lime_init(-1 if device is None else int(device), C.byref(h)))
         self.h = h
+        self._lists = []                     # Lists of this ctx still alive: lime_shutdown frees them
 
     def set_option(self, key, value=""):
         """a tuning / test knob of the ctx by name (lime_set_option; include/lime_hip.h lists them); "" = the library's own choice"""
@@ -46,6 +50,11 @@ class Context:
 
     def close(self):
         if self.h:
+            for ref in self._lists:
+                li = ref()
+                if li is not None:
+                    li.h = None              # (freed by lime_shutdown)
+            self._lists = []
             self.lib.lime_shutdown(self.h)
             self.h = None
 
@@ -162,6 +171,45 @@ class Context:
                                              mx.ctypes.data, off.ctypes.data, C.byref(pp), C.byref(npairs), C.byref(s), stream))
         return mx[:n_reads], off[:n_reads + 1], self._pairs_out(pp, npairs), s
 
+    # ---- clusterChoose results left in HBM, classified there (include/lime_hip.h: lime_lists) ----
+    def _lists_of(self, h):
+        import weakref
+        li = Lists(self, h)
+        self._lists = [r for r in self._lists if r() is not None] + [weakref.ref(li)]
+        return li
+
+    def choose_lists_dev(self, sim_t, n_reads, n_refs, norm, beta, stream=None):
+        """clusterChoose of a device-resident table, the lists left in HBM -> Lists"""
+        h = C.c_void_p()
+        check(self.lib.lime_choose_lists_dev(self.h, _ptr(sim_t), n_reads, n_refs, norm, beta, C.byref(h), stream))
+        return self._lists_of(h)
+
+    def fused_choose_lists_dev(self, lcp_t, da_t, ebwt_t, n, n_reads, n_refs, alpha, norm, beta, stream=None):
+        """scan + clusterAnalyze + clusterChoose on device-resident arrays, the lists left in HBM -> (Lists, Stats)"""
+        h, s = C.c_void_p(), Stats()
+        check(self.lib.lime_fused_choose_lists_dev(self.h, _ptr(lcp_t), _ptr(da_t), _ptr(ebwt_t), n, n_reads, n_refs, alpha, norm, beta,
+                                                   C.byref(h), C.byref(s), stream))
+        return self._lists_of(h), s
+
+    def fused_choose_lists(self, lcp, da, ebwt, n_reads, n_refs, alpha, norm, beta):
+        """the same from host arrays (or np.memmap'd files; the collection is as long as the shortest of them) -> (Lists, Stats)"""
+        lcp = np.ascontiguousarray(lcp, dtype=np.uint32) if not isinstance(lcp, np.memmap) else lcp
+        da = np.ascontiguousarray(da, dtype=np.uint32) if not isinstance(da, np.memmap) else da
+        n = min(len(lcp), len(da)) if ebwt is None else min(len(lcp), len(da), len(ebwt))     # (a short file: no read past its end)
+        h, s = C.c_void_p(), Stats()
+        check(self.lib.lime_fused_choose_lists(self.h, lcp.ctypes.data, da.ctypes.data, None if ebwt is None else ebwt.ctypes.data,
+                                               n, n_reads, n_refs, alpha, norm, beta, C.byref(h), C.byref(s)))
+        return self._lists_of(h), s
+
+    def classify_lists_dev(self, lists, n_targ, taxonomy, binary=True, stream=None):
+        """Classify over 2 or 4 Lists of this ctx -> (verdicts: numpy VERDICT[n_reads], counts {C, U, A, H} as a list)"""
+        hs = (C.c_void_p * len(lists))(*[li.h for li in lists])
+        n_reads = lists[0].info()[0] if lists and lists[0].h else 0
+        v = np.zeros(max(n_reads, 1), dtype=VERDICT)
+        counts = (C.c_uint64 * 4)()
+        check(self.lib.lime_classify_lists_dev(self.h, len(lists), hs, n_targ, taxonomy.h, int(bool(binary)), v.ctypes.data, counts, stream))
+        return v[:n_reads], list(counts)
+
     # ---- array level, device pointers (torch tensors on this ctx's device) ---------------
     def stats(self, stream=None):
         s = Stats()
@@ -240,7 +288,89 @@ class Context:
         v = (C.c_double * 8)()
         check(self.lib.lime_get_host_times(self.h, v))
         return {"alloc_ms": v[0], "probe_ms": v[1], "probes": int(v[2]), "repeats": int(v[3]), "cas_fallbacks": int(v[4]),
-                "records_per_symbol": None if v[5] < 0 else v[5], "choose_without_table": int(v[6])}
+                "records_per_symbol": None if v[5] < 0 else v[5], "choose_without_table": int(v[6]), "classify_kernel_ms": v[7]}
+
+
+class Lists:
+    """one collection's clusterChoose result resident in HBM (lime_lists), owned by its Context"""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def info(self):
+        """-> (n_reads, n_pairs, norm, beta)"""
+        nr, npairs, norm, beta = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_float()
+        check(self.ctx.lib.lime_lists_info(self.h, C.byref(nr), C.byref(npairs), C.byref(norm), C.byref(beta)))
+        return int(nr.value), int(npairs.value), int(norm.value), float(beta.value)
+
+    def get(self):
+        """host copies -> (row_max u8[n_reads], row_off u64[n_reads + 1], pairs u32[n, 2] = (idRef, sim))"""
+        nr = self.info()[0]
+        mx = np.zeros(nr + 1, dtype=np.uint8)
+        off = np.zeros(nr + 1, dtype=np.uint64)
+        pp, npairs = C.c_void_p(), C.c_uint64(0)
+        check(self.ctx.lib.lime_lists_get(self.h, mx.ctypes.data, off.ctypes.data, C.byref(pp), C.byref(npairs)))
+        return mx[:nr], off, self.ctx._pairs_out(pp, npairs)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lime_lists_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Taxonomy:
+    """a lineage file at one rank (lime_taxonomy_load); its device copy is made by the first classification on a device"""
+
+    def __init__(self, path, rank, higher, n_targ):
+        self.lib = _lib.load()
+        h = C.c_void_p()
+        check_cls(self.lib.lime_taxonomy_load(str(path).encode(), int(rank), int(bool(higher)), int(n_targ), C.byref(h)))
+        self.h, self.n_targ = h, int(n_targ)
+
+    def close(self):
+        if self.h:
+            self.lib.lime_taxonomy_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def load_taxonomy(path, rank, higher, n_targ):
+    return Taxonomy(path, rank, higher, n_targ)
+
+
+def write_classification(path, verdicts):
+    """the classification file (lime_classify's bytes) from VERDICT records"""
+    v = np.ascontiguousarray(verdicts, dtype=VERDICT)
+    check_cls(_lib.load().lime_write_classification(str(path).encode(), v.ctypes.data if len(v) else None, len(v)))
+
+
+def classify_mem(lists, norms, betas, n_targ, taxonomy, binary=True):
+    """Classify on the host over 2 or 4 (row_max, row_off, pairs) triples (Lists.get's copies) -> (verdicts, counts)"""
+    lib = _lib.load()
+    k = len(lists)
+    mx = [np.ascontiguousarray(l[0], dtype=np.uint8) for l in lists]
+    off = [np.ascontiguousarray(l[1], dtype=np.uint64) for l in lists]
+    pr = [np.ascontiguousarray(np.asarray(l[2], dtype=np.uint32).reshape(-1, 2)) for l in lists]
+    n_reads = len(mx[0]) if k else 0
+    P = lambda arrs: (C.c_void_p * k)(*[a.ctypes.data for a in arrs])
+    nm = np.ascontiguousarray(norms, dtype=np.uint32)
+    bt = np.ascontiguousarray(betas, dtype=np.float32)
+    v = np.zeros(max(n_reads, 1), dtype=VERDICT)
+    counts = (C.c_uint64 * 4)()
+    check_cls(lib.lime_classify_mem(k, P(mx), P(off), P(pr), nm.ctypes.data, bt.ctypes.data, int(bool(binary)), n_reads, n_targ,
+                                    taxonomy.h, v.ctypes.data, counts))
+    return v[:n_reads], list(counts)
 
 
 def _ptr(t):
@@ -290,6 +420,36 @@ def cluster_lcp(file_fasta, num_reads, num_genomes, alpha, threads=1, ctx=None):
     check(lib.lime_write_clrs(f"{file_fasta}.{alpha}.clrs".encode(), cl.ctypes.data if nc else None, nc))
     check(lib.lime_write_aux(aux_name(file_fasta).encode(), num_reads, num_genomes, alpha, ml, nc))
     return nc, ml
+
+
+def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, threads=1, ebwt=True, higher=False, binary=True, ctx=None):
+    """`LiME_paired.sh File1_F File1_RC File2_F File2_RC output numReads numGenomes LineageFile readLen threads` (LiME_paired.sh:44-79) in
+    one process, like lime_amd/bin/LiME_paired: alpha 16, beta 0.25, taxRank 1; reads <file>.lcp / .da / .ebwt, writes only `output`
+    (no .clrs, .out or .res.* files).  -> counts {C, U, A, H}"""
+    if len(files) != 4:
+        raise ValueError("LiME_paired takes four collections: File1_F File1_RC File2_F File2_RC")
+    alpha, beta, rank = 16, float(np.float32(0.25)), 1
+    norm = ((int(read_len) & 0xFF) + 1 - alpha) & 0xFFFFFFFF
+    tx = Taxonomy(lineage, rank, higher, num_genomes)
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        lists = []
+        for f in files:
+            lcp = np.memmap(f + ".lcp", dtype="<u4", mode="r")
+            da = np.memmap(f + ".da", dtype="<u4", mode="r")
+            eb = np.memmap(f + ".ebwt", dtype=np.uint8, mode="r") if ebwt else None
+            li, _ = ctx.fused_choose_lists(lcp, da, eb, num_reads, num_genomes, alpha, norm, beta)
+            lists.append(li)
+        v, counts = ctx.classify_lists_dev(lists, num_genomes, tx, binary)
+        for li in lists:
+            li.close()
+    finally:
+        if own:
+            ctx.close()
+        tx.close()
+    write_classification(output, v)
+    return counts
 
 
 def cluster_bwt_da(file_fasta, read_len, beta, threads=1, ebwt=True, binary=True, ctx=None):

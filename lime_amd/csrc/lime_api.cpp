@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "lime_classify.h"
 #include "lime_device.h"
 #include "lime_hip.h"
 #include "lime_kernels.h"
@@ -124,6 +125,19 @@ struct lime_ctx {
     bool timing = false;
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
+    double cls_ms = 0.0;                    // the last lime_classify_lists_dev kernel (timing on)
+    std::vector<lime_lists *> lists;        // clusterChoose results left in HBM that are still alive (lime_lists_free / lime_shutdown)
+};
+
+// one collection's clusterChoose result in HBM: [row_off u64[n_reads + 1]][row_max u8[n_reads]] in one block, the pairs in another
+struct lime_lists {
+    lime_ctx *ctx = nullptr;
+    uint32_t n_reads = 0, norm = 0; float beta = 0.0f;
+    uint64_t n_pairs = 0;
+    uint8_t *d_rows = nullptr;
+    lime_pair_t *d_pairs = nullptr;
+    const uint64_t *row_off() const { return reinterpret_cast<const uint64_t *>(d_rows); }
+    const uint8_t *row_max() const { return d_rows + ((size_t)n_reads + 1) * 8; }
 };
 
 extern "C" const char *lime_last_error(void) { return g_err.c_str(); }
@@ -429,6 +443,7 @@ extern "C" void lime_shutdown(lime_ctx *c)
     if (c->h_xoff) (void)hipHostFree(c->h_xoff);
     if (c->ev_xoff) (void)hipEventDestroy(c->ev_xoff);
     for (void *p : {(void *)c->d_bigrec, (void *)c->d_bigrec_n, (void *)c->d_xrecs, (void *)c->d_xrecs2, (void *)c->d_xoff, (void *)c->d_xreg}) dev_release(p);
+    for (lime_lists *L : c->lists) { dev_release(L->d_rows); dev_release(L->d_pairs); delete L; }
     delete c;
 }
 
@@ -580,7 +595,7 @@ extern "C" int lime_get_host_times(lime_ctx *c, double out[8])
     if (!out) return fail(LIME_ERR_ARG, "lime_get_host_times: out is NULL");
     out[0] = c->alloc_ms; out[1] = c->probe_ms; out[2] = (double)c->n_probes; out[3] = (double)c->n_repeats; out[4] = (double)c->n_fallbacks;
     out[5] = c->density_known ? c->density : -1.0;
-    out[6] = (double)c->n_table_free; out[7] = 0.0;
+    out[6] = (double)c->n_table_free; out[7] = c->cls_ms;
     return LIME_OK;
 }
 
@@ -2071,19 +2086,59 @@ static void choose_pass_table(uint32_t norm, float beta, bool pass[256])
     }
 }
 
-// clusterChoose on the device, compact results to the host
-extern "C" int lime_choose_pairs_dev(lime_ctx *c, const uint8_t *d_sim, uint32_t n_reads, uint32_t n_refs,
-                                     uint32_t norm, float beta, uint8_t *row_max, uint64_t *row_off,
-                                     lime_pair_t **pairs, uint64_t *n_pairs, void *stream)
+// ---- clusterChoose results left in HBM (lime_lists) ---------------------------------------------------------------------
+static void lists_release(lime_lists *L)
 {
-    int rc = check_ctx(c, "lime_choose_pairs_dev"); if (rc) return rc;
-    if (!pairs || !n_pairs || !row_off || (n_reads && (!d_sim || !row_max)))
-        return fail(LIME_ERR_ARG, "lime_choose_pairs_dev: NULL array");
-    *pairs = nullptr; *n_pairs = 0; row_off[0] = 0;
-    if (!n_reads) return LIME_OK;
-    if (misaligned(d_sim, 16)) return fail(LIME_ERR_ARG, "lime_choose_pairs_dev: d_sim must be 16-byte aligned (and lime_sim_bytes() long)");
-    hipStream_t st = (hipStream_t)stream;
-    DevBuf doff, dp;
+    if (!L) return;
+    std::vector<lime_lists *> &v = L->ctx->lists;
+    v.erase(std::remove(v.begin(), v.end(), L), v.end());
+    dev_release(L->d_rows); dev_release(L->d_pairs);
+    delete L;
+}
+struct ListsGuard {                                      // releases a lists object on an error path
+    lime_lists *L = nullptr;
+    ~ListsGuard() { lists_release(L); }
+    lime_lists *take() { lime_lists *r = L; L = nullptr; return r; }
+};
+// a lists object for rows whose offsets the host has made: the offsets (and, with_max, the maxima) are uploaded, the pairs' block is
+// allocated for the caller's kernel to fill
+static int lists_new(lime_ctx *c, uint32_t n_reads, uint32_t norm, float beta, const uint8_t *row_max, const uint64_t *row_off, bool with_max,
+                     hipStream_t st, ListsGuard &g)
+{
+    lime_lists *L = new (std::nothrow) lime_lists();
+    if (!L) return fail(LIME_ERR_NOMEM, "clusterChoose lists: out of host memory");
+    L->ctx = c; L->n_reads = n_reads; L->norm = norm; L->beta = beta; L->n_pairs = row_off[n_reads];
+    c->lists.push_back(L);
+    g.L = L;
+    const size_t off_bytes = ((size_t)n_reads + 1) * 8;
+    void *p = nullptr;
+    HIP_TRY(dev_acquire(&p, off_bytes + n_reads + 16));
+    L->d_rows = static_cast<uint8_t *>(p);
+    if (L->n_pairs) { HIP_TRY(dev_acquire(&p, (size_t)L->n_pairs * sizeof(lime_pair_t))); L->d_pairs = static_cast<lime_pair_t *>(p); }
+    HIP_TRY(hipMemcpyAsync(L->d_rows, row_off, off_bytes, hipMemcpyHostToDevice, st));
+    if (with_max && n_reads) HIP_TRY(hipMemcpyAsync(L->d_rows + off_bytes, row_max, n_reads, hipMemcpyHostToDevice, st));
+    return LIME_OK;
+}
+// the pairs of a lists object into freshly allocated host memory (what the host-returning calls hand out)
+static int lists_pairs_to_host(lime_ctx *c, const lime_lists *L, lime_pair_t **pairs, uint64_t *n_pairs, hipStream_t st)
+{
+    *pairs = nullptr; *n_pairs = L->n_pairs;
+    if (!L->n_pairs) { HIP_TRY(hipStreamSynchronize(st)); return LIME_OK; }
+    lime_pair_t *h = (lime_pair_t *)malloc((size_t)L->n_pairs * sizeof(lime_pair_t));
+    if (!h) return fail(LIME_ERR_NOMEM, "clusterChoose lists: out of host memory");
+    int rc = d2h_pageable(c, h, L->d_pairs, (size_t)L->n_pairs * sizeof(lime_pair_t), st);
+    if (rc) { free(h); return rc; }
+    *pairs = h;
+    return LIME_OK;
+}
+
+// clusterChoose of a device table into a lists object; row_max / row_off (host, n_reads / n_reads + 1) receive the rows' maxima and offsets
+static int choose_lists_impl(lime_ctx *c, const uint8_t *d_sim, uint32_t n_reads, uint32_t n_refs, uint32_t norm, float beta,
+                             uint8_t *row_max, uint64_t *row_off, bool with_max, hipStream_t st, ListsGuard &g)
+{
+    int rc;
+    row_off[0] = 0;
+    if (!n_reads) return lists_new(c, 0, norm, beta, row_max, row_off, with_max, st, g);
     const size_t nz_off = ((size_t)n_reads + 15u) & ~(size_t)15u;      // row non-zero counts behind the row maxima, in both buffers
     if ((rc = ensure_choose(c, nz_off + (size_t)n_reads * 4, nz_off + (size_t)n_reads * 4, st))) return rc;
     launch_choose(d_sim, n_reads, n_refs, c->d_choose, reinterpret_cast<uint32_t *>(c->d_choose + nz_off), st);
@@ -2102,16 +2157,44 @@ extern "C" int lime_choose_pairs_dev(lime_ctx *c, const uint8_t *d_sim, uint32_t
         if (pass[mx]) total += nnz[r];
     }
     row_off[n_reads] = total;
-    *n_pairs = total;
+    if ((rc = lists_new(c, n_reads, norm, beta, row_max, row_off, with_max, st, g))) return rc;
     if (!total) return LIME_OK;
-    if ((rc = doff.upload(row_off, ((size_t)n_reads + 1) * 8))) return rc;
-    if ((rc = dp.alloc((size_t)total * sizeof(lime_pair_t)))) return rc;
-    launch_gather_pairs(d_sim, n_reads, n_refs, (const uint64_t *)doff.p, (lime_pair_t *)dp.p, st);
+    launch_gather_pairs(d_sim, n_reads, n_refs, g.L->row_off(), g.L->d_pairs, st);
     HIP_TRY(hipGetLastError());
-    lime_pair_t *h = (lime_pair_t *)malloc((size_t)total * sizeof(lime_pair_t));
-    if (!h) return fail(LIME_ERR_NOMEM, "lime_choose_pairs_dev: out of host memory");
-    if ((rc = d2h_pageable(c, h, dp.p, (size_t)total * sizeof(lime_pair_t), st))) { free(h); return rc; }
-    *pairs = h;
+    return LIME_OK;
+}
+
+// clusterChoose on the device, compact results to the host: the lists, copied out
+extern "C" int lime_choose_pairs_dev(lime_ctx *c, const uint8_t *d_sim, uint32_t n_reads, uint32_t n_refs,
+                                     uint32_t norm, float beta, uint8_t *row_max, uint64_t *row_off,
+                                     lime_pair_t **pairs, uint64_t *n_pairs, void *stream)
+{
+    int rc = check_ctx(c, "lime_choose_pairs_dev"); if (rc) return rc;
+    if (!pairs || !n_pairs || !row_off || (n_reads && (!d_sim || !row_max)))
+        return fail(LIME_ERR_ARG, "lime_choose_pairs_dev: NULL array");
+    *pairs = nullptr; *n_pairs = 0; row_off[0] = 0;
+    if (!n_reads) return LIME_OK;
+    if (misaligned(d_sim, 16)) return fail(LIME_ERR_ARG, "lime_choose_pairs_dev: d_sim must be 16-byte aligned (and lime_sim_bytes() long)");
+    hipStream_t st = (hipStream_t)stream;
+    ListsGuard g;
+    if ((rc = choose_lists_impl(c, d_sim, n_reads, n_refs, norm, beta, row_max, row_off, false, st, g))) return rc;
+    return lists_pairs_to_host(c, g.L, pairs, n_pairs, st);
+}
+
+extern "C" int lime_choose_lists_dev(lime_ctx *c, const uint8_t *d_sim, uint32_t n_reads, uint32_t n_refs, uint32_t norm, float beta,
+                                     lime_lists **out, void *stream)
+{
+    int rc = check_ctx(c, "lime_choose_lists_dev"); if (rc) return rc;
+    if (!out || (n_reads && !d_sim)) return fail(LIME_ERR_ARG, "lime_choose_lists_dev: NULL argument");
+    *out = nullptr;
+    if (misaligned(d_sim, 16)) return fail(LIME_ERR_ARG, "lime_choose_lists_dev: d_sim must be 16-byte aligned (and lime_sim_bytes() long)");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<uint8_t> mx((size_t)n_reads + 1);
+    std::vector<uint64_t> off((size_t)n_reads + 1);
+    ListsGuard g;
+    if ((rc = choose_lists_impl(c, d_sim, n_reads, n_refs, norm, beta, mx.data(), off.data(), true, st, g))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = g.take();
     return LIME_OK;
 }
 
@@ -2122,16 +2205,13 @@ extern "C" int lime_choose_pairs_dev(lime_ctx *c, const uint8_t *d_sim, uint32_t
 // `float(max) / norm > beta` (:404-406), for the passing rows' (idRef, sim) lists (:408-423; regions without a passing row are skipped).  Against
 // table + k_choose + k_gather_pairs that saves writing T bytes and reading them once or twice.  Elsewhere (small tables, short passes, n_refs < 256):
 // the table is built and scanned as before.  Outputs as lime_choose_pairs_dev; *stats (may be NULL) as lime_get_stats.
-extern "C" int lime_fused_choose_dev(lime_ctx *c, const uint32_t *d_lcp, const uint32_t *d_da, const uint8_t *d_ebwt, uint64_t n,
-                                     uint32_t n_reads, uint32_t n_refs, uint32_t alpha, uint32_t norm, float beta,
-                                     uint8_t *row_max, uint64_t *row_off, lime_pair_t **pairs, uint64_t *n_pairs,
-                                     lime_stats_t *stats, void *stream)
+static int fused_choose_lists_impl(lime_ctx *c, const uint32_t *d_lcp, const uint32_t *d_da, const uint8_t *d_ebwt, uint64_t n,
+                                   uint32_t n_reads, uint32_t n_refs, uint32_t alpha, uint32_t norm, float beta,
+                                   uint8_t *row_max, uint64_t *row_off, bool with_max, lime_stats_t *stats, hipStream_t st, ListsGuard &g)
 {
-    int rc = check_ctx(c, "lime_fused_choose_dev"); if (rc) return rc;
-    if (!pairs || !n_pairs || !row_off || !row_max) return fail(LIME_ERR_ARG, "lime_fused_choose_dev: NULL output");
-    if (!n_reads || !n_refs) return fail(LIME_ERR_ARG, "lime_fused_choose_dev: n_reads and n_refs must be > 0");
-    *pairs = nullptr; *n_pairs = 0; row_off[0] = 0;
-    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    void *stream = st;
+    row_off[0] = 0;
     const size_t sim_bytes = lime_sim_bytes(n_reads, n_refs);
     const bool bin_fits = !(sim_bytes > ((size_t)BIN_MAX << BIN_SHIFT_MAX) || sim_bytes >= (1ull << CELL_BITS) || sim_bytes > ((uint64_t)MAX_SUB << 32));
     uint32_t n_bins = 0, bin_shift = REGION_SHIFT;
@@ -2148,7 +2228,10 @@ extern "C" int lime_fused_choose_dev(lime_ctx *c, const uint32_t *d_lcp, const u
         rc = lime_get_stats(c, &s, stream);
         if (stats) *stats = s;
         if (rc) return rc;
-        return lime_choose_pairs_dev(c, (const uint8_t *)ds.p, n_reads, n_refs, norm, beta, row_max, row_off, pairs, n_pairs, stream);
+        if (misaligned(ds.p, 16)) return fail(LIME_ERR_ARG, "lime_fused_choose_dev: misaligned table");
+        if ((rc = choose_lists_impl(c, (const uint8_t *)ds.p, n_reads, n_refs, norm, beta, row_max, row_off, with_max, st, g))) return rc;
+        HIP_TRY(hipStreamSynchronize(st));                  // (before the table goes)
+        return LIME_OK;
     }
     ++c->n_table_free;
     if ((rc = fused_dev_impl(c, d_lcp, d_da, d_ebwt, n, n, 1, n_reads, n_refs, alpha, nullptr, 1, false, st, nullptr, false, true))) return rc;
@@ -2160,7 +2243,7 @@ extern "C" int lime_fused_choose_dev(lime_ctx *c, const uint32_t *d_lcp, const u
     HIP_TRY(hipStreamSynchronize(st));
     if (nb > c->bigrec_cap) return fail(LIME_ERR_NOMEM, "more update records of long clusters (%u) than their list holds (%u)", nb, c->bigrec_cap);
     const uint32_t n_regions = (uint32_t)((sim_bytes + ((size_t)1 << REGION_SHIFT) - 1) >> REGION_SHIFT);
-    DevBuf bcnt, bcur, boff, bout, doff, dp;
+    DevBuf bcnt, bcur, boff, bout;
     // the ctx's scratch: [region words 16 R][row max 4 n][row nnz 4 n][last nnz 4 R]; the rows' two arrays come back in one copy
     const size_t rows_off = (size_t)n_regions * 16, rows_bytes = (size_t)n_reads * 8, last_off = rows_off + rows_bytes;
     if ((rc = ensure_choose(c, last_off + (size_t)n_regions * 4, rows_bytes, st))) return rc;
@@ -2197,18 +2280,165 @@ extern "C" int lime_fused_choose_dev(lime_ctx *c, const uint32_t *d_lcp, const u
         if (pass[mx]) total += hz[r];
     }
     row_off[n_reads] = total;
-    *n_pairs = total;
-    if (!total) return LIME_OK;
-    if ((rc = doff.upload(row_off, ((size_t)n_reads + 1) * 8))) return rc;
-    if ((rc = dp.alloc((size_t)total * sizeof(lime_pair_t)))) return rc;
-    fin.row_off = (const uint64_t *)doff.p; fin.pairs = (lime_pair_t *)dp.p;
-    launch_region_rows(n_regions, n_refs, fin.table_bytes, fin.row_off, drr, st);          // (now with the regions that have nothing to gather marked)
-    launch_apply_tiles_fin(2, sim_bytes, bin_shift, c->d_tbase, c->d_tidx, rows, many_records_of(c, expect), fin, st);
+    if ((rc = lists_new(c, n_reads, norm, beta, row_max, row_off, with_max, st, g))) return rc;
+    if (total) {
+        fin.row_off = g.L->row_off(); fin.pairs = g.L->d_pairs;
+        launch_region_rows(n_regions, n_refs, fin.table_bytes, fin.row_off, drr, st);      // (now with the regions that have nothing to gather marked)
+        launch_apply_tiles_fin(2, sim_bytes, bin_shift, c->d_tbase, c->d_tidx, rows, many_records_of(c, expect), fin, st);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));                      // (before the scratch of this call goes)
+    return LIME_OK;
+}
+
+// scan + clusterAnalyze + clusterChoose, results on the host: the lists, copied out
+extern "C" int lime_fused_choose_dev(lime_ctx *c, const uint32_t *d_lcp, const uint32_t *d_da, const uint8_t *d_ebwt, uint64_t n,
+                                     uint32_t n_reads, uint32_t n_refs, uint32_t alpha, uint32_t norm, float beta,
+                                     uint8_t *row_max, uint64_t *row_off, lime_pair_t **pairs, uint64_t *n_pairs,
+                                     lime_stats_t *stats, void *stream)
+{
+    int rc = check_ctx(c, "lime_fused_choose_dev"); if (rc) return rc;
+    if (!pairs || !n_pairs || !row_off || !row_max) return fail(LIME_ERR_ARG, "lime_fused_choose_dev: NULL output");
+    if (!n_reads || !n_refs) return fail(LIME_ERR_ARG, "lime_fused_choose_dev: n_reads and n_refs must be > 0");
+    *pairs = nullptr; *n_pairs = 0; row_off[0] = 0;
+    hipStream_t st = (hipStream_t)stream;
+    ListsGuard g;
+    if ((rc = fused_choose_lists_impl(c, d_lcp, d_da, d_ebwt, n, n_reads, n_refs, alpha, norm, beta, row_max, row_off, false, stats, st, g))) return rc;
+    return lists_pairs_to_host(c, g.L, pairs, n_pairs, st);
+}
+
+extern "C" int lime_fused_choose_lists_dev(lime_ctx *c, const uint32_t *d_lcp, const uint32_t *d_da, const uint8_t *d_ebwt, uint64_t n,
+                                           uint32_t n_reads, uint32_t n_refs, uint32_t alpha, uint32_t norm, float beta, lime_lists **out,
+                                           lime_stats_t *stats, void *stream)
+{
+    int rc = check_ctx(c, "lime_fused_choose_lists_dev"); if (rc) return rc;
+    if (!out) return fail(LIME_ERR_ARG, "lime_fused_choose_lists_dev: NULL output");
+    *out = nullptr;
+    if (!n_reads || !n_refs) return fail(LIME_ERR_ARG, "lime_fused_choose_lists_dev: n_reads and n_refs must be > 0");
+    std::vector<uint8_t> mx((size_t)n_reads + 1);
+    std::vector<uint64_t> off((size_t)n_reads + 1);
+    ListsGuard g;
+    if ((rc = fused_choose_lists_impl(c, d_lcp, d_da, d_ebwt, n, n_reads, n_refs, alpha, norm, beta, mx.data(), off.data(), true, stats,
+                                      (hipStream_t)stream, g))) return rc;
+    *out = g.take();
+    return LIME_OK;
+}
+
+extern "C" int lime_lists_info(const lime_lists *L, uint32_t *n_reads, uint64_t *n_pairs, uint32_t *norm, float *beta)
+{
+    if (!L) return fail(LIME_ERR_ARG, "lime_lists_info: lists is NULL");
+    if (n_reads) *n_reads = L->n_reads;
+    if (n_pairs) *n_pairs = L->n_pairs;
+    if (norm) *norm = L->norm;
+    if (beta) *beta = L->beta;
+    return LIME_OK;
+}
+
+extern "C" int lime_lists_get(const lime_lists *L, uint8_t *row_max, uint64_t *row_off, lime_pair_t **pairs, uint64_t *n_pairs)
+{
+    if (!L) return fail(LIME_ERR_ARG, "lime_lists_get: lists is NULL");
+    if (!row_off || !pairs || !n_pairs || (L->n_reads && !row_max)) return fail(LIME_ERR_ARG, "lime_lists_get: NULL output");
+    int rc = check_ctx(L->ctx, "lime_lists_get"); if (rc) return rc;
+    HIP_TRY(hipMemcpy(row_off, L->row_off(), ((size_t)L->n_reads + 1) * 8, hipMemcpyDeviceToHost));
+    if (L->n_reads) HIP_TRY(hipMemcpy(row_max, L->row_max(), L->n_reads, hipMemcpyDeviceToHost));
+    return lists_pairs_to_host(L->ctx, L, pairs, n_pairs, nullptr);
+}
+
+extern "C" void lime_lists_free(lime_lists *L)
+{
+    if (!L) return;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(L->ctx->device);
+    lists_release(L);
+    (void)hipSetDevice(cur);
+}
+
+// ---- Classify on the device over lists in HBM (lime_classify_kernel.hip) -------------------------------------------------
+static std::mutex g_tax_mu;                              // a taxonomy's device copy is made on first use: contexts of several threads may share one
+static void taxonomy_release_dev(lime_taxonomy *tx)
+{
+    if (!tx->d_tab) return;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(tx->dev);
+    dev_release(tx->d_tab);
+    (void)hipSetDevice(cur);
+    tx->d_tab = nullptr; tx->dev = -1;
+}
+
+extern "C" int lime_classify_lists_dev(lime_ctx *c, uint32_t n_lists, const lime_lists *const *lists, uint32_t n_targ,
+                                       const lime_taxonomy *tx_in, int binary, lime_verdict_t *verdicts, uint64_t counts[4], void *stream)
+{
+    int rc = check_ctx(c, "lime_classify_lists_dev"); if (rc) return rc;
+    uint64_t local[4];
+    if (!counts) counts = local;
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (n_lists != 2 && n_lists != 4)
+        return fail(LIME_ERR_ARG, "lime_classify_lists_dev: n_lists is %u; the allowed number of lists is 2 (single-end reads) or 4 (paired-end reads)", n_lists);
+    if (!lists || !tx_in) return fail(LIME_ERR_ARG, "lime_classify_lists_dev: NULL argument");
+    for (uint32_t i = 0; i < n_lists; ++i) {
+        if (!lists[i]) return fail(LIME_ERR_ARG, "lime_classify_lists_dev: list %u is NULL", i);
+        if (lists[i]->ctx != c) return fail(LIME_ERR_ARG, "lime_classify_lists_dev: list %u belongs to another context", i);
+        if (lists[i]->n_reads != lists[0]->n_reads)
+            return fail(LIME_ERR_ARG, "lime_classify_lists_dev: the lists hold different numbers of reads (%u in list 0, %u in list %u)",
+                        lists[0]->n_reads, lists[i]->n_reads, i);
+    }
+    if (!n_targ || tx_in->n_targ != n_targ)
+        return fail(LIME_ERR_ARG, "lime_classify_lists_dev: the taxonomy holds %u genomes, numGenomes is %u", tx_in->n_targ, n_targ);
+    const uint32_t n_reads = lists[0]->n_reads;
+    if (!n_reads) return LIME_OK;
+    if (!verdicts) return fail(LIME_ERR_ARG, "lime_classify_lists_dev: verdicts is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    // the taxonomy's device copy, made once per device: at_rank[n_targ], then with HIGHER higher[6][n_targ]
+    lime_taxonomy *tx = const_cast<lime_taxonomy *>(tx_in);
+    std::lock_guard<std::mutex> tax_lock(g_tax_mu);           // (held for the call: a copy for another device replaces this one only after it)
+    if (tx->d_tab && tx->dev != c->device) taxonomy_release_dev(tx);
+    if (!tx->d_tab) {
+        const size_t words = (size_t)n_targ * (tx->higher ? 7u : 1u);
+        std::vector<uint32_t> h(words, 0u);
+        std::copy(tx->host.at_rank.begin(), tx->host.at_rank.end(), h.begin());
+        if (tx->higher)
+            for (int q = 0; q < lime_cls::N_RANKS; ++q) std::copy(tx->host.higher[q].begin(), tx->host.higher[q].end(), h.begin() + (size_t)(q + 1) * n_targ);
+        void *p = nullptr;
+        HIP_TRY(dev_acquire(&p, words * 4));
+        tx->d_tab = p; tx->dev = c->device; tx->release = taxonomy_release_dev;
+        HIP_TRY(hipMemcpy(p, h.data(), words * 4, hipMemcpyHostToDevice));
+    }
+    // per list the 256 values the writer's expression gives a count (and the record tops), built here so that the device divides nothing
+    std::vector<float> tabs(4 * 2 * 256, 0.0f);
+    for (uint32_t i = 0; i < n_lists; ++i) lime_cls::value_tables(lists[i]->norm, lists[i]->beta, binary, &tabs[i * 512], &tabs[i * 512 + 256]);
+    DevBuf dt, dv;
+    const size_t tab_bytes = tabs.size() * 4;
+    if ((rc = dt.alloc(tab_bytes + 16)) || (rc = dv.alloc((size_t)n_reads * sizeof(lime_verdict_t)))) return rc;
+    uint32_t *d_err = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(dt.p) + tab_bytes);
+    HIP_TRY(hipMemcpy(dt.p, tabs.data(), tab_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d_err, 0, 4, st));
+    ClsArgs a;
+    memset(&a, 0, sizeof a);
+    for (uint32_t i = 0; i < n_lists; ++i) { a.row_max[i] = lists[i]->row_max(); a.row_off[i] = lists[i]->row_off(); a.pairs[i] = lists[i]->d_pairs; }
+    a.tabs = static_cast<const float *>(dt.p);
+    a.at_rank = static_cast<const uint32_t *>(tx->d_tab);
+    a.higher = tx->higher ? a.at_rank + n_targ : nullptr;
+    a.n_lists = n_lists; a.n_reads = n_reads; a.n_targ = n_targ; a.rank_lo = tx->higher ? (uint32_t)(tx->rank - 1) : 6u;
+    a.out = static_cast<lime_verdict_t *>(dv.p); a.err = d_err;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c->timing) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, st)); }
+    launch_classify(a, st);
     HIP_TRY(hipGetLastError());
-    lime_pair_t *h = (lime_pair_t *)malloc((size_t)total * sizeof(lime_pair_t));
-    if (!h) return fail(LIME_ERR_NOMEM, "lime_fused_choose_dev: out of host memory");
-    if ((rc = d2h_pageable(c, h, dp.p, (size_t)total * sizeof(lime_pair_t), st))) { free(h); return rc; }
-    *pairs = h;
+    if (c->timing) HIP_TRY(hipEventRecord(e1, st));
+    uint32_t err = 0;
+    rc = d2h_pageable(c, verdicts, dv.p, (size_t)n_reads * sizeof(lime_verdict_t), st);
+    if (!rc && hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(LIME_ERR_HIP, "lime_classify_lists_dev: reading the error word");
+    if (c->timing) {
+        float ms = 0.0f;
+        if (!rc && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) c->cls_ms = ms;
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    }
+    if (rc) return rc;
+    if (err) return fail(LIME_ERR_ARG, "lime_classify_lists_dev: genome index beyond numGenomes (%u) in the lists", n_targ);
+    for (uint32_t r = 0; r < n_reads; ++r)
+        switch (verdicts[r].type) { case 'C': ++counts[0]; break; case 'U': ++counts[1]; break; case 'A': ++counts[2]; break; default: ++counts[3]; }
     return LIME_OK;
 }
 
@@ -2344,4 +2574,22 @@ extern "C" uint8_t lime_pair_score(const uint8_t cr[16], const uint8_t cg[16])
     uint32_t r[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0};
     for (int i = 0; i < 16; ++i) { r[i >> 2] |= (uint32_t)cr[i] << ((i & 3) * 8); g[i >> 2] |= (uint32_t)cg[i] << ((i & 3) * 8); }
     return (uint8_t)pair_score(r, g);
+}
+
+// lime_fused_choose_lists_dev from host arrays or mapped files (the drop-in LiME_paired): the arrays come in through the staging ring
+extern "C" int lime_fused_choose_lists(lime_ctx *c, const uint32_t *lcp, const uint32_t *da, const uint8_t *ebwt, uint64_t n,
+                                       uint32_t n_reads, uint32_t n_refs, uint32_t alpha, uint32_t norm, float beta, lime_lists **out,
+                                       lime_stats_t *stats)
+{
+    int rc = check_ctx(c, "lime_fused_choose_lists"); if (rc) return rc;
+    if (!out || (n && (!lcp || !da))) return fail(LIME_ERR_ARG, "lime_fused_choose_lists: NULL argument");
+    *out = nullptr;
+    DevBuf dl, dd, de;
+    if ((rc = dl.alloc(n * 4 + 16)) || (rc = dd.alloc(n * 4 + 16)) || (ebwt && (rc = de.alloc(n + 16)))) return rc;
+    const void *src[3] = {lcp, da, ebwt};
+    void *dst[3] = {dl.p, dd.p, de.p};
+    const size_t bytes[3] = {(size_t)n * 4, (size_t)n * 4, (size_t)n};
+    if ((rc = lime_internal_upload(ebwt ? 3 : 2, src, dst, bytes, nullptr))) return rc;
+    return lime_fused_choose_lists_dev(c, (const uint32_t *)dl.p, (const uint32_t *)dd.p, ebwt ? (const uint8_t *)de.p : nullptr, n, n_reads,
+                                       n_refs, alpha, norm, beta, out, stats, nullptr);
 }

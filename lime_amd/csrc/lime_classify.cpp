@@ -11,7 +11,8 @@
 //   3  else the same sums over ALL genomes; genomes within ERROR of the best: one taxon -> C,
 //      otherwise (HIGHER) the lowest higher rank they share -> H, or A        (:642-690, :168-302)
 // float arithmetic, the 0.02 tolerance and the text/binary difference (text values are the %.5f
-// roundings) are kept as they are.
+// roundings) are kept as they are.  read_taxonomy, value_tables, decide and write_verdict (lime_classify.h) are shared with
+// the device path (lime_api.cpp: lime_classify_lists_dev), lime_classify_mem runs decide over lists held in memory.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,30 +20,16 @@
 
 #include <fstream>
 #include <iostream>
+#include <new>
 #include <set>
 #include <sstream>
 #include <string>
 #include <vector>
 
 #include "lime_hip.h"
+#include "lime_classify.h"
 
-namespace {
-
-const float TOL = static_cast<float>(0.02);      // ERROR, src/Tools.h:37
-const int N_RANKS = 6;                           // species .. phylum (RANK, Classify.cpp:24)
-
-struct Cell { float sim; uint32_t ref; };
-struct ReadLists {                               // one read in one .res file
-    float top = 0.0f;                            // the file's maximum for the read (0: no record)
-    std::vector<Cell> cells;
-    void clear() { top = 0.0f; cells.clear(); }
-};
-
-struct Taxonomy {
-    std::vector<uint32_t> at_rank;               // genome -> taxon at the chosen rank (rank 0: genome index)
-    std::vector<std::vector<uint32_t>> higher;   // [rank-1 .. 5][genome], 0 = unknown (HIGHER)
-    std::string rank_name;
-};
+namespace lime_cls {
 
 // ';'-separated lineage file, first line a header (Classify.cpp:32-85).  As in the reference a last
 // line without a newline is not taken, and an empty field at the chosen rank is skipped.
@@ -74,6 +61,27 @@ bool read_taxonomy(const std::string &path, int rank, bool higher, uint32_t n_ta
     }
     return true;
 }
+
+void value_tables(uint32_t norm, float beta, int binary, float vals[256], float tops[256])
+{
+    for (uint32_t k = 0; k < 256u; ++k) {
+        const float v = static_cast<float>(static_cast<uint8_t>(k)) / norm;       // the writers' expression (lime_host.cpp)
+        float seen = v;
+        if (!binary) {                                                           // fprintf("%.5f") -> TxtSource's `>> float`
+            char buf[64];
+            snprintf(buf, sizeof buf, "%.5f", v);
+            std::istringstream is(buf);
+            if (!(is >> seen)) seen = 0.0f;
+        }
+        vals[k] = seen;
+        tops[k] = v > beta ? seen : 0.0f;
+    }
+}
+
+} // namespace lime_cls
+
+namespace {
+using namespace lime_cls;
 
 // ---- sources of the per-read lists ---------------------------------------------------------
 struct BinSource {                               // .res.bin + .res.pos (ClusterBWT_DA.cpp:376-436)
@@ -119,16 +127,26 @@ struct TxtSource {                               // .res.txt, one line per read 
     }
 };
 
-struct Verdict { char type; uint32_t taxon; float sim; };
+} // namespace
+
+namespace lime_cls {
 
 // value of genome g in a read's list (first match), 0 if absent
-float value_of(const ReadLists &l, uint32_t g)
+static float value_of(const ReadLists &l, uint32_t g)
 {
     for (const Cell &c : l.cells) if (c.ref == g) return c.sim;
     return 0.0f;
 }
 
-Verdict decide(const ReadLists *L, uint32_t n_files, uint32_t n_targ, const Taxonomy &tx, int rank, bool higher,
+static lime_verdict_t verdict(char type, uint32_t taxon, float sim, uint8_t rule)
+{
+    lime_verdict_t v;
+    memset(&v, 0, sizeof v);
+    v.taxon = taxon; v.sim = sim; v.type = (uint8_t)type; v.rule = rule;
+    return v;
+}
+
+lime_verdict_t decide(const ReadLists *L, uint32_t n_files, uint32_t n_targ, const Taxonomy &tx, int rank, bool higher,
                std::vector<float> (&all)[2])
 {
     // which files hold the read, and the best file maximum
@@ -136,7 +154,7 @@ Verdict decide(const ReadLists *L, uint32_t n_files, uint32_t n_targ, const Taxo
     bool any = false;
     for (uint32_t i = 0; i < n_files; ++i)
         if (L[i].top) { if (!any || L[i].top > best) best = L[i].top; any = true; }
-    if (!any) return Verdict{'U', 0u, 0.0f};
+    if (!any) return verdict('U', 0u, 0.0f, 0);
 
     // rule 1: candidates = genomes close to the maximum of every file that is close to the best
     std::vector<uint32_t> cand;
@@ -151,7 +169,7 @@ Verdict decide(const ReadLists *L, uint32_t n_files, uint32_t n_targ, const Taxo
     }
     std::set<uint32_t> taxa;
     for (uint32_t g : cand) taxa.insert(tx.at_rank[g]);
-    if (taxa.size() == 1) return Verdict{'C', *taxa.begin(), best};
+    if (taxa.size() == 1) return verdict('C', *taxa.begin(), best, 1);
 
     // rule 2: per-strand sums of the candidates
     {
@@ -172,7 +190,7 @@ Verdict decide(const ReadLists *L, uint32_t n_files, uint32_t n_targ, const Taxo
         if (win) {
             taxa.clear();
             for (size_t e = 0; e < cand.size(); ++e) if ((*win)[e] == wtop) taxa.insert(tx.at_rank[cand[e]]);
-            if (taxa.size() == 1) return Verdict{'C', *taxa.begin(), wtop};
+            if (taxa.size() == 1) return verdict('C', *taxa.begin(), wtop, 2);
         }
     }
 
@@ -198,20 +216,35 @@ Verdict decide(const ReadLists *L, uint32_t n_files, uint32_t n_targ, const Taxo
     if (hi[0] > hi[1]) { h = hi[0]; for (uint32_t j = 0; j < n_targ; ++j) if (h - all[0][j] < TOL) gens.push_back(j); }
     else if (hi[0] < hi[1]) { h = hi[1]; for (uint32_t j = 0; j < n_targ; ++j) if (h - all[1][j] < TOL) gens.push_back(j); }
     else { h = hi[0]; for (uint32_t j = 0; j < n_targ; ++j) if ((h - all[0][j] < TOL) || (h - all[1][j] < TOL)) gens.push_back(j); }
-    if (gens.empty()) return Verdict{'A', 0u, 0.0f};
+    if (gens.empty()) return verdict('A', 0u, 0.0f, 3);
     bool one = true;
     for (uint32_t g : gens) if (tx.at_rank[g] != tx.at_rank[gens[0]]) one = false;
-    if (one) return Verdict{'C', tx.at_rank[gens[0]], h};
+    if (one) return verdict('C', tx.at_rank[gens[0]], h, 3);
     if (higher && rank >= 1) {
         for (int idx = rank - 1; idx < N_RANKS; ++idx) {
             const uint32_t t = tx.higher[idx][gens[0]];
             bool same = true;
             for (uint32_t g : gens) if (tx.higher[idx][g] != t) { same = false; break; }
-            if (same && t != 0u) return Verdict{'H', t, h};
+            if (same && t != 0u) return verdict('H', t, h, 3);
         }
     }
-    return Verdict{'A', 0u, 0.0f};
+    return verdict('A', 0u, 0.0f, 3);
 }
+
+void write_verdict(std::ostream &out, uint64_t r, const lime_verdict_t &v, uint64_t counts[4])
+{
+    switch (v.type) {
+    case 'U': out << "U," << r << ",NA,0\n"; ++counts[1]; break;
+    case 'A': out << "A," << r << ",NA,0\n"; ++counts[2]; break;
+    case 'C': out << "C," << r << "," << v.taxon << "," << v.sim << "\n"; ++counts[0]; break;
+    default:  out << "H," << r << "," << v.taxon << "," << v.sim << "\n"; ++counts[3]; break;
+    }
+}
+
+} // namespace lime_cls
+
+namespace {
+using namespace lime_cls;
 
 template <typename Source>
 int run(uint32_t n_files, const char *const *inputs, uint32_t n_reads, uint32_t n_targ, const Taxonomy &tx, int rank,
@@ -228,13 +261,7 @@ int run(uint32_t n_files, const char *const *inputs, uint32_t n_reads, uint32_t 
         for (uint32_t i = 0; i < n_files; ++i)
             for (const Cell &c : L[i].cells)
                 if (c.ref >= n_targ) { err = std::string("genome index beyond numGenomes in ") + inputs[i]; return LIME_ERR_ARG; }
-        const Verdict v = decide(L, n_files, n_targ, tx, rank, higher, all);
-        switch (v.type) {
-        case 'U': out << "U," << r << ",NA,0\n"; ++counts[1]; break;
-        case 'A': out << "A," << r << ",NA,0\n"; ++counts[2]; break;
-        case 'C': out << "C," << r << "," << v.taxon << "," << v.sim << "\n"; ++counts[0]; break;
-        default:  out << "H," << r << "," << v.taxon << "," << v.sim << "\n"; ++counts[3]; break;
-        }
+        write_verdict(out, r, decide(L, n_files, n_targ, tx, rank, higher, all), counts);
     }
     return LIME_OK;
 }
@@ -270,4 +297,84 @@ extern "C" int lime_classify(uint32_t n_files, const char *const *inputs, int bi
                     : run<TxtSource>(n_files, inputs, n_reads, n_targ, tx, rank, higher != 0, out, counts, g_cls_err);
     out.close();
     return rc;
+}
+
+// ---- the same decision over lists held in memory, and the pieces the device path shares ------------------------------
+extern "C" int lime_taxonomy_load(const char *path, int rank, int higher, uint32_t n_targ, lime_taxonomy **out)
+{
+    if (!out || !path || rank < 0 || rank > N_RANKS || (higher && rank == 0)) {
+        g_cls_err = "lime_taxonomy_load: bad argument (rank 0..6; HIGHER needs a rank of 1 or more)";
+        return LIME_ERR_ARG;
+    }
+    *out = nullptr;
+    lime_taxonomy *t = new (std::nothrow) lime_taxonomy();
+    if (!t) { g_cls_err = "lime_taxonomy_load: out of host memory"; return LIME_ERR_NOMEM; }
+    if (!read_taxonomy(path, rank, higher != 0, n_targ, t->host, g_cls_err)) { delete t; return LIME_ERR_IO; }
+    if (t->host.at_rank.size() != n_targ) {
+        std::ostringstream m;
+        m << "Number of taxIDs = " << t->host.at_rank.size() << " lower than genome number: poor taxonomy information to classify.";
+        g_cls_err = m.str();
+        delete t;
+        return LIME_ERR_ARG;
+    }
+    t->rank = rank; t->higher = higher != 0; t->n_targ = n_targ;
+    *out = t;
+    return LIME_OK;
+}
+
+extern "C" void lime_taxonomy_free(lime_taxonomy *tx)
+{
+    if (!tx) return;
+    if (tx->release) tx->release(tx);            // (the device copy, if a device classification made one)
+    delete tx;
+}
+
+extern "C" int lime_write_classification(const char *path, const lime_verdict_t *verdicts, uint32_t n_reads)
+{
+    if (!path || (n_reads && !verdicts)) { g_cls_err = "lime_write_classification: NULL argument"; return LIME_ERR_ARG; }
+    std::ofstream out(path);
+    if (!out.is_open()) { g_cls_err = "ERROR: File Output not Open"; return LIME_ERR_IO; }
+    out << "C/U/A/H,IdSeqRead,TaxID,maxSim\n";
+    uint64_t counts[4] = {0, 0, 0, 0};
+    for (uint32_t r = 0; r < n_reads; ++r) write_verdict(out, r, verdicts[r], counts);
+    out.close();
+    if (out.fail()) { g_cls_err = std::string("Error writing ") + path; return LIME_ERR_IO; }
+    return LIME_OK;
+}
+
+extern "C" int lime_classify_mem(uint32_t n_files, const uint8_t *const *row_max, const uint64_t *const *row_off,
+                                 const lime_pair_t *const *pairs, const uint32_t *norms, const float *betas, int binary,
+                                 uint32_t n_reads, uint32_t n_targ, const lime_taxonomy *tx, lime_verdict_t *verdicts,
+                                 uint64_t counts[4])
+{
+    uint64_t local[4] = {0, 0, 0, 0};
+    if (!counts) counts = local;
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if ((n_files != 2 && n_files != 4) || !row_max || !row_off || !pairs || !norms || !betas || !tx || (n_reads && !verdicts)) {
+        g_cls_err = "lime_classify_mem: bad argument";
+        return LIME_ERR_ARG;
+    }
+    if (tx->n_targ != n_targ) { g_cls_err = "lime_classify_mem: the taxonomy was loaded for another number of genomes"; return LIME_ERR_ARG; }
+    float vals[4][256], tops[4][256];
+    for (uint32_t i = 0; i < n_files; ++i) {
+        if (!norms[i] || (n_reads && (!row_max[i] || !row_off[i]))) { g_cls_err = "lime_classify_mem: bad list"; return LIME_ERR_ARG; }
+        value_tables(norms[i], betas[i], binary, vals[i], tops[i]);
+    }
+    ReadLists L[4];
+    std::vector<float> all[2];
+    std::ostringstream sink;
+    for (uint32_t r = 0; r < n_reads; ++r) {
+        for (uint32_t i = 0; i < n_files; ++i) {
+            L[i].clear();
+            L[i].top = tops[i][row_max[i][r]];
+            for (uint64_t k = row_off[i][r]; k < row_off[i][r + 1]; ++k) {
+                const lime_pair_t p = pairs[i][k];
+                if (p.id_ref >= n_targ) { g_cls_err = "genome index beyond numGenomes in list " + std::to_string(i); return LIME_ERR_ARG; }
+                L[i].cells.push_back(Cell{vals[i][(uint8_t)p.sim], p.id_ref});
+            }
+        }
+        verdicts[r] = decide(L, n_files, n_targ, tx->host, tx->rank, tx->higher != 0, all);
+        switch (verdicts[r].type) { case 'C': ++counts[0]; break; case 'U': ++counts[1]; break; case 'A': ++counts[2]; break; default: ++counts[3]; }
+    }
+    return LIME_OK;
 }

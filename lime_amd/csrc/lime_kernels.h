@@ -162,4 +162,16 @@ void launch_fill_u32(uint32_t *p, size_t n, uint32_t v, hipStream_t st, uint32_t
 void launch_add_u64(uint64_t *p, size_t n, uint64_t v, hipStream_t st);             // p[i] += v (tests: LIME_P64_TEST_BASE)
 void launch_zero2(void *a, size_t a_bytes, void *b, size_t b_bytes, hipStream_t st);   // a: a multiple of 4 bytes; b: 16-byte aligned, a multiple of 16 bytes
 
+// the read-assignment decision over 2 or 4 lists in HBM (lime_classify_kernel.hip; lime_api.cpp lime_classify_lists_dev)
+struct ClsArgs {
+    const uint8_t *row_max[4]; const uint64_t *row_off[4]; const lime_pair_t *pairs[4];
+    const float *tabs;                              // [4][2][256]: per list the values of the counts 0..255 and the record tops (0: no record)
+    const uint32_t *at_rank;                        // [n_targ]: taxon at the chosen rank
+    const uint32_t *higher;                         // [6][n_targ] (HIGHER) or NULL
+    uint32_t n_lists, n_reads, n_targ, rank_lo;     // rank_lo: the first higher rank tried (the chosen rank - 1)
+    lime_verdict_t *out;                            // [n_reads]
+    uint32_t *err;                                  // |= 1: an idRef >= n_targ was met
+};
+void launch_classify(const ClsArgs &a, hipStream_t st);
+
 } // namespace lime
