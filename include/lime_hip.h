@@ -33,7 +33,11 @@ extern "C" {
 #define LIME_ERR_NOMEM    (-3)  /* host or device allocation failed                           */
 #define LIME_ERR_MAXLEN   (-4)  /* a cluster is longer than LIME_MAX_CLUSTER (ClusterBWT_DA.cpp:558-562) */
 #define LIME_ERR_HALO     (-5)  /* shard: a run owned by this shard does not close inside its halo       */
-#define LIME_ERR_DOCID    (-6)  /* a da value >= n_reads + n_refs was met while scoring       */
+#define LIME_ERR_DOCID    (-6)  /* a da value >= n_reads + n_refs was met while scoring.  Holds on every update path and
+                                 * for every cluster size, on all 32 bits of the value; no kernel of such a pass writes
+                                 * outside the buffers it was given (the table's contents are unspecified, but they are
+                                 * contents of the table); calls that do more after the pass return the error and hand
+                                 * out no lists, pairs or verdicts                                                    */
 #define LIME_ERR_IO       (-7)  /* file I/O (CLI helpers)                                     */
 
 #define LIME_MAX_CLUSTER  65536u /* Tools.h:33 sizeMaxBuf */
@@ -339,6 +343,22 @@ int  lime_score_choose_multi(int n_dev, const int *devices, const uint32_t *da, 
 /* ---- pure host helpers (no device work; used by the CLIs and by CPU-side tests) -------- */
 uint8_t lime_sym_index(uint8_t byte);                              /* ClusterBWT_DA.cpp:455-470 */
 uint8_t lime_pair_score(const uint8_t cr[16], const uint8_t cg[16]); /* :129-177, host build of the device routine */
+
+/* The update records of the binned path, as the scan writes them and the partition kernels bin them (one definition,
+ * lime_device.h).  cell = read * n_refs + genome index; record = the cell's low 32 bits, sub-region = its high part,
+ * bin = cell >> bin_shift.  lime_rec_layout: the layout a table of that shape gets (one_level = two_level = 0: the
+ * defaults, else as LIME_BIN_LEVELS).  lime_rec_valid: the test every genome index (da - n_reads) passes, on all 32 bits,
+ * before anything is stored for it.  lime_rec_batch: what the scan stores for each of n pairs -- nothing for an index that
+ * fails the test, or (fixed_slot: a slot handed out before the test, one sub-region) a stand-in record inside the table --
+ * and the bin the partition kernels compute for it. */
+typedef struct { uint32_t n_bins, bin_shift, n_sub, sub_rb, sub_gb; } lime_rec_layout_t;
+int      lime_rec_layout(uint32_t n_reads, uint32_t n_refs, uint32_t one_level, uint32_t two_level, lime_rec_layout_t *out);
+int      lime_rec_valid(uint32_t gd, uint32_t n_refs);
+uint32_t lime_rec_of(uint32_t rd, uint32_t gd, uint32_t n_refs);
+uint32_t lime_rec_sub2(uint32_t rd, uint32_t gd, uint32_t sub_rb, uint32_t sub_gb);
+uint32_t lime_rec_bin(uint32_t rec, uint32_t sub, uint32_t bin_shift);
+int      lime_rec_batch(const uint32_t *rd, const uint32_t *gd, uint64_t n, uint32_t n_refs, const lime_rec_layout_t *layout,
+                        int fixed_slot, uint8_t *valid, uint8_t *stored, uint32_t *rec, uint32_t *sub, uint32_t *bin);
 
 /* Writers of the reference's files (byte-identical formats). */
 int lime_write_clrs(const char *path, const lime_cluster_t *clusters, uint64_t n_clusters); /* ClusterLCP.cpp:229-235 */

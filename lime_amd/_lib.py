@@ -74,6 +74,12 @@ SYMBOLS = {
     "lime_get_host_times": (_i, [_vp, C.POINTER(C.c_double)]),
     "lime_sym_index": (C.c_uint8, [C.c_uint8]),
     "lime_pair_score": (C.c_uint8, [_vp, _vp]),
+    "lime_rec_layout": (_i, [_u32, _u32, _u32, _u32, _vp]),
+    "lime_rec_valid": (_i, [_u32, _u32]),
+    "lime_rec_of": (_u32, [_u32, _u32, _u32]),
+    "lime_rec_sub2": (_u32, [_u32, _u32, _u32, _u32]),
+    "lime_rec_bin": (_u32, [_u32, _u32, _u32]),
+    "lime_rec_batch": (_i, [_vp, _vp, _u64, _u32, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "lime_write_clrs": (_i, [C.c_char_p, _vp, _u64]),
     "lime_write_aux": (_i, [C.c_char_p, _u32, _u32, _u32, _u64, _u64]),
     "lime_read_aux": (_i, [C.c_char_p, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), _pu64, _pu64]),

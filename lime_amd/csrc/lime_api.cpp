@@ -735,24 +735,24 @@ static int ensure_binned(lime_ctx *c, uint64_t n_own, uint32_t n_waves, uint32_t
 // The table's bins for the binned update path: one bin per 64 KB region for small tables; else as few levels of fan-out
 // as fit: at most 2048 bins of 2^k regions (the bins' open output lines then merge in the L2), more bins only when k would
 // pass its limit.  A pure function of the table's size (and LIME_BIN_LEVELS): every rank of an exchange gets the same.
-static void bin_layout(const lime_ctx *c, size_t sim_bytes, uint32_t *n_bins, uint32_t *bin_shift_out)
+static void bin_layout_of(uint32_t one_level, uint32_t two_level, bool levels_forced, size_t sim_bytes, uint32_t *n_bins, uint32_t *bin_shift_out)
 {
     uint32_t bin_shift = REGION_SHIFT;
     auto bins_at = [&](uint32_t sh) { return (sim_bytes + ((size_t)1 << sh) - 1) >> sh; };
     const uint32_t bmax = BIN_MAX;                        // what the scan's LDS histogram holds
-    const uint32_t one = c->bin_one_level < bmax ? c->bin_one_level : bmax, two = c->bin_two_level < bmax ? c->bin_two_level : bmax;
+    const uint32_t one = one_level < bmax ? one_level : bmax, two = two_level < bmax ? two_level : bmax;
     if (bins_at(bin_shift) > one) {
         while ((bins_at(bin_shift) > two && bin_shift < BIN_SHIFT_MAX) || bins_at(bin_shift) > bmax) ++bin_shift;
         // fewer, wider bins while that leaves at least 256 of them and at most 64 regions per bin: measured on a 1 GB
         // table (N = 10^10) 477 bins of 32 regions beat 1908 of 8 by 1 ms in 11; a 5 GB table keeps its 1193 bins of 64
-        if (!c->bin_levels_forced)
+        if (!levels_forced)
             while (bin_shift < REGION_SHIFT + 6 && bin_shift < BIN_SHIFT_MAX && bins_at(bin_shift + 1) >= 256) ++bin_shift;
         // Round 6: wider bins still where that brings the table under LINES_BINS bins -- k_part_lines (whole 64-byte lines, two workgroups per CU) then
         // does the first level instead of k_part (pieces of lines: 2 against 3.4 TB/s), and since k_apply_tiles shares a wave among short runs the
         // second level no longer pays for the regions per bin: configs[2] (5 GB: 1193 bins of 64 regions -> 299 of 256) 3.10 -> 2.95 ms per pass,
         // configs[4]'s shape (10.3 GB: 1229 of 128 -> 308 of 512) clustered 31.8 -> 31.0 ms.  Tables beyond 477 x 32 MB = 16 GB keep what they had.
         constexpr uint32_t LINES_BINS = 477;                 // (what fits a CU twice, 32- and 64-bit positions: tools/kres.py gates it)
-        if (!c->bin_levels_forced && bins_at(bin_shift) > LINES_BINS) {
+        if (!levels_forced && bins_at(bin_shift) > LINES_BINS) {
             uint32_t sh = bin_shift;
             while (sh < BIN_SHIFT_MAX && bins_at(sh) > LINES_BINS) ++sh;
             if (bins_at(sh) <= LINES_BINS) bin_shift = sh;
@@ -760,6 +760,17 @@ static void bin_layout(const lime_ctx *c, size_t sim_bytes, uint32_t *n_bins, ui
     }
     *n_bins = (uint32_t)bins_at(bin_shift);               // <= BIN_MAX: want_binned checked the table size
     *bin_shift_out = bin_shift;
+}
+static void bin_layout(const lime_ctx *c, size_t sim_bytes, uint32_t *n_bins, uint32_t *bin_shift_out)
+{
+    bin_layout_of(c->bin_one_level, c->bin_two_level, c->bin_levels_forced, sim_bytes, n_bins, bin_shift_out);
+}
+// the sub-regions of a table (4 GB each) and, for two of them, the first cell of the second as (read, genome index)
+static void sub_layout(size_t sim_bytes, uint32_t n_refs, uint32_t *n_sub, uint32_t *sub_rb, uint32_t *sub_gb)
+{
+    *n_sub = (uint32_t)((sim_bytes + 0xFFFFFFFFull) >> 32);
+    *sub_rb = 0xFFFFFFFFu; *sub_gb = 0u;
+    if (*n_sub == 2) { *sub_rb = (uint32_t)((1ull << 32) / n_refs); *sub_gb = (uint32_t)((1ull << 32) - (uint64_t)*sub_rb * n_refs); }
 }
 
 static int read_stats(lime_ctx *c, lime_stats_t *s, hipStream_t st, uint32_t *sticky = nullptr);
@@ -781,7 +792,9 @@ static int density_probe(lime_ctx *c, const uint32_t *d_lcp, const uint32_t *d_d
     const uint32_t ps = n_own < (1ull << 30) ? 6u : n_own < (1ull << 32) ? 7u : 8u;
     uint32_t n_bins = 0, bin_shift = REGION_SHIFT;
     bin_layout(c, sim_bytes, &n_bins, &bin_shift);
-    const uint32_t n_sub = (uint32_t)((sim_bytes + 0xFFFFFFFFull) >> 32), wpw = scan_waves_per_wg(ebwt, 0);
+    uint32_t n_sub = 1, sub_rb = 0xFFFFFFFFu, sub_gb = 0u;
+    sub_layout(sim_bytes, n_refs, &n_sub, &sub_rb, &sub_gb);
+    const uint32_t wpw = scan_waves_per_wg(ebwt, 0);
     const uint32_t grid = scan_grid(ebwt, 0, bin_mode(c, n_sub), n_tiles, c->max_blocks, ps);
     const uint32_t prod_waves = part_prod_waves(c, ebwt, n_bins), n_prod = grid * (wpw / prod_waves);
     g_alloc_ms = 0.0;
@@ -793,8 +806,7 @@ static int density_probe(lime_ctx *c, const uint32_t *d_lcp, const uint32_t *d_d
     a.upd_mode = 1; a.pool = reinterpret_cast<uint32_t *>(c->d_stats);       // (never written: no slot is below a capacity of 0)
     a.cap_w = 0; a.n_sub = n_sub; a.wave_cnt = c->d_wave_cnt; a.counts = c->d_counts;
     a.n_bins = n_bins; a.bin_shift = bin_shift; a.prod_waves = prod_waves;
-    a.sub_rb = 0xFFFFFFFFu; a.sub_gb = 0u;
-    if (n_sub == 2) { a.sub_rb = (uint32_t)((1ull << 32) / n_refs); a.sub_gb = (uint32_t)((1ull << 32) - (uint64_t)a.sub_rb * n_refs); }
+    a.sub_rb = sub_rb; a.sub_gb = sub_gb;
     a.probe_shift = ps; a.static_pct = 100u;
     launch_tile(ebwt, 0, a, c->max_blocks, st);
     HIP_TRY(hipGetLastError());
@@ -847,12 +859,12 @@ static int fused_dev_impl(lime_ctx *c, const uint32_t *d_lcp, const uint32_t *d_
         if ((rc = density_probe(c, d_lcp, d_da, d_ebwt, n_own, n_avail, eof, n_reads, n_refs, alpha, sim_bytes, st))) return rc;
     bool binned = n_avail && !no_bin && want_binned(c, n_own, sim_bytes, zero_sim, keep_stats, ebwt);
     if (records_only) binned = true;                      // the records ARE the result: the binned path or nothing
-    uint32_t grid = 0, cap_w = 0, n_bins = 0, bin_shift = REGION_SHIFT, n_sub = 1, prod_waves = 0, n_prod = 0;
+    uint32_t grid = 0, cap_w = 0, n_bins = 0, bin_shift = REGION_SHIFT, n_sub = 1, sub_rb = 0xFFFFFFFFu, sub_gb = 0u, prod_waves = 0, n_prod = 0;
     bool p64 = false, fell_back = false;
     const double share = sub_share(sim_bytes);
     if (binned) {
         bin_layout(c, sim_bytes, &n_bins, &bin_shift);
-        n_sub = (uint32_t)((sim_bytes + 0xFFFFFFFFull) >> 32);
+        sub_layout(sim_bytes, n_refs, &n_sub, &sub_rb, &sub_gb);
         grid = scan_grid(ebwt, 0, bin_mode(c, n_sub), n_tiles, c->max_blocks);
         prod_waves = part_prod_waves(c, ebwt, n_bins);
         n_prod = grid * (scan_waves_per_wg(ebwt, 0) / prod_waves);
@@ -897,8 +909,7 @@ static int fused_dev_impl(lime_ctx *c, const uint32_t *d_lcp, const uint32_t *d_
     if (binned) {
         a.upd_mode = 1; a.pool = c->d_pool; a.cap_w = cap_w; a.n_sub = n_sub; a.wave_cnt = c->d_wave_cnt; a.counts = c->d_counts;
         a.n_bins = n_bins; a.bin_shift = bin_shift; a.prod_waves = prod_waves;
-        a.sub_rb = 0xFFFFFFFFu; a.sub_gb = 0u;
-        if (n_sub == 2) { a.sub_rb = (uint32_t)((1ull << 32) / n_refs); a.sub_gb = (uint32_t)((1ull << 32) - (uint64_t)a.sub_rb * n_refs); }
+        a.sub_rb = sub_rb; a.sub_gb = sub_gb;
     }
     if (records_only) { a.sim = nullptr; a.bigrec = c->d_bigrec; a.bigrec_n = c->d_bigrec_n; a.bigrec_cap = c->bigrec_cap; }
     if ((rc = timing_mark(c, st))) return rc;
@@ -1281,12 +1292,10 @@ static int score_dev_impl(lime_ctx *c, const uint32_t *d_da, const uint8_t *d_eb
         if (binned) {
             if (blocks > 1024u) blocks = 1024u;           // fewer, longer producers: a partition workgroup per scoring workgroup
             bin_layout(c, sim_bytes, &n_bins, &bin_shift);
-            n_sub = (uint32_t)((sim_bytes + 0xFFFFFFFFull) >> 32);
+            sub_layout(sim_bytes, n_refs, &n_sub, &a.sub_rb, &a.sub_gb);
             if ((rc = ensure_binned(c, n, blocks * (SCAN_WG / 64), blocks, n_bins, bin_shift, n_sub, sub_share(sim_bytes), &cap_w, &p64, st))) return rc;
             a.upd_mode = 1; a.pool = c->d_pool; a.cap_w = cap_w; a.n_sub = n_sub; a.wave_cnt = c->d_wave_cnt; a.counts = c->d_counts;
             a.n_bins = n_bins; a.bin_shift = bin_shift; a.prod_waves = SCAN_WG / 64;
-            a.sub_rb = 0xFFFFFFFFu; a.sub_gb = 0u;
-            if (n_sub == 2) { a.sub_rb = (uint32_t)((1ull << 32) / n_refs); a.sub_gb = (uint32_t)((1ull << 32) - (uint64_t)a.sub_rb * n_refs); }
         }
         launch_score_list(ebwt, a, d_clusters, n_clusters, blocks, st);
         if (binned) {
@@ -2574,6 +2583,38 @@ extern "C" uint8_t lime_pair_score(const uint8_t cr[16], const uint8_t cg[16])
     uint32_t r[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0};
     for (int i = 0; i < 16; ++i) { r[i >> 2] |= (uint32_t)cr[i] << ((i & 3) * 8); g[i >> 2] |= (uint32_t)cg[i] << ((i & 3) * 8); }
     return (uint8_t)pair_score(r, g);
+}
+
+// The update records' arithmetic (lime_device.h) and the layout a table of n_reads x n_refs gets, without a device:
+// what the scan stores for a scored pair and where the partition kernels put it.
+extern "C" int lime_rec_layout(uint32_t n_reads, uint32_t n_refs, uint32_t one_level, uint32_t two_level, lime_rec_layout_t *out)
+{
+    if (!n_reads || !n_refs || !out) return fail(LIME_ERR_ARG, "lime_rec_layout: bad argument");
+    const size_t sim_bytes = lime_sim_bytes(n_reads, n_refs);
+    if (sim_bytes > ((size_t)BIN_MAX << BIN_SHIFT_MAX) || sim_bytes >= (1ull << CELL_BITS) || sim_bytes > ((uint64_t)MAX_SUB << 32))
+        return fail(LIME_ERR_ARG, "lime_rec_layout: table too large for update records");
+    const bool forced = one_level && two_level;                       // as LIME_BIN_LEVELS="a,b"
+    bin_layout_of(forced ? one_level : BIN_ONE_LEVEL, forced ? two_level : BIN_TWO_LEVEL, forced, sim_bytes, &out->n_bins, &out->bin_shift);
+    sub_layout(sim_bytes, n_refs, &out->n_sub, &out->sub_rb, &out->sub_gb);
+    return LIME_OK;
+}
+extern "C" int lime_rec_valid(uint32_t gd, uint32_t n_refs) { return genome_ok(gd, n_refs) ? 1 : 0; }
+extern "C" uint32_t lime_rec_of(uint32_t rd, uint32_t gd, uint32_t n_refs) { return rec_of(rd, gd, n_refs); }
+extern "C" uint32_t lime_rec_sub2(uint32_t rd, uint32_t gd, uint32_t sub_rb, uint32_t sub_gb) { return rec_sub2(rd, gd, sub_rb, sub_gb); }
+extern "C" uint32_t lime_rec_bin(uint32_t rec, uint32_t sub, uint32_t bin_shift) { return rec_bin(rec, sub, bin_shift); }
+// What the scan stores for each pair (read rd[i], genome index gd[i]) and where the partition kernels put it: valid[i] = genome_ok;
+// stored[i] = 0: nothing (the pass ends in LIME_ERR_DOCID), else rec[i] / sub[i] = the record and its sub-region, bin[i] = rec_bin of them.
+// `fixed_slot`: the pair's slot was given out before its id was looked at (score_small3, one sub-region): a bad id leaves the stand-in.
+extern "C" int lime_rec_batch(const uint32_t *rd, const uint32_t *gd, uint64_t n, uint32_t n_refs, const lime_rec_layout_t *lay, int fixed_slot,
+                              uint8_t *valid, uint8_t *stored, uint32_t *rec, uint32_t *sub, uint32_t *bin)
+{
+    if (!lay || !n_refs || (n && (!rd || !gd || !valid || !stored || !rec || !sub || !bin))) return fail(LIME_ERR_ARG, "lime_rec_batch: bad argument");
+    for (uint64_t i = 0; i < n; ++i) {
+        valid[i] = genome_ok(gd[i], n_refs);
+        stored[i] = rec_stored(rd[i], gd[i], n_refs, lay->n_sub, lay->sub_rb, lay->sub_gb, fixed_slot != 0, rec[i], sub[i]);
+        bin[i] = rec_bin(rec[i], sub[i], lay->bin_shift);
+    }
+    return LIME_OK;
 }
 
 // lime_fused_choose_lists_dev from host arrays or mapped files (the drop-in LiME_paired): the arrays come in through the staging ring

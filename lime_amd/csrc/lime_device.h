@@ -159,6 +159,44 @@ LIME_HD void hist_add(uint32_t (&w)[4], uint32_t s, uint32_t on)
     w[3] += (k == 3u) ? inc : 0u;
 }
 
+// ---- update records of the binned path: the one definition the scan (which writes them) and the partition kernels
+// (which bin them again) share; lime_rec_* in include/lime_hip.h export them for the CPU tests.
+// A table cell is read * n_refs + genome index; a record is the cell's LOW 32 bits, the high part picks the sub-region
+// (4 GB of table each) it is stored in; bin = cell >> bin_shift.
+// genome_ok: the validity test of a genome index gd = da - n_reads, on all 32 bits.  Nothing that fails it may become a
+// record or a queue entry: a pass that meets one ends in LIME_ERR_DOCID, and where a slot has already been given out
+// the stand-in record below fills it.
+LIME_HD bool genome_ok(uint32_t gd, uint32_t n_refs) { return gd < n_refs; }
+LIME_HD uint32_t rec_of(uint32_t rd, uint32_t gd, uint32_t n_refs) { return rd * n_refs + gd; }
+// tables of two sub-regions: (sub_rb, sub_gb) = the first cell of sub-region 1 as (read, genome index)
+LIME_HD uint32_t rec_sub2(uint32_t rd, uint32_t gd, uint32_t sub_rb, uint32_t sub_gb)
+{
+    return (rd > sub_rb || (rd == sub_rb && gd >= sub_gb)) ? 1u : 0u;
+}
+LIME_HD uint32_t rec_bin_off(uint32_t sub, uint32_t bin_shift) { return sub << (32u - bin_shift); }      // bin_shift >= 16
+LIME_HD uint32_t rec_bin_at(uint32_t rec, uint32_t bin_shift, uint32_t bin_off) { return (rec >> bin_shift) + bin_off; }
+LIME_HD uint32_t rec_bin(uint32_t rec, uint32_t sub, uint32_t bin_shift) { return rec_bin_at(rec, bin_shift, rec_bin_off(sub, bin_shift)); }
+constexpr uint32_t REC_STAND_IN = 0u;            // cell 0 of sub-region 0: inside every table
+// A slot handed out before the id was looked at (score_small3: the prefix sum over the pair lists) is filled whatever the id:
+// with the pair's record / queue entry, or with a stand-in that touches nothing outside the table (record 0; an entry that adds 0).
+LIME_HD uint32_t rec_or_stand_in(bool ok, uint32_t rd, uint32_t gd, uint32_t n_refs) { return ok ? rec_of(rd, gd, n_refs) : REC_STAND_IN; }
+LIME_HD uint32_t entry_or_stand_in(bool ok, uint32_t gd, uint32_t t_shift) { return ok ? gd | (1u << t_shift) : 0u; }
+// tables of three and more sub-regions (drain_bin): the whole cell, its sub-region and its bin
+LIME_HD uint64_t cell_of(uint32_t rd, uint32_t gd, uint32_t n_refs) { return (uint64_t)rd * n_refs + gd; }
+LIME_HD uint32_t cell_sub(uint64_t cell) { return (uint32_t)(cell >> 32); }
+LIME_HD uint32_t cell_bin(uint64_t cell, uint32_t bin_shift) { return (uint32_t)(cell >> bin_shift); }
+// Whether the scan stores anything for a pair, what, and in which sub-region of a table of n_sub of them (sub_rb / sub_gb: rec_sub2): the
+// one statement of the policy above, for the host-side check of the bound (lime_rec_batch).  fixed_slot: as rec_or_stand_in -- only the
+// scorers of one-sub-region tables hand slots out in advance, everywhere else a bad id leaves nothing.
+LIME_HD bool rec_stored(uint32_t rd, uint32_t gd, uint32_t n_refs, uint32_t n_sub, uint32_t sub_rb, uint32_t sub_gb, bool fixed_slot,
+                        uint32_t &rec, uint32_t &sub)
+{
+    const bool ok = genome_ok(gd, n_refs);
+    rec = rec_or_stand_in(ok, rd, gd, n_refs);
+    sub = !ok || n_sub == 1u ? 0u : n_sub == 2u ? rec_sub2(rd, gd, sub_rb, sub_gb) : cell_sub(cell_of(rd, gd, n_refs));
+    return ok || (fixed_slot && n_sub == 1u);
+}
+
 // splitmix64 finaliser; synthetic inputs of SURVEY.md 8(d) (identical to oracle/lime_oracle.c)
 LIME_HD uint64_t mix64(uint64_t z)
 {

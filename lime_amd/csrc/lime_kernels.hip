@@ -266,11 +266,20 @@ struct UpdQueue { uint32_t *qr, *qg; uint32_t n, cap;
     uint32_t n1 = 0, base0 = 0, base1 = 0;                 // records waiting in qg[]; records stored so far per sub-region (wave-uniform)
     uint32_t sub_rb = 0xFFFFFFFFu, sub_gb = 0;             // where sub-region 1 begins (read, genome); sub_rb = ~0: one sub-region
     __device__ __forceinline__ bool two() const { return sub_rb != 0xFFFFFFFFu; }
-    uint32_t bad = 0;                                      // per lane: a genome index beyond the table was met (LIME_FLAG_DOCID at the next flush)
+    uint32_t bad = 0;                                      // per lane: a genome index beyond the table was met (LIME_FLAG_DOCID at the next flush / window top)
 #ifdef LIME_PHASE_TIMING
     uint64_t t_drain = 0; uint32_t n_drain = 0;
 #endif
 };
+
+// The scorers that write queue entries or records themselves pass every genome index through genome_ok (lime_device.h, all 32 bits) first:
+// the lanes with `hit` are about to store one whose validity is `ok`.  A bad one is noted for report_bad and NOT stored -- no drain, flush or
+// partition kernel ever sees a genome index beyond the table (the drains' own tests on the masked index are a second line only).
+__device__ __forceinline__ bool checked(UpdQueue &q, bool hit, bool ok) { q.bad |= (uint32_t)(hit && !ok); return hit && ok; }
+__device__ __forceinline__ void report_bad(UpdQueue &q, const ScanArgs &a)
+{
+    if (__ballot(q.bad != 0u)) { if (q.bad) atomicOr(&cold(a).stats->flags, LIME_FLAG_DOCID); q.bad = 0u; }
+}
 
 // The wave's region of the record pool (n_sub sub-regions of cap_w records), recomputed where it is needed from the kernel's arguments and the wave's number
 __device__ __forceinline__ uint32_t *pool_of(const ScanArgs &ca, uint32_t n_sub, uint32_t cap_w)
@@ -312,7 +321,7 @@ __device__ __forceinline__ void drain_async(UpdQueue &q, const ScanArgs &a)
         if (fre && r < n) {
             const uint32_t k = n - 1u - r;
             const uint32_t gt = q.qg[k];
-            if ((gt & ((1u << T_SHIFT) - 1u)) >= a.n_refs) atomicOr(&cold(a).stats->flags, LIME_FLAG_DOCID);   // dropped: see drain_bin
+            if ((gt & ((1u << T_SHIFT) - 1u)) >= a.n_refs) atomicOr(&cold(a).stats->flags, LIME_FLAG_DOCID);   // (a second line, like drain_bin's: the writers of the entries test the whole index)
             else {
                 q.fr[64u * (uint32_t)j + lane] = q.qr[k]; q.fg[64u * (uint32_t)j + lane] = gt;
                 q.fe[64u * (uint32_t)j + lane] = 0u;
@@ -350,7 +359,7 @@ __device__ __forceinline__ void drain_lines(UpdQueue &q, const ScanArgs &a, bool
     const uint32_t lane = lane_id();
     const uint32_t n = q.n;
     const ScanArgs &ca = cold(a);                                 // the fields a drain needs are loaded here, not held through the window loop
-    const uint32_t cap_w = ca.cap_w, bin_shift = ca.bin_shift, n_sub = ca.n_sub, sub_rb = ca.sub_rb, sub_gb = ca.sub_gb, n_refs = ca.n_refs;
+    const uint32_t cap_w = ca.cap_w, bin_shift = ca.bin_shift, sub_rb = ca.sub_rb, sub_gb = ca.sub_gb, n_refs = ca.n_refs;
     uint32_t f0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.lfill[0]), f1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.lfill[1]);
     const uint32_t hoff = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.sub_n[MAX_SUB]);
     auto flush = [&](uint32_t sub, uint32_t &f, uint32_t keep_mask) {      // keep_mask = 15: whole lines only; 0: everything
@@ -361,7 +370,7 @@ __device__ __forceinline__ void drain_lines(UpdQueue &q, const ScanArgs &a, bool
         const uint32_t rec = lb[lane < nl ? lane : 0u];
         const uint32_t slot = base + lane;
         if (lane < nl && slot < cap_w && !ABL(7)) {               // a full sub-region only counts (sub_n): the pass is repeated with a larger pool
-            const uint32_t bin = n_sub == 1u ? rec >> bin_shift : (rec >> bin_shift) | (sub << (32u - bin_shift));
+            const uint32_t bin = rec_bin(rec, sub, bin_shift);
             atomicAdd(&q.hist[hoff + bin], 1u);                   // the histogram counts exactly the records that are stored
             if (!ABL(6)) __builtin_nontemporal_store(rec, q.out + (size_t)sub * cap_w + slot);
         }
@@ -376,12 +385,12 @@ __device__ __forceinline__ void drain_lines(UpdQueue &q, const ScanArgs &a, bool
         const bool on = k < n;
         const uint32_t gt = q.qg[on ? k : 0u], rd = q.qr[on ? k : 0u];
         const uint32_t g = gt & (MAX_REFS - 1u);
-        // the scan's fast emitters do not look at the document ids: a genome id beyond the table is caught here, on
-        // full waves (the entry is dropped; the pass fails with LIME_ERR_DOCID)
+        // (a second line: every writer of queue entries passes its genome index through genome_ok first, so no entry beyond the
+        // table gets here; one that did would be dropped and the pass fail with LIME_ERR_DOCID)
         const bool bad = on && g >= n_refs;
         if (__ballot(bad)) { if (bad) atomicOr(&cold(a).stats->flags, LIME_FLAG_DOCID); }
-        const uint32_t rec = rd * n_refs + g;                     // the cell's low 32 bits
-        const bool hi = rd > sub_rb || (rd == sub_rb && g >= sub_gb);
+        const uint32_t rec = rec_of(rd, g, n_refs);               // the cell's low 32 bits
+        const bool hi = rec_sub2(rd, g, sub_rb, sub_gb) != 0u;
         uint32_t left = (on && !bad) ? gt >> T_SHIFT : 0u;
         while (__ballot(left != 0u)) {                            // once, unless a pair scored more than 1
             const bool act = left != 0u;
@@ -411,7 +420,7 @@ __device__ __forceinline__ void flush_direct(UpdQueue &q, const ScanArgs &a, boo
     const ScanArgs &ca = cold(a);
     const uint32_t cap_w = ca.cap_w, bin_shift = ca.bin_shift, n_sub = ca.n_sub, bin_lim = ca.n_bins;
     const uint32_t hoff = ((uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) / ca.prod_waves) * bin_lim;     // the producer group's part of the workgroup's histogram
-    if (__ballot(q.bad != 0u)) { if (q.bad) atomicOr(&cold(a).stats->flags, LIME_FLAG_DOCID); q.bad = 0u; }
+    report_bad(q, a);
     uint32_t *const out = pool_of(ca, n_sub, cap_w);
 #pragma unroll
     for (uint32_t sub = 0; sub < 2u; ++sub) {
@@ -424,8 +433,8 @@ __device__ __forceinline__ void flush_direct(UpdQueue &q, const ScanArgs &a, boo
             const uint32_t k = k0 + lane;
             const bool on = k < nl;
             const uint32_t rec = buf[on ? k : 0u], slot = base + k;
-            uint32_t bin = (rec >> bin_shift) | (sub << (32u - bin_shift));
-            bin = bin < bin_lim ? bin : bin_lim - 1u;                // (only a pass that fails with LIME_ERR_DOCID can get here with a cell beyond the table)
+            uint32_t bin = rec_bin(rec, sub, bin_shift);
+            bin = bin < bin_lim ? bin : bin_lim - 1u;                // (a second line: the scorers store no record of a cell beyond the table)
             if (on && slot < cap_w && !ABL(7)) {                     // a full sub-region only counts: the pass is repeated with a larger pool
                 atomicAdd(&q.hist[hoff + bin], 1u);                  // the histogram counts exactly the records that are stored
                 if (!ABL(6)) __builtin_nontemporal_store(rec, out + (size_t)sub * cap_w + slot);
@@ -439,11 +448,11 @@ __device__ __forceinline__ void flush_direct(UpdQueue &q, const ScanArgs &a, boo
 }
 
 // direct mode: the lanes with `hit` append the record of (read rd, genome index gd), t = 1.  All 64 lanes call.
+// The callers have taken the lanes whose gd fails genome_ok out of `hit` (checked()): every record stored is a cell of the table.
 __device__ __forceinline__ void put_rec(UpdQueue &q, const ScanArgs &a, bool hit, uint32_t rd, uint32_t gd)
 {
     if (ABL(13)) return;
-    const uint32_t rec = rd * a.n_refs + gd;                         // the cell's low 32 bits
-    q.bad |= (uint32_t)(hit && gd >= a.n_refs);
+    const uint32_t rec = rec_of(rd, gd, a.n_refs);                   // the cell's low 32 bits
     if (!q.two()) {
         const uint64_t m = __ballot(hit);
         const uint32_t tot = (uint32_t)__popcll(m);
@@ -451,7 +460,7 @@ __device__ __forceinline__ void put_rec(UpdQueue &q, const ScanArgs &a, bool hit
         if (hit) q.qr[q.n + rank_in(m)] = rec;
         q.n += tot;
     } else {
-        const bool hi = rd > q.sub_rb || (rd == q.sub_rb && gd >= q.sub_gb);      // cell >= 2^32
+        const bool hi = rec_sub2(rd, gd, q.sub_rb, q.sub_gb) != 0u;               // cell >= 2^32
         const uint64_t m1 = __ballot(hit && hi), m0 = __ballot(hit && !hi);
         const uint32_t t0 = (uint32_t)__popcll(m0), t1 = (uint32_t)__popcll(m1);
         while (q.n + t0 > q.cap || q.n1 + t1 > q.cap) flush_direct(q, a, false);
@@ -491,7 +500,7 @@ __device__ __forceinline__ void drain_bin(UpdQueue &q, const ScanArgs &a, bool f
     auto store_waiting = [&](uint32_t sub, uint32_t c0, uint32_t c1, uint32_t wrec) {
         const uint32_t l0 = c0 & ~15u;
         if (sub < n_sub && (c1 & ~15u) != l0 && wi < (c0 & 15u) && l0 + wi < cap_w && !ABL(7)) {     // a full sub-region only counts: the pass is repeated with a larger pool
-            atomicAdd(&q.hist[hoff + ((wrec >> bin_shift) | (sub << (32u - bin_shift)))], 1u);      // the histogram counts exactly the records that are stored
+            atomicAdd(&q.hist[hoff + rec_bin(wrec, sub, bin_shift)], 1u);      // the histogram counts exactly the records that are stored
             if (!ABL(6)) out[(size_t)sub * cap_w + l0 + wi] = wrec;       // (a plain store, like the other piece of its line below: a non-temporal store of less than a line is a read-modify-write at the memory, 4.5 x a whole line's -- plain, the two pieces meet in L2)
         }
     };
@@ -500,10 +509,10 @@ __device__ __forceinline__ void drain_bin(UpdQueue &q, const ScanArgs &a, bool f
         const uint32_t k = k0 + lane;
         const bool on = k < n;
         const uint32_t gt = q.qg[on ? k : 0u], rd = q.qr[on ? k : 0u];
-        // the scan's fast emitters do not look at the document ids: a genome id beyond the table is caught here, on
-        // full waves (the entry is dropped; the pass fails with LIME_ERR_DOCID)
-        const uint64_t cell = (uint64_t)rd * n_refs + (gt & (MAX_REFS - 1u));
-        const uint32_t hi = (uint32_t)(cell >> 32), rec = (uint32_t)cell;
+        // (a second line: every writer of queue entries passes its genome index through genome_ok first, so no entry beyond the
+        // table gets here; one that did would be dropped and the pass fail with LIME_ERR_DOCID)
+        const uint64_t cell = cell_of(rd, gt & (MAX_REFS - 1u), n_refs);
+        const uint32_t hi = cell_sub(cell), rec = (uint32_t)cell;
         const bool bad = on && ((gt & (MAX_REFS - 1u)) >= n_refs || hi >= n_sub);
         if (__ballot(bad)) { if (bad) atomicOr(&cold(a).stats->flags, LIME_FLAG_DOCID); }
         uint32_t left = (on && !bad) ? gt >> T_SHIFT : 0u;
@@ -519,7 +528,7 @@ __device__ __forceinline__ void drain_bin(UpdQueue &q, const ScanArgs &a, bool f
             if (act) {
                 if (slot >= lim) q.lbuf[16u * hi + (slot & 15u)] = rec;
                 else if (slot < cap_w && !ABL(7)) {
-                    atomicAdd(&q.hist[hoff + (uint32_t)(cell >> bin_shift)], 1u);
+                    atomicAdd(&q.hist[hoff + cell_bin(cell, bin_shift)], 1u);
                     if (!ABL(6)) out[(size_t)hi * cap_w + slot] = rec;
                 }
             }
@@ -586,7 +595,7 @@ __device__ __forceinline__ uint32_t emit(UpdQueue &q, const ScanArgs &a, bool on
 {
     if (!q.direct) while (q.n + 64u > q.cap) drain(q, a);
     const uint32_t g = gdoc - a.n_reads;
-    const bool bad = on && (g >= a.n_refs || rdoc >= a.n_reads);
+    const bool bad = on && (!genome_ok(g, a.n_refs) || rdoc >= a.n_reads);
     if (__ballot(bad)) { if (bad) atomicOr(&cold(a).stats->flags, LIME_FLAG_DOCID); }
     on = on && !bad;
     if (q.direct) {                                        // a score of t = t records (t > 1: repeated documents only)
@@ -839,13 +848,14 @@ __device__ __forceinline__ uint32_t score_len2(LDS &L, const WgTables &T, UpdQue
     bool hit = on;
     if (EBWT) hit = hit && ((T.compatb[L.fl[p]] >> T.symidx[L.fl[p + 1u]]) & 1u);
     const uint32_t rd = r0 ? d0 : d1, gd = (r0 ? d1 : d0) - a.n_reads;
+    hit = checked(qu, hit, genome_ok(gd, a.n_refs));
     if (qu.direct) { put_rec(qu, a, hit, rd, gd); return hit ? 1u : 0u; }
-    const uint64_t m = EBWT ? __ballot(hit) : __ballot(on);
+    const uint64_t m = __ballot(hit);
     const uint32_t tot = (uint32_t)__popcll(m);
     while (qu.n + tot > qu.cap) drain(qu, a);
     if (hit) {
         const uint32_t slot = qu.n + rank_in(m);
-        qu.qr[slot] = rd; qu.qg[slot] = gd | (1u << T_SHIFT);               // (document ids are range-checked by the drains, on full waves)
+        qu.qr[slot] = rd; qu.qg[slot] = gd | (1u << T_SHIFT);
     }
     qu.n += tot;
     return hit ? 1u : 0u;
@@ -861,8 +871,8 @@ __device__ __forceinline__ uint32_t score_len2(LDS &L, const WgTables &T, UpdQue
 // Clusters of 2..4 symbols, one lane per cluster.  The pairs that join a read with a genome come as a LIST from a
 // table indexed by (read bits, length): at most four slots, so the emission is four short blocks with static queue
 // offsets instead of six; the documents of a slot are re-read from the staged window by position (a per-lane
-// register index would cost a select chain).  Documents are not range-checked here: the drains do that on full
-// waves.  Two equal documents (only documents of one kind can be equal: six plain compares, positions past the
+// register index would cost a select chain).  Every genome index passes genome_ok before it is stored; where the
+// slots come from the prefix sum over `hits`, a bad one's slot takes a stand-in that stays inside the table.  Two equal documents (only documents of one kind can be equal: six plain compares, positions past the
 // cluster carry impossible ids) hand the cluster to the wave's repeat store.
 template <int EBWT, typename LDS>
 __device__ __forceinline__ uint32_t score_small3(LDS &L, const WgTables &T, UpdQueue &qu, uint32_t &n_dup, const ScanArgs &a,
@@ -905,7 +915,8 @@ __device__ __forceinline__ uint32_t score_small3(LDS &L, const WgTables &T, UpdQ
             const bool he = (hits >> e) & 1u;
             if (e >= 2 && !__ballot(he)) continue;                            // wave-uniform
             const uint32_t rp = (pl >> (7 * e)) & 3u, gp = (pl >> (7 * e + 2)) & 3u;
-            put_rec(qu, a, he, L.da[p + rp], L.da[p + gp] - a.n_reads);
+            const uint32_t gd = L.da[p + gp] - a.n_reads;
+            put_rec(qu, a, checked(qu, he, genome_ok(gd, a.n_refs)), L.da[p + rp], gd);
         }
         return nh + nflush;
     }
@@ -927,13 +938,14 @@ __device__ __forceinline__ uint32_t score_small3(LDS &L, const WgTables &T, UpdQ
             if (he) {
                 const uint32_t rp = (pl >> (7 * e)) & 3u, gp = (pl >> (7 * e + 2)) & 3u;
                 const uint32_t slot = (EBWT || halves != 1u) ? slot0 + (uint32_t)__popc(hp & ((1u << e) - 1u)) : slot0 + (uint32_t)e;
+                // (the slot is given out already: a genome index beyond the table leaves a stand-in there -- cell 0 / an entry that adds 0)
+                const uint32_t gd = L.da[p + gp] - a.n_reads;
+                const bool ok = checked(qu, true, genome_ok(gd, a.n_refs));
                 if (qu.direct) {                                              // (one sub-region: the finished record)
-                    const uint32_t gd = L.da[p + gp] - a.n_reads;
-                    qu.bad |= (uint32_t)(gd >= a.n_refs);
-                    qu.qr[slot] = L.da[p + rp] * a.n_refs + gd;
+                    qu.qr[slot] = rec_or_stand_in(ok, L.da[p + rp], gd, a.n_refs);
                 } else {
                 qu.qr[slot] = L.da[p + rp];
-                qu.qg[slot] = (L.da[p + gp] - a.n_reads) | (1u << T_SHIFT);
+                qu.qg[slot] = entry_or_stand_in(ok, gd, T_SHIFT);
                 }
             }
         }
@@ -984,13 +996,15 @@ __device__ __forceinline__ uint32_t score_rows3(LDS &L, const WgTables &T, UpdQu
             const uint32_t dj = L.da[p + k];
             bool hit = act;
             if (EBWT) hit = act && ((ci >> T.symidx[L.fl[p + k]]) & 1u);
-            if (qu.direct) { put_rec(qu, a, hit, ri ? di : dj, (ri ? dj : di) - a.n_reads); nupd += (uint32_t)hit; continue; }
+            const uint32_t gd = (ri ? dj : di) - a.n_reads;
+            hit = checked(qu, hit, genome_ok(gd, a.n_refs));
+            if (qu.direct) { put_rec(qu, a, hit, ri ? di : dj, gd); nupd += (uint32_t)hit; continue; }
             const uint64_t m = __ballot(hit);
             while (qu.n + 64u > qu.cap) drain(qu, a);
             if (hit) {
                 const uint32_t slot = qu.n + rank_in(m);
                 qu.qr[slot] = ri ? di : dj;
-                qu.qg[slot] = ((ri ? dj : di) - a.n_reads) | (1u << T_SHIFT);
+                qu.qg[slot] = gd | (1u << T_SHIFT);
             }
             qu.n += (uint32_t)__popcll(m);
             nupd += (uint32_t)hit;
@@ -1377,7 +1391,7 @@ __global__ __launch_bounds__((ScanCfg<EBWT, BIN>::wg)) __attribute__((amdgpu_wav
         if (MODE == 0 && !ABL(8)) {
             if (ABL(13)) { qu.n = 0; qu.n1 = 0; } else
             if (BIN == 2) flush_direct(qu, a, false); else
-            if (binned) drain_bin(qu, a); else drain(qu, a);
+            { report_bad(qu, a); if (binned) drain_bin(qu, a); else drain(qu, a); }
             asm volatile("" ::: "memory");                    // the loads below stay below
         }
         // ---- the next window's loads go out now and land while this one is processed ----------
@@ -1585,6 +1599,7 @@ __global__ __launch_bounds__((ScanCfg<EBWT, BIN>::wg)) __attribute__((amdgpu_wav
         if (n_dup) acc_upd += dup_flush<EBWT>(L, n_dup, a, T, qu);
         if (BIN == 2) flush_direct(qu, a, true);                               // the last, partial lines too
         else {
+        report_bad(qu, a);
         do drain(qu, a); while (qu.n != 0u || __ballot(qu.f_pend != 0u));      // until every update has landed
         if (binned) drain_bin(qu, a, true);                                    // the records still waiting for their line
         }
@@ -2003,7 +2018,7 @@ __global__ __launch_bounds__(WGS) void k_part(ScanArgs a, const uint64_t *binbas
             while (seg_p(t.w0 + 1u) <= v0) ++t.w0;
             const uint32_t end = v0 + PART_TILE < l_pad ? v0 + PART_TILE : l_pad;
             t.one = end <= seg_p(t.w0 + 1u);
-            if (t.one) { const uint32_t left = seg_n(t.w0) - (v0 - seg_p(t.w0)); t.tn = left < PART_TILE ? left : PART_TILE; t.binoff = (t.w0 % a.n_sub) << (32u - sh); }
+            if (t.one) { const uint32_t left = seg_n(t.w0) - (v0 - seg_p(t.w0)); t.tn = left < PART_TILE ? left : PART_TILE; t.binoff = rec_bin_off(t.w0 % a.n_sub, sh); }
         }
         return t;
     };
@@ -2045,16 +2060,16 @@ __global__ __launch_bounds__(WGS) void k_part(ScanArgs a, const uint64_t *binbas
                 const uint32_t i = 4u * (j * PART_WG + tid);
                 const uint32_t v[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
 #pragma unroll
-                for (uint32_t k = 0; k < 4; ++k) if (i + k < t.tn) atomicAdd(&cnt[(v[k] >> sh) + t.binoff], 1u);
+                for (uint32_t k = 0; k < 4; ++k) if (i + k < t.tn) atomicAdd(&cnt[rec_bin_at(v[k], sh, t.binoff)], 1u);
             }
             return;
         }
 #pragma unroll
         for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-            const uint32_t vc = (meta >> (6u * j)) & 7u, bo = ((meta >> (6u * j + 3u)) & 7u) << (32u - sh);
+            const uint32_t vc = (meta >> (6u * j)) & 7u, bo = rec_bin_off((meta >> (6u * j + 3u)) & 7u, sh);
             const uint32_t v[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
 #pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) if (k < vc) atomicAdd(&cnt[(v[k] >> sh) + bo], 1u);
+            for (uint32_t k = 0; k < 4; ++k) if (k < vc) atomicAdd(&cnt[rec_bin_at(v[k], sh, bo)], 1u);
         }
     };
     Tile tc = tile_at(0u, 0u);
@@ -2099,12 +2114,12 @@ __global__ __launch_bounds__(WGS) void k_part(ScanArgs a, const uint64_t *binbas
 #pragma unroll
         for (uint32_t j = 0; j < PART_PER / 4; ++j) {
             const uint32_t vc = tc.one ? (4u * (j * PART_WG + tid) < tc.tn ? (tc.tn - 4u * (j * PART_WG + tid) < 4u ? tc.tn - 4u * (j * PART_WG + tid) : 4u) : 0u) : (m4 >> (6u * j)) & 7u;
-            const uint32_t bo = tc.one ? tc.binoff : ((m4 >> (6u * j + 3u)) & 7u) << (32u - sh);
+            const uint32_t bo = tc.one ? tc.binoff : rec_bin_off((m4 >> (6u * j + 3u)) & 7u, sh);
             const uint32_t v[4] = {v4[j].x, v4[j].y, v4[j].z, v4[j].w};
 #pragma unroll
             for (uint32_t k = 0; k < 4; ++k)
                 if (k < vc) {
-                    const uint32_t b = (v[k] >> sh) + bo;
+                    const uint32_t b = rec_bin_at(v[k], sh, bo);
                     const uint32_t slot = atomicAdd(&cur[b], 1u);
                     if (P64) {
                         const uint64_t p = slot + delta64[b];
@@ -2229,7 +2244,7 @@ __global__ __launch_bounds__(PART_WG) void k_part_lines(ScanArgs a, const uint64
             while (seg_p(t.w0 + 1u) <= v0) ++t.w0;
             const uint32_t end = v0 + PART_TILE < l_pad ? v0 + PART_TILE : l_pad;
             t.one = end <= seg_p(t.w0 + 1u);
-            if (t.one) { const uint32_t left = seg_n(t.w0) - (v0 - seg_p(t.w0)); t.tn = left < PART_TILE ? left : PART_TILE; t.binoff = (t.w0 % a.n_sub) << (32u - sh); }
+            if (t.one) { const uint32_t left = seg_n(t.w0) - (v0 - seg_p(t.w0)); t.tn = left < PART_TILE ? left : PART_TILE; t.binoff = rec_bin_off(t.w0 % a.n_sub, sh); }
         }
         return t;
     };
@@ -2271,16 +2286,16 @@ __global__ __launch_bounds__(PART_WG) void k_part_lines(ScanArgs a, const uint64
                 const uint32_t i = 4u * (j * PART_WG + tid);
                 const uint32_t v[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
 #pragma unroll
-                for (uint32_t k = 0; k < 4; ++k) if (i + k < t.tn) atomicAdd(&cnt[(v[k] >> sh) + t.binoff], 1u);
+                for (uint32_t k = 0; k < 4; ++k) if (i + k < t.tn) atomicAdd(&cnt[rec_bin_at(v[k], sh, t.binoff)], 1u);
             }
             return;
         }
 #pragma unroll
         for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-            const uint32_t vc = (meta >> (6u * j)) & 7u, bo = ((meta >> (6u * j + 3u)) & 7u) << (32u - sh);
+            const uint32_t vc = (meta >> (6u * j)) & 7u, bo = rec_bin_off((meta >> (6u * j + 3u)) & 7u, sh);
             const uint32_t v[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
 #pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) if (k < vc) atomicAdd(&cnt[(v[k] >> sh) + bo], 1u);
+            for (uint32_t k = 0; k < 4; ++k) if (k < vc) atomicAdd(&cnt[rec_bin_at(v[k], sh, bo)], 1u);
         }
     };
     Tile tc = tile_at(0u, 0u);
@@ -2343,16 +2358,16 @@ __global__ __launch_bounds__(PART_WG) void k_part_lines(ScanArgs a, const uint64
                 const uint32_t v[4] = {v4[j].x, v4[j].y, v4[j].z, v4[j].w};
 #pragma unroll
                 for (uint32_t k = 0; k < 4; ++k)
-                    if (i + k < tc.tn) stage[atomicAdd(&cur[(v[k] >> sh) + tc.binoff], 1u)] = (v[k] & omask) | tbit;      // t = 1
+                    if (i + k < tc.tn) stage[atomicAdd(&cur[rec_bin_at(v[k], sh, tc.binoff)], 1u)] = (v[k] & omask) | tbit;      // t = 1
             }
         } else
 #pragma unroll
         for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-            const uint32_t vc = (m4 >> (6u * j)) & 7u, bo = ((m4 >> (6u * j + 3u)) & 7u) << (32u - sh);
+            const uint32_t vc = (m4 >> (6u * j)) & 7u, bo = rec_bin_off((m4 >> (6u * j + 3u)) & 7u, sh);
             const uint32_t v[4] = {v4[j].x, v4[j].y, v4[j].z, v4[j].w};
 #pragma unroll
             for (uint32_t k = 0; k < 4; ++k)
-                if (k < vc) stage[atomicAdd(&cur[(v[k] >> sh) + bo], 1u)] = (v[k] & omask) | tbit;      // t = 1
+                if (k < vc) stage[atomicAdd(&cur[rec_bin_at(v[k], sh, bo)], 1u)] = (v[k] & omask) | tbit;      // t = 1
         }
         PP(3)
         __syncthreads();
@@ -3325,7 +3340,7 @@ __global__ __launch_bounds__(WGSZ) void k_score_big(ScanArgs a, uint32_t *scratc
                 }
                 if (t) {
                     const uint32_t g = gdoc - a.n_reads;
-                    if (g >= a.n_refs) atomicOr(&a.stats->flags, LIME_FLAG_DOCID);
+                    if (!genome_ok(g, a.n_refs)) atomicOr(&a.stats->flags, LIME_FLAG_DOCID);
                     else if (a.sim) { sim_add(a.sim, row + g, t); ++nupd; }
                     else {                                     // records for the owner of the cell (owner-partitioned exchange)
                         const uint32_t k = atomicAdd(a.bigrec_n, 1u);

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""tools/fuzz.py [seconds] [seed] -- random inputs through every entry point of the hot path against the oracle (bit-exact), on
+"""tools/fuzz.py [seconds] [seed] [--bad-ids] -- random inputs through every entry point of the hot path against the oracle (bit-exact), on
 the GPU box.  Shapes, generator parameters, cluster-length regimes, update paths, chunk sizes and shard counts are
 drawn at random; stops at the first difference with a description that reproduces it.  Not part of the test suite
-(time-boxed soak); the fixed cases it found nothing beyond are in tests/."""
+(time-boxed soak); the fixed cases it found nothing beyond are in tests/.
+--bad-ids (off by default): every case also plants ONE out-of-range document id (da >= n_reads + n_refs, any 32-bit value) on a genome position of a
+scored cluster and expects LIME_ERR_DOCID (-6) from the pass and a clean, bit-exact pass of the unchanged input afterwards on the same context."""
 import os, sys, time
 os.environ["LIME_TEST_HOOKS"] = "1"           # the library reads its LIME_<KNOB> variables only in a process that says it is a test (lime_init)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,12 +14,35 @@ import lime_amd
 from lime_amd.dist import shard_ranges, combine_edges
 from oracle import oracle_py as O
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+BAD_IDS = "--bad-ids" in sys.argv
+argv = [a for a in sys.argv if a != "--bad-ids"]
+budget = float(argv[1]) if len(argv) > 1 else 120.0
+seed0 = int(argv[2]) if len(argv) > 2 else 1
 t_end = time.time() + budget
 it = 0
 t_print = time.time()
-stats = {"cases": 0, "symbols": 0, "binned": 0, "shards": 0, "streams": 0, "p64": 0, "choose_free": 0}
+stats = {"cases": 0, "symbols": 0, "binned": 0, "shards": 0, "streams": 0, "p64": 0, "choose_free": 0, "bad_ids": 0}
+
+
+def plant_bad_id(rng, da, eb, cl, nr, ng):
+    """a copy of da with the genome document of one position of one accepted cluster (<= 65536 symbols) replaced by an out-of-range id, and an
+    ebwt under which every pair of that cluster scores; None if no cluster qualifies"""
+    # (the detector accepts only clusters that hold a read AND a genome, so a genome document of an accepted cluster is in at least one scored
+    # pair once every symbol of the cluster is 'A'; all occurrences of that document in the cluster take the bad id.  rng.choice over Python
+    # ints >= 2^31 gives an int64, hence the int() around it)
+    ok = [k for k in rng.permutation(len(cl))[:64] if cl[k, 1] <= 65536]
+    for k in ok:
+        p0, ln = int(cl[k, 0]), int(cl[k, 1])
+        gpos = [p for p in range(p0, p0 + ln) if da[p] >= nr]
+        if not gpos: continue
+        lo, hi = nr + ng, 0xFFFFFFEF
+        bad = int(rng.choice([lo, lo + int(rng.integers(0, 1 << 12)), nr + (1 << 25) * int(rng.integers(1, 100)) + int(rng.integers(0, ng)), hi, int(rng.integers(lo, hi + 1))]))
+        d2, e2 = da.copy(), eb.copy()
+        g_old = da[gpos[-1]]
+        d2[p0:p0 + ln][da[p0:p0 + ln] == g_old] = min(max(bad, lo), hi)
+        e2[p0:p0 + ln] = ord("A")
+        return d2, e2
+    return None
 
 
 def expected_choose(sim, norm, beta):
@@ -90,6 +115,15 @@ while time.time() < t_end:
             exp = O.score(da, e, cl, nr, ng, threads=8)
             sim, gnc, gml = ctx.fused(lcp, da, e, nr, ng, alpha)
             assert (gnc, gml) == (nc, ml) and np.array_equal(sim, exp), "fused: " + tag
+            planted = plant_bad_id(rng, da, eb, cl, nr, ng) if BAD_IDS and nr + ng < 0xFFFFFFEF else None
+            if planted is not None:
+                try:
+                    ctx.fused(lcp, planted[0], None if e is None else planted[1], nr, ng, alpha); raise AssertionError("no DOCID error: " + tag)
+                except lime_amd.LimeError as ex:
+                    assert ex.code == -6, f"rc={ex.code}: " + tag
+                sim, gnc, gml = ctx.fused(lcp, da, e, nr, ng, alpha)
+                assert (gnc, gml) == (nc, ml) and np.array_equal(sim, exp), "fused after a failed pass: " + tag
+                stats["bad_ids"] += 1
             r = rng.random()
             if r < 0.35:
                 chunk = int(rng.choice([4096, 8192, 65536, 262144]))
