@@ -437,6 +437,40 @@ int lime_classify_mem(uint32_t n_files, const uint8_t *const *row_max, const uin
 /* The classification file of lime_classify (header, "C,read,taxon,sim" lines, same float formatting) from verdicts. */
 int lime_write_classification(const char *path, const lime_verdict_t *verdicts, uint32_t n_reads);
 
+/* ---- ebwt / lcp / da from the sequences: a generalized suffix sort on the device ---------- *
+ * What the reference leaves to BCR_LCP_GSA / eGSA / eGap (Preprocessing.sh), in the convention the calls above consume and
+ * lime_amd/builder.py defines: the documents are the reads (ids 0 .. n_reads - 1) followed by the genomes, each followed by its own
+ * terminator; a terminator sorts below every symbol, two terminators by document id; symbols compare as unsigned bytes (all 256 values
+ * are legal, empty documents too).  da[i] = document of suffix i, ebwt[i] = the byte in front of it (`term` for a document's whole
+ * suffix), lcp[i] = leading non-terminator symbols suffixes i - 1 and i share (lcp[0] = 0), min(lcp[i], lcp_cap) when lcp_cap > 0
+ * (eGap's --trlcp; the scan needs lcp_cap >= alpha), the full value when lcp_cap == 0.
+ * text: the documents' symbols back to back WITHOUT terminators, reads first; doc_off[n_docs + 1] their starts (doc_off[0] = 0).
+ * Outputs: N = doc_off[n_docs] + n_docs elements each (lime_index_size); any of the three may be NULL.
+ * Limits: N <= 2^32 - 1, one GPU, the whole collection resident -- beyond them, and for a doc_off that does not start at 0, decreases
+ * or (device call) does not end at n_text: LIME_ERR_ARG.  Device memory: 52 bytes of scratch per position (N) next to the text
+ * (1 byte per symbol), doc_off (8 bytes per document) and the outputs (9 bytes per position), taken from lime_reserve's arena / the
+ * block cache and given back before the call returns; LIME_ERR_NOMEM without it.
+ * Cost: a radix sort of N 64-bit keys, then one sort per doubling round over the suffixes whose rank is not unique yet (repeats
+ * longer than the 64-bit key's symbols: genome repeats; a run of L equal symbols takes log2 L rounds); the LCP step compares
+ * sum(lcp) / 8 words of text in the worst case (near-identical genomes), at most N * lcp_cap / 8 with a cap.
+ * Out of scope: merging with a prebuilt genome index, several GPUs, collections larger than HBM. */
+uint64_t lime_index_size(const uint64_t *doc_off, uint32_t n_docs);
+/* host arrays, staged through HBM like the other host calls */
+int lime_build_index(lime_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, uint8_t term, uint32_t lcp_cap,
+                     uint8_t *ebwt, uint32_t *lcp, uint32_t *da);
+/* device arrays; outputs that are 16-byte aligned go straight into lime_fused_dev / lime_fused_choose_lists_dev.  Synchronises `stream`. */
+int lime_build_index_dev(lime_ctx *ctx, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
+                         uint8_t term, uint32_t lcp_cap, uint8_t *d_ebwt, uint32_t *d_lcp, uint32_t *d_da, void *stream);
+/* the last build of the ctx: out[0] doubling rounds run, out[1 .. 4] suffixes still without a unique rank after the first sort and
+ * after rounds 1, 2, 3; with lime_set_timing on, HIP-event ms of out[5] preparation + first sort, out[6] the doubling rounds,
+ * out[7] da / ebwt / lcp */
+int lime_get_index_info(lime_ctx *ctx, double out[8]);
+/* FASTA: '>' lines are headers, every other line's bytes minus CR/LF are appended as they are (no case folding; lines in front of the
+ * first header are skipped); rc != 0 reverse-complements each record (A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H, S, W, N and
+ * every other byte unchanged, case kept).  *text (at least one byte) and *doc_off[*n_docs + 1] are library-owned (lime_free).
+ * Pure host code.  LIME_ERR_IO when the file cannot be read. */
+int lime_fasta_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,11 @@ SYMBOLS = {
     "lime_classify_lists_dev": (_i, [_vp, _u32, _vp, _u32, _vp, _i, _vp, _vp, _vp]),
     "lime_classify_mem": (_i, [_u32, _vp, _vp, _vp, _vp, _vp, _i, _u32, _u32, _vp, _vp, _vp]),
     "lime_write_classification": (_i, [C.c_char_p, _vp, _u32]),
+    "lime_index_size": (_u64, [_vp, _u32]),
+    "lime_build_index": (_i, [_vp, _vp, _vp, _u32, C.c_uint8, _u32, _vp, _vp, _vp]),
+    "lime_build_index_dev": (_i, [_vp, _vp, _vp, _u32, _u64, C.c_uint8, _u32, _vp, _vp, _vp, _vp]),
+    "lime_get_index_info": (_i, [_vp, C.POINTER(C.c_double)]),
+    "lime_fasta_read": (_i, [C.c_char_p, _i, _pp, _pp, C.POINTER(_u32)]),
 }
 
 _LIB = None

@@ -290,6 +290,37 @@ class Context:
         return {"alloc_ms": v[0], "probe_ms": v[1], "probes": int(v[2]), "repeats": int(v[3]), "cas_fallbacks": int(v[4]),
                 "records_per_symbol": None if v[5] < 0 else v[5], "choose_without_table": int(v[6]), "classify_kernel_ms": v[7]}
 
+    # ---- ebwt / lcp / da from the sequences (include/lime_hip.h: lime_build_index) ----
+    def build_index(self, reads, genomes, term=0, lcp_cap=0):
+        """the collection reads + genomes -> (ebwt u8[N], lcp u32[N], da u32[N]) numpy arrays: lime_amd.builder.build_arrays' contract, sorted
+        on the device; lcp_cap > 0 stores min(lcp, lcp_cap)"""
+        text, off = pack_documents(reads, genomes)
+        n = int(off[-1]) + len(off) - 1
+        ebwt, lcp, da = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        check(self.lib.lime_build_index(self.h, text.ctypes.data, off.ctypes.data, len(off) - 1, int(term), int(lcp_cap),
+                                        ebwt.ctypes.data, lcp.ctypes.data, da.ctypes.data))
+        return ebwt[:n], lcp[:n], da[:n]
+
+    def build_index_dev(self, text_t, doc_off_t, n_docs, n_text, term=0, lcp_cap=0, stream=None, out=None):
+        """the same on torch device tensors: text_t uint8[n_text] (no terminators), doc_off_t int64[n_docs + 1] -> (ebwt_t uint8[N],
+        lcp_t, da_t int32[N] holding the u32 values), fresh tensors unless `out` gives the three (any of them None: not computed)"""
+        import torch
+        n = int(n_text) + int(n_docs)
+        if out is None:
+            dev = text_t.device
+            out = (torch.empty(max(n, 1), dtype=torch.uint8, device=dev), torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+                   torch.empty(max(n, 1), dtype=torch.int32, device=dev))
+        ebwt_t, lcp_t, da_t = out
+        check(self.lib.lime_build_index_dev(self.h, _ptr(text_t), _ptr(doc_off_t), int(n_docs), int(n_text), int(term), int(lcp_cap),
+                                            _ptr(ebwt_t), _ptr(lcp_t), _ptr(da_t), stream))
+        return tuple(None if t is None else t[:n] for t in out)
+
+    def index_info(self):
+        """the last build_index* of this context (lime_get_index_info); the ms need set_timing(True)"""
+        v = (C.c_double * 8)()
+        check(self.lib.lime_get_index_info(self.h, v))
+        return {"rounds": int(v[0]), "unresolved": [int(v[1]), int(v[2]), int(v[3]), int(v[4])], "sort_ms": v[5], "doubling_ms": v[6], "lcp_ms": v[7]}
+
 
 class Lists:
     """one collection's clusterChoose result resident in HBM (lime_lists), owned by its Context"""
@@ -371,6 +402,53 @@ def classify_mem(lists, norms, betas, n_targ, taxonomy, binary=True):
     check_cls(lib.lime_classify_mem(k, P(mx), P(off), P(pr), nm.ctypes.data, bt.ctypes.data, int(bool(binary)), n_reads, n_targ,
                                     taxonomy.h, v.ctypes.data, counts))
     return v[:n_reads], list(counts)
+
+
+def pack_documents(reads, genomes):
+    """lists of bytes / str -> (text uint8: the documents back to back without terminators, reads first; doc_off uint64[n_docs + 1])"""
+    docs = [d.encode() if isinstance(d, str) else bytes(d) for d in list(reads) + list(genomes)]
+    off = np.zeros(len(docs) + 1, dtype=np.uint64)
+    if docs:
+        off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+    text = np.frombuffer(b"".join(docs), dtype=np.uint8) if int(off[-1]) else np.zeros(1, np.uint8)
+    return np.ascontiguousarray(text), off
+
+
+def build_index(reads, genomes, term=0, lcp_cap=0, ctx=None):
+    """lime_amd.builder.build_arrays(reads, genomes, term) on the GPU -> (ebwt, lcp, da); lcp_cap > 0: min(lcp, lcp_cap).  ctx: a Context to
+    run on (default: a fresh one on the current device, closed again)"""
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        return ctx.build_index(reads, genomes, term, lcp_cap)
+    finally:
+        if own:
+            ctx.close()
+
+
+def build_index_dev(ctx, text_t, doc_off_t, n_docs, n_text, term=0, lcp_cap=0, stream=None, out=None):
+    """Context.build_index_dev"""
+    return ctx.build_index_dev(text_t, doc_off_t, n_docs, n_text, term, lcp_cap, stream, out)
+
+
+def index_size(doc_off):
+    off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    return int(_lib.load().lime_index_size(off.ctypes.data, len(off) - 1))
+
+
+def fasta_read(path, rc=False):
+    """a FASTA file's records -> list of bytes (lime_fasta_read: header lines dropped, CR / LF dropped, case kept; rc: reverse complements)"""
+    lib = _lib.load()
+    pt, po, nd = C.c_void_p(), C.c_void_p(), C.c_uint32(0)
+    rcode = lib.lime_fasta_read(os.fsencode(path), int(bool(rc)), C.byref(pt), C.byref(po), C.byref(nd))
+    if rcode != 0:
+        raise LimeError(rcode, f"lime_fasta_read: {path}")
+    try:
+        off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(nd.value + 1,)).copy()
+        raw = C.string_at(pt, int(off[-1]))
+    finally:
+        lib.lime_free(pt); lib.lime_free(po)
+    return [raw[int(off[k]):int(off[k + 1])] for k in range(nd.value)]
 
 
 def _ptr(t):

@@ -1,0 +1,77 @@
+// BuildIndex -- the preprocessing the reference leaves to BCR_LCP_GSA / eGSA / eGap (Preprocessing.sh), from FASTA files, on the GPU:
+//   BuildIndex reads.fasta refs.fasta outBase [--rc] [--trlcp k]
+// writes outBase.ebwt (u8), outBase.lcp and outBase.da (u32, little-endian, no header: what ClusterLCP / ClusterBWT_DA / LiME_paired
+// read) of the collection reads + genomes and prints numReads and numGenomes.  --rc reverse-complements the READS only (the script's
+// `seqtk seq -r`): four runs (reads_1, reads_1 --rc, reads_2, reads_2 --rc) give the four collections of LiME_paired.  --trlcp k stores
+// min(lcp, k) (eGap's option; k >= alpha changes no result downstream).  A thin shell over lime_fasta_read / lime_build_index.
+#include <string.h>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "cli_common.h"
+
+static bool write_file(const std::string &path, const void *data, size_t bytes)
+{
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = !bytes || fwrite(data, 1, bytes, f) == bytes;
+    return (fclose(f) == 0) && ok;
+}
+
+int main(int argc, char **argv)
+{
+    CliClock clk;
+    std::vector<const char *> pos;
+    int rc_reads = 0;
+    unsigned trlcp = 0;
+    bool bad = false;
+    for (int i = 1; i < argc; ++i) {
+        if (!strcmp(argv[i], "--rc")) rc_reads = 1;
+        else if (!strcmp(argv[i], "--trlcp")) { if (i + 1 < argc && sscanf(argv[i + 1], "%u", &trlcp) == 1) ++i; else bad = true; }
+        else pos.push_back(argv[i]);
+    }
+    if (bad || pos.size() != 3) {
+        std::cerr << "Error usage " << argv[0] << " reads.fasta refs.fasta outBase [--rc] [--trlcp k]\n"
+                  << "  writes outBase.ebwt, outBase.lcp, outBase.da of the collection reads + genomes; --rc: the reads' reverse complements;\n"
+                  << "  --trlcp k: lcp values truncated at k." << std::endl;
+        exit(1);
+    }
+    const std::string base = pos[2];
+    uint8_t *text[2] = {nullptr, nullptr};
+    uint64_t *off[2] = {nullptr, nullptr};
+    uint32_t nd[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        const int rc = lime_fasta_read(pos[k], k == 0 ? rc_reads : 0, &text[k], &off[k], &nd[k]);
+        if (rc != LIME_OK) { std::cerr << "Error reading " << pos[k] << "." << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
+    }
+    clk.mark("FASTA files");
+    if ((uint64_t)nd[0] + nd[1] > 0xFFFFFFFFull) { std::cerr << "Error: too many sequences." << std::endl; return 1; }
+    const uint32_t n_docs = nd[0] + nd[1];
+    const uint64_t n_reads_sym = off[0][nd[0]], n_text = n_reads_sym + off[1][nd[1]];
+    std::vector<uint8_t> all(n_text ? n_text : 1);
+    if (n_reads_sym) memcpy(all.data(), text[0], n_reads_sym);
+    if (n_text > n_reads_sym) memcpy(all.data() + n_reads_sym, text[1], n_text - n_reads_sym);
+    std::vector<uint64_t> doc_off((size_t)n_docs + 1);
+    for (uint32_t k = 0; k <= nd[0]; ++k) doc_off[k] = off[0][k];
+    for (uint32_t k = 0; k <= nd[1]; ++k) doc_off[nd[0] + k] = n_reads_sym + off[1][k];
+    for (int k = 0; k < 2; ++k) { lime_free(text[k]); lime_free(off[k]); }
+    const uint64_t n = lime_index_size(doc_off.data(), n_docs);
+    std::vector<uint8_t> ebwt(n ? n : 1);
+    std::vector<uint32_t> lcp(n ? n : 1), da(n ? n : 1);
+    lime_ctx *ctx = nullptr;
+    if (lime_init(pick_device(), &ctx) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(EXIT_FAILURE); }
+    clk.mark("lime_init (HIP runtime)");
+    if (lime_build_index(ctx, all.data(), doc_off.data(), n_docs, 0, trlcp, ebwt.data(), lcp.data(), da.data()) != LIME_OK) {
+        std::cerr << "Error: " << lime_last_error() << std::endl; exit(1);
+    }
+    clk.mark("index");
+    lime_shutdown(ctx);
+    if (!write_file(base + ".ebwt", ebwt.data(), n) || !write_file(base + ".lcp", lcp.data(), n * 4) || !write_file(base + ".da", da.data(), n * 4)) {
+        std::cerr << "Error writing " << base << ".ebwt / .lcp / .da." << std::endl;
+        return -LIME_ERR_IO;
+    }
+    clk.mark("output files");
+    std::cout << "numReads: " << nd[0] << "\nnumGenomes: " << nd[1] << "\nsymbols: " << n << std::endl;
+    return 0;
+}

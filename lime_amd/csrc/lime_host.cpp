@@ -182,3 +182,57 @@ extern "C" int lime_write_res_bin_pairs(const char *path_bin, const char *path_p
     int e1 = ob.close(), e2 = op.close();
     return (e1 || e2) ? LIME_ERR_IO : LIME_OK;
 }
+
+// ---- FASTA in: the documents of lime_build_index ---------------------------------------------
+// '>' lines are headers and start a record; every other line's bytes, CR and LF dropped, are the record's symbols as they are (no case
+// folding; lines in front of the first header belong to no record and are skipped).  rc: every record reversed and complemented
+// (the script's `seqtk seq -r`): A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H in both cases; S, W, N and every other byte stay.
+extern "C" int lime_fasta_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs)
+{
+    if (!path || !text || !doc_off || !n_docs) return LIME_ERR_ARG;
+    *text = nullptr; *doc_off = nullptr; *n_docs = 0;
+    File in(path, "rb");
+    if (!in.f) return LIME_ERR_IO;
+    uint8_t comp[256];
+    for (int b = 0; b < 256; ++b) comp[b] = (uint8_t)b;
+    const char *from = "ATCGURYKMBVDH", *to = "TAGCAYRMKVBHD";
+    for (int k = 0; from[k]; ++k) { comp[(uint8_t)from[k]] = (uint8_t)to[k]; comp[(uint8_t)(from[k] | 0x20)] = (uint8_t)(to[k] | 0x20); }
+    std::vector<uint8_t> sym;
+    std::vector<uint64_t> off;
+    std::vector<char> buf(1 << 20);
+    bool line_start = true, in_header = false;
+    auto close_record = [&]() {
+        if (rc && !off.empty()) {
+            uint8_t *a = sym.data() + off.back(), *b = sym.data() + sym.size();
+            for (uint8_t *x = a, *y = b; x < y; ) { --y; const uint8_t u = comp[*x], v = comp[*y]; *x++ = v; *y = u; }
+        }
+    };
+    size_t got;
+    while ((got = fread(buf.data(), 1, buf.size(), in.f)) > 0) {
+        for (size_t i = 0; i < got; ++i) {
+            const uint8_t ch = (uint8_t)buf[i];
+            if (ch == '\n') { line_start = true; in_header = false; continue; }
+            if (line_start) {
+                line_start = false;
+                if (ch == '>') {
+                    close_record();
+                    if (off.size() >= 0xFFFFFFFFull) return LIME_ERR_ARG;
+                    off.push_back(sym.size()); in_header = true; continue;
+                }
+            }
+            if (in_header || ch == '\r' || off.empty()) continue;
+            sym.push_back(ch);
+        }
+    }
+    if (ferror(in.f)) return LIME_ERR_IO;
+    close_record();
+    off.push_back(sym.size());
+    const uint32_t nd = (uint32_t)(off.size() - 1);                        // (no record: doc_off = {0})
+    uint8_t *t = static_cast<uint8_t *>(malloc(sym.size() ? sym.size() : 1));
+    uint64_t *o = static_cast<uint64_t *>(malloc(off.size() * 8));
+    if (!t || !o) { free(t); free(o); return LIME_ERR_NOMEM; }
+    if (!sym.empty()) memcpy(t, sym.data(), sym.size());
+    memcpy(o, off.data(), off.size() * 8);
+    *text = t; *doc_off = o; *n_docs = nd;
+    return LIME_OK;
+}

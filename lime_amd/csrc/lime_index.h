@@ -1,0 +1,56 @@
+// lime_index.h -- what the index builder's three parts share: the kernels (lime_index_kernel.hip), the rocPRIM sorts and
+// prefix sums (lime_index_sort.hip, a translation unit of its own) and the host sequencing (lime_api.cpp: lime_build_index_dev).
+// Not part of the public ABI (include/lime_hip.h is).
+//
+// Positions: the collection with one terminator after every document has N = n_text + n_docs positions; document k owns
+// [doc_off[k] + k, doc_off[k + 1] + k], the last one its terminator.  The symbol at a non-terminator position p of document k is
+// text[p - k].  A suffix is named by its position (u32: N <= 2^32 - 1).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace lime {
+
+constexpr uint32_t IDX_STRETCH = 16;             // consecutive positions one lane of k_idx_lcp walks (Kasai's bound carried along)
+
+struct IdxText {                                 // the collection as the kernels see it
+    const uint8_t *text;                         // n_text symbols, no terminators
+    const uint64_t *doc_off;                     // [n_docs + 1]
+    const uint32_t *doc_of;                      // [N] document of every position
+    uint64_t n_text;
+    uint32_t n_docs, n;                          // n = N
+};
+
+// ---- lime_index_kernel.hip ----
+// err |= 1 unless doc_off[0] == 0, doc_off is non-decreasing and doc_off[n_docs] == n_text; present[b] = 1 for every byte b of the text
+void idx_launch_check(const uint64_t *doc_off, uint32_t n_docs, uint64_t n_text, const uint8_t *text, uint32_t *present, uint32_t *err, hipStream_t st);
+// code[b] = 1 + number of present bytes below b (0 for absent bytes); *sigma = number of present bytes
+void idx_launch_codes(const uint32_t *present, uint16_t *code, uint32_t *sigma, hipStream_t st);
+// flags[doc_off[k] + k] = 1 for k = 1 .. n_docs - 1 (flags zeroed by the caller; its inclusive sum is doc_of)
+void idx_launch_doc_heads(const uint64_t *doc_off, uint32_t n_docs, uint32_t *flags, hipStream_t st);
+// keys[p] = the first k_syms symbols' codes of suffix p, `bits` each, first symbol highest; 0 from the terminator on.  vals[p] = p
+void idx_launch_pack(const IdxText &t, const uint16_t *code, uint32_t k_syms, uint32_t bits, uint64_t *keys, uint32_t *vals, hipStream_t st);
+// element j of a sorted list of m (key, suffix) pairs that sits at suffix-array slot idx[j] (idx NULL: slot j).  A new group starts at
+// j == 0, where the key changes, and (low_mask != 0) where key & low_mask == 0: the terminator is inside the packed window, the suffix
+// is alone.  head_pos[j] = the slot if j starts a group, else 0 (its running maximum is every element's group head)
+void idx_launch_heads(const uint64_t *keys, const uint32_t *idx, uint32_t m, uint64_t low_mask, uint32_t *head_pos, hipStream_t st);
+// rank[vals[j]] = grp[j], sa[slot j] = vals[j] (both arrays of n), act[j] = 1 unless j is a group of one
+void idx_launch_settle(const uint64_t *keys, const uint32_t *vals, const uint32_t *idx, const uint32_t *grp, uint32_t m, uint64_t low_mask,
+                       uint32_t n, uint32_t *rank, uint32_t *sa, uint32_t *act, hipStream_t st);
+// the elements with act[j] != 0 move to slot pos[j] of (idx_out, vals_out)
+void idx_launch_compact(const uint32_t *vals, const uint32_t *idx, const uint32_t *act, const uint32_t *pos, uint32_t m,
+                        uint32_t *vals_out, uint32_t *idx_out, hipStream_t st);
+// keys[j] = rank[vals[j]] << nb | rank[vals[j] + h]
+void idx_launch_double(const uint32_t *vals, uint32_t m, const uint32_t *rank, uint32_t n, uint64_t h, uint32_t nb, uint64_t *keys, hipStream_t st);
+// da[i] = doc_of[sa[i]], ebwt[i] = the symbol before suffix sa[i] (term for a document's whole suffix); either may be NULL
+void idx_launch_gather(const IdxText &t, const uint32_t *sa, uint8_t term, uint32_t *da, uint8_t *ebwt, hipStream_t st);
+// lcp[rank[p]] for every position p (rank = the inverse of sa), capped at lcp_cap when that is not 0
+void idx_launch_lcp(const IdxText &t, const uint32_t *sa, const uint32_t *rank, uint32_t lcp_cap, uint32_t *lcp, hipStream_t st);
+
+// ---- lime_index_sort.hip: rocPRIM's device primitives.  temp == NULL: only *temp_bytes is set (the size to pass next time) ----
+struct IdxPairs { uint64_t *keys[2]; uint32_t *vals[2]; int cur; };       // double buffers; cur = which holds the data (updated by the sort)
+hipError_t idx_sort_pairs(void *temp, size_t *temp_bytes, IdxPairs *b, size_t m, unsigned begin_bit, unsigned end_bit, hipStream_t st);
+hipError_t idx_scan_sum(void *temp, size_t *temp_bytes, const uint32_t *in, uint32_t *out, size_t m, bool inclusive, hipStream_t st);
+hipError_t idx_scan_max(void *temp, size_t *temp_bytes, const uint32_t *in, uint32_t *out, size_t m, hipStream_t st);
+
+} // namespace lime
