@@ -1,5 +1,5 @@
 // lime_api.cpp -- implementation of the C ABI in include/lime_hip.h on top of the HIP kernels
-// in lime_kernels.hip.  Host side only: argument checks, scratch management in HBM, kernel
+// in lime_kernels.hip, lime_partition.hip and lime_apply.hip.  Host side only: argument checks, scratch management in HBM, kernel
 // sequencing on the caller's stream, staging for the host-pointer entry points.
 // There is no CPU code path for the computation: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>

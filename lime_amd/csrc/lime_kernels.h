@@ -1,5 +1,5 @@
-// lime_kernels.h -- declarations shared by the kernels (lime_kernels.hip) and the C-ABI
-// implementation (lime_api.cpp).  Not part of the public ABI (include/lime_hip.h is).
+// lime_kernels.h -- declarations shared by the kernel files (lime_kernels.hip, lime_partition.hip, lime_apply.hip)
+// and the C-ABI implementation (lime_api.cpp).  Not part of the public ABI (include/lime_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,6 +55,13 @@ constexpr uint32_t BIN_MAX = 3072;           // bins: one u32 counter each in th
 #endif
 constexpr uint32_t REGION_SHIFT = LIME_REGION_SHIFT;   // k_apply / k_apply_tiles build 2^REGION_SHIFT bytes of the table per workgroup (<= 16: the second level's records are 16-bit)
 static_assert(REGION_SHIFT >= 12 && REGION_SHIFT <= 16, "region offsets are 16-bit records");
+// the partition kernels' tile (lime_partition.hip): k_bin_bases counts the bins' tiles, k_sort_tiles writes a row per tile, k_apply_tiles reads them
+#ifndef LIME_PART_PER
+#define LIME_PART_PER 16
+#endif
+constexpr int PART_WG = 512;
+constexpr uint32_t PART_PER = LIME_PART_PER, PART_TILE = PART_WG * PART_PER;   // 8192 records per tile, 64 KB of (position, record)
+constexpr uint32_t ROW_STRIDE = PART_TILE;                              // 16-bit records from one second-level tile row to the next (padding it -- 256 B, 4.25 KB -- changed nothing)
 constexpr uint32_t BIN_ONE_LEVEL = 1024;     // tables of up to this many regions: one bin per region, no second level
 constexpr uint32_t BIN_TWO_LEVEL = 2048;     // larger tables: at most this many bins of 2^k regions each (while k allows); measured best of 256..2048 on configs[2]
 constexpr uint32_t BIN_SHIFT_MAX = 25;       // bin-relative cell offset + 7 bits of t must fit 32 bits

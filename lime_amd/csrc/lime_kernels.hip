@@ -15,6 +15,10 @@
 // apply through LDS.  Segments still open after the read-ahead are closed by k_resolve_open /
 // k_resolve; clusters longer than 64 go to a one-workgroup-per-cluster hash kernel.  Integer / byte
 // work only: no MFMA, HBM-bound.
+//
+// This file: the scan and detection kernels, the list and long-cluster scorers, the kernels over the finished table and the small
+// utilities.  The partition kernels are in lime_partition.hip, the apply kernels in lime_apply.hip.
+#define LIME_DEBUG_TU_SCAN          // lime_debug.h: this file defines the LIME_WALL_TIMING globals
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -23,6 +27,9 @@
 #include <type_traits>
 #include "lime_device.h"
 #include "lime_kernels.h"
+#include "lime_wave.h"
+#include "lime_debug.h"
+#include "lime_launch.h"
 
 namespace lime {
 
@@ -38,13 +45,6 @@ static_assert(MID_MAX / 2u < (1u << (32u - T_SHIFT)), "the queue's t field must 
 constexpr uint32_t CAP_A = 256;       // clusters (2..SMALL_MAX symbols) a window can own
 constexpr uint32_t CAP_D = 256;       // of those, clusters with a repeated document (general routine)
 
-// LDS is written and read through differently typed pointers (bytes as u16/u64, words as uint4):
-// these may_alias types keep the compiler from reordering such accesses under type-based aliasing.
-typedef volatile uint8_t __attribute__((address_space(3))) lds_vu8;
-typedef volatile uint32_t __attribute__((address_space(3))) lds_vu32;
-typedef uint16_t __attribute__((may_alias)) u16a;
-typedef uint64_t __attribute__((may_alias)) u64a;
-typedef uint4 __attribute__((may_alias)) u4a;
 
 // LDS of ONE wave: the staged window and its work lists.  `da`/`fl` are sized by the kernel.
 template <uint32_t NPOS>
@@ -62,38 +62,6 @@ struct alignas(16) WaveLds {
     uint32_t q_read[QCAP], q_gen[QCAP];
 };
 
-// timing experiments (tools/quick.sh): a build with -DLIME_ABLATE_BUILD cuts the scan after phase k when the
-// environment says LIME_ABLATE=k (results invalid); the release library has no such switch
-#ifdef LIME_ABLATE_BUILD
-#define ABL(k) (a.ablate == (k))
-#else
-#define ABL(k) false
-#endif
-
-#ifdef LIME_WALL_TIMING      // debug build: start and end wall clock (100 MHz) of every wave of the last scan
-__device__ uint64_t g_wall[2 * 8192];
-extern "C" int lime_debug_wall(uint64_t *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wall), sizeof(g_wall)); }
-__device__ uint32_t g_winmark[1u << 20];       // which wave (+ 1) took window w of the last scan
-extern "C" int lime_debug_winmark(uint32_t *out)
-{
-    int rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_winmark), sizeof(g_winmark));
-    void *p = nullptr; (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_winmark)); (void)hipMemset(p, 0, sizeof(g_winmark));
-    return rc;
-}
-#endif
-#ifdef LIME_PHASE_TIMING     // debug build: per-wave cycle counts of the scan's phases, printed by a few waves
-#define PT_DECL uint64_t pt_t = __builtin_readcyclecounter(), pt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt_m[4] = {0, 0, 0, 0}; uint32_t pt_nwin = 0;
-#define PT(i) { const uint64_t n_ = __builtin_readcyclecounter(); pt_acc[i] += n_ - pt_t; pt_t = n_; }
-#define PT_WAITVM asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#elif defined(LIME_MARK)     // ISA reading aid: phase borders as comments in the assembly (tools/isa_count.py)
-#define PT_DECL
-#define PT(i) asm volatile("; LIMEMARK " #i);
-#define PT_WAITVM
-#else
-#define PT_DECL
-#define PT(i)
-#define PT_WAITVM
-#endif
 
 // threads per workgroup of k_scan and waves per SIMD it is compiled for: ScanCfg in lime_kernels.h (one workgroup per CU:
 // EBWT = 0: 16 waves = 4 per SIMD; EBWT = 1: 12 waves = 3 per SIMD); the LDS of one wave is kept small: it bounds them
@@ -102,82 +70,6 @@ constexpr uint32_t DUP_SLOTS_E = 4;   // ... with symbols (EBWT=1: 16 waves per 
 constexpr uint32_t QCAP_SCAN = 286;   // >= the 256 hits one batch of 64 clusters of <= 4 symbols can add + the 2 x 15 entries a binned drain leaves behind
 constexpr uint32_t QCAP_SCAN_SHORT = 160;   // EBWT=1 with records (16 waves per CU): a batch that would not fit is emitted in two halves (score_small3)
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-// The kernel's ScanArgs (always its first argument) re-read from the kernarg segment at the point of use: fields that only
-// rare paths need (counters, flags, the long-cluster list ...) then cost a scalar load there instead of SGPRs held through
-// the whole window loop -- the scan kernels were 2..40 SGPRs over budget and spilled them into VGPR lanes.
-__device__ __forceinline__ const ScanArgs &cold(const ScanArgs &)
-{
-    const ScanArgs __attribute__((address_space(4))) *p = (const ScanArgs __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));                               // opaque: not merged with the by-value copy, not hoisted
-    return *(const ScanArgs *)p;
-}
-__device__ __forceinline__ uint64_t brev64(uint64_t x) { return __builtin_bitreverse64(x); }
-__device__ __forceinline__ uint32_t rl32(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-// v with lane L replaced by the wave-uniform value s (this compiler has no v_writelane builtin).  On gfx940/gfx950 a
-// vector instruction that reads an SGPR / VCC written by the vector instruction just before it -- here the v_cmp whose
-// ballot is s -- needs two wait states.  The compiler's hazard recognizer inserts them for instructions it knows; inline
-// assembly is opaque to it, and whenever the scheduler happened to put a bare `v_writelane` right behind its v_cmp it read
-// the PREVIOUS ballot: round 2's "wrong cluster counts" of the build with the runtime update-path flag, and round 3's of the
-// first lean EBWT=1 binned scan (`v_cmp_gt_u32 vcc, ..` / `v_writelane_b32 v2, vcc_lo, 1` back to back).
-// So the wait states are part of the assembly: `s_nop 1` (two wait states) in front, and the four writes of a mask word
-// share one statement and one nop.
-template <int L> __device__ __forceinline__ uint32_t write_lane(uint32_t v, uint32_t s)
-{
-    asm("s_nop 1\n\tv_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(s), "n"(L));
-    return v;
-}
-template <int L> __device__ __forceinline__ void write_lane4(uint32_t &v0, uint32_t &v1, uint32_t &v2, uint32_t &v3,
-                                                            uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3)
-{
-    asm("s_nop 1\n\tv_writelane_b32 %0, %4, %8\n\tv_writelane_b32 %1, %5, %8\n\tv_writelane_b32 %2, %6, %8\n\tv_writelane_b32 %3, %7, %8"
-        : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3) : "s"(s0), "s"(s1), "s"(s2), "s"(s3), "n"(L));
-}
-__device__ __forceinline__ uint64_t rl64(uint64_t v, uint32_t l)
-{
-    return ((uint64_t)rl32((uint32_t)(v >> 32), l) << 32) | rl32((uint32_t)v, l);
-}
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int l)
-{
-    return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), l) << 32) | (uint32_t)__shfl((int)(uint32_t)v, l);
-}
-// number of set bits of the wave mask m in lanes below this one (v_mbcnt_lo/hi: two instructions)
-__device__ __forceinline__ uint32_t rank_in(uint64_t m)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-// 32 mask bits starting at bit `pos` of a bit array in LDS (8-byte aligned, at least (pos >> 5) + 2 words long):
-// two aligned words and one v_alignbit
-typedef uint32_t __attribute__((may_alias)) u32a;
-__device__ __forceinline__ uint32_t bits_at(const uint8_t *bits, uint32_t pos)
-{
-    const u32a *w = reinterpret_cast<const u32a *>(bits) + (pos >> 5);
-    return __builtin_amdgcn_alignbit(w[1], w[0], pos & 31u);
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const uint32_t o = __shfl_xor(v, d); v = o > v ? o : v; }
-    return v;
-}
-
-// inclusive prefix sum over the 64 lanes with DPP row shifts / row broadcasts (no LDS)
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1,3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2,3
-    return v;
-}
 
 // byte -> symbol index, and symbol index -> set of symbol indices it scores 1 against
 // (iupac_match); filled once per workgroup
@@ -225,22 +117,6 @@ __device__ __forceinline__ void tables_init(WgTables &T)
     __syncthreads();
 }
 
-// exact "cell += t (mod 256)" on the byte table through a 32-bit CAS on the containing word.
-// First attempt assumes the word is still zero (tables are sparse), then retries on the
-// value the CAS returned.
-__device__ __forceinline__ void sim_add(uint8_t *sim, uint64_t cell, uint32_t t)
-{
-    uint32_t *w = reinterpret_cast<uint32_t *>(sim + (cell & ~3ull));
-    const uint32_t sh = (uint32_t)(cell & 3ull) * 8u;
-    uint32_t expect = 0u;
-    for (;;) {
-        uint32_t b = ((expect >> sh) + t) & 255u;
-        uint32_t want = (expect & ~(255u << sh)) | (b << sh);
-        uint32_t old = atomicCAS(w, expect, want);
-        if (old == expect) break;
-        expect = old;
-    }
-}
 
 // ---- table updates of a wave: queued in its LDS ring, applied together so that the round
 // trips of the compare-and-swaps overlap instead of following one another -----------------
@@ -1869,1307 +1745,6 @@ __global__ __launch_bounds__(1024) void k_bin_bases(const uint32_t *totals, uint
     }
 }
 
-// (bins as wide as a region: the bin bases are the region bases; wider bins go through k_part2 first)
-//
-// Both partition kernels move records TILE by TILE through LDS: a tile's records are ranked inside their bin with
-// one returning LDS add each, an exclusive scan of the tile's bin counts gives every bin a run of LDS slots, the
-// records go to their slots together with their final position, and the tile leaves LDS slot by slot -- so a wave's
-// store instruction writes runs of consecutive positions instead of 64 scattered dwords (scattered 4-byte stores
-// cost the CU's address path about 3 cycles per lane: 0.8 ms per 1.2e8 records and level, measured).
-#ifndef LIME_PART_PER
-#define LIME_PART_PER 16
-#endif
-constexpr int PART_WG = 512;
-constexpr uint32_t PART_PER = LIME_PART_PER, PART_TILE = PART_WG * PART_PER;   // 8192 records per tile, 64 KB of (position, record)
-constexpr uint32_t ROW_STRIDE = PART_TILE;                              // 16-bit records from one second-level tile row to the next (padding it -- 256 B, 4.25 KB -- changed nothing)
-
-// exclusive prefix of cnt[0 .. nb) into toff[0 .. nb), nb <= PART_WG * 8; all threads of the workgroup call it
-// (barriers inside: cnt is complete on entry, toff on exit)
-template <int WG = PART_WG>
-__device__ __forceinline__ void part_scan(const uint32_t *cnt, uint32_t *toff, uint32_t nb, uint32_t *wsum)
-{
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t per = (nb + WG - 1u) / WG, b0 = tid * per;
-    uint32_t mine = 0;
-    for (uint32_t k = 0; k < per; ++k) mine += b0 + k < nb ? cnt[b0 + k] : 0u;
-    const uint32_t incl = wave_incl_scan(mine);
-    if (lane == 63u) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t run = incl - mine;
-    for (uint32_t k = 0; k < wave; ++k) run += wsum[k];
-    for (uint32_t k = 0; k < per; ++k) if (b0 + k < nb) { toff[b0 + k] = run; run += cnt[b0 + k]; }
-    __syncthreads();
-}
-
-// k_part: workgroup p moves the records of producer p (a group of prod_waves scan waves: their pool segments, one after the
-// other) into their bins; a record leaves as 4 bytes: cell offset inside the bin | t << bin_shift.  Positions are 32-bit
-// (the host keeps a pass below 2^32 records).
-// Round 4 (the round-3 kernel issued 60 instructions per 64 records -- 36 vector, 15 scalar, 6 LDS, 2 memory -- and ran at 2.1
-// cycles per record and CU whatever the number of bins or of workgroups per CU): (1) a tile is COUNTED per bin (LDS add, nothing
-// returned), the counts are scanned, and each record then takes the next slot of its bin's cursor -- the order inside a bin is
-// free -- so no rank travels in registers between the passes; (2) records are loaded four at a time (16-byte loads) and the
-// tile leaves LDS four slots at a time: consecutive positions go out as ONE 16-byte store (the hardware takes them at any
-// 4-byte alignment, tools/store_bench.hip), the others as single words; (3) the bins' global cursors live in the registers of
-// the threads that scan them; the counters are cleared by the scan, and the NEXT tile is counted while this one is written
-// out: three barriers a tile.
-typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(4)));   // four words at any 4-byte alignment
-#if defined(LIME_PART_TIMING) || defined(LIME_APPLY_TIMING) || defined(LIME_SORT_TIMING)      // debug builds: cycles of k_part's (k_apply_tiles') phases, summed over the first wave of every workgroup (tools/r04_part_phases.sh, tools/r04_apply_phases.sh)
-__device__ unsigned long long g_part_pt[8];
-extern "C" int lime_debug_part_times(unsigned long long *out)
-{
-    int rc = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_part_pt), sizeof(g_part_pt));
-    void *p = nullptr; (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_part_pt)); (void)hipMemset(p, 0, sizeof(g_part_pt));
-    return rc;
-}
-#define PT_DECL_ uint64_t pp_t = __builtin_readcyclecounter(), pp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define PT_(i) { const uint64_t n_ = __builtin_readcyclecounter(); pp_acc[i] += n_ - pp_t; pp_t = n_; }
-#ifndef LIME_PT_WAVE
-#define LIME_PT_WAVE 0               // the wave of every workgroup whose cycles are summed (tools/r04_part_phases_waves.sh)
-#endif
-#define PT_END_ if (threadIdx.x == 64 * LIME_PT_WAVE) { for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_part_pt[i_], (unsigned long long)pp_acc[i_]); }
-#endif
-#ifdef LIME_PART_TIMING
-#define PP_DECL PT_DECL_
-#define PP(i) PT_(i)
-#define PP_END PT_END_
-#else
-#define PP_DECL
-#define PP(i)
-#define PP_END
-#endif
-#ifdef LIME_SORT_TIMING
-#define ST_DECL PT_DECL_
-#define ST(i) PT_(i)
-#define ST_END PT_END_
-#define ST_WAITVM asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-#define ST_DECL
-#define ST(i)
-#define ST_END
-#define ST_WAITVM
-#endif
-#ifdef LIME_APPLY_TIMING
-#define AP_DECL PT_DECL_
-#define AP(i) PT_(i)
-#define AP_END PT_END_
-#define AP_WAITVM asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-#define AP_DECL
-#define AP(i)
-#define AP_END
-#define AP_WAITVM
-#endif
-
-// WGS threads and tiles of 16 WGS records: 512 / 8192, or -- few bins: the runs stay long enough -- 256 / 4096 with twice as many
-// workgroups per CU: a tile is a chain of short phases between barriers, and what hides their latencies is other workgroups
-// P64 (round 5): a pass whose record pool holds 2^32 records or more (N = 1e10 at the update density of real text: 2.4 .. 3.9e9 records) --
-// positions in `out` are 64-bit: the bins' cursors are 64-bit registers, a bin's (position - slot) is a 64-bit word in LDS, and the high part
-// of a slot's position travels through the stage in the record's free bits above t (t is 1 here: a score of t left the scan as t records),
-// bits bin_shift + 1 .. 31: six bits at the widest bins, 2^38 records.  Rounds 1-4 sent such a pass to the compare-and-swap path.
-template <int WGS, uint32_t NB_MAX, bool P64>
-__global__ __launch_bounds__(WGS) void k_part(ScanArgs a, const uint64_t *binbase, uint32_t *out)
-{
-    constexpr uint32_t PART_WG = WGS, PART_TILE = WGS * PART_PER, PART_BPT = (NB_MAX + WGS - 1) / WGS;   // (shadow the file's constants)
-    __shared__ uint4 stage4[PART_TILE / 2];                              // (position in out, record) per slot
-    extern __shared__ __attribute__((aligned(8))) uint32_t part_lds[];   // per bin: tile count, cursor (LDS slot), position - slot (P64: two words)
-    __shared__ uint32_t wsum[PART_WG / 64], tile_n_s;
-    uint2 *stage = reinterpret_cast<uint2 *>(stage4);
-    const uint32_t nb = a.n_bins, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t *cnt = part_lds, *cur = cnt + nb, *delta = cur + nb;
-    u64a *delta64 = reinterpret_cast<u64a *>(part_lds + 2u * nb);        // (8-byte aligned: 2 nb words in front; takes the place of delta)
-    typedef typename std::conditional<P64, uint64_t, uint32_t>::type pos_t;
-    const uint32_t per = (nb + PART_WG - 1u) / PART_WG, b0 = tid * per;
-    pos_t G[PART_BPT];                                                   // where this producer's records of bins b0 .. go next
-#pragma unroll
-    for (uint32_t k = 0; k < PART_BPT; ++k) {
-        G[k] = 0u;
-        if (k < per && b0 + k < nb) { G[k] = (pos_t)binbase[b0 + k] + a.counts[(size_t)(b0 + k) * gridDim.x + blockIdx.x]; cnt[b0 + k] = 0u; }
-    }
-    __syncthreads();
-    const uint32_t sh = a.bin_shift, omask = (1u << sh) - 1u, tbit = 1u << sh;
-    // the producer's segments -- (wave, sub-region): 32-bit records, the cell's high part is the sub-region's number -- as one
-    // sequence of tiles
-    const uint32_t n_seg = a.prod_waves * a.n_sub, seg0 = blockIdx.x * n_seg;
-    // The producer's records -- its (wave, sub-region) pool segments one after the other, each padded to a multiple of four records (16-byte loads,
-    // segments start on 64-byte lines) -- are ONE stream cut into tiles of PART_TILE (round 5).  Rounds 3-4 cut every segment into tiles of its own:
-    // nothing lost where a segment holds many tiles, but on 10^8-symbol inputs a wave has 800 .. 6000 records and every producer walked 8 partly
-    // filled tiles where 1 .. 6 full ones do (configs[1] binned: k_part 52 of the pass's 280 us; the text workload: 8 tiles of 0.72 instead of 5.8).
-    // (one word per segment: its padded start | the segment's padding, 0 .. 3 records, in the two low bits -- a second array of counts was the 512 bytes
-    // by which k_part_lines<true> at 477 bins no longer fitted a CU twice)
-    __shared__ uint32_t segp_s[16u * MAX_SUB + 1u];
-    for (uint32_t i = tid; i < n_seg; i += PART_WG) segp_s[i] = a.wave_cnt[seg0 + i];
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        for (uint32_t i = 0; i < n_seg; ++i) { const uint32_t n = segp_s[i]; segp_s[i] = run | ((0u - n) & 3u); run += (n + 3u) & ~3u; }
-        segp_s[n_seg] = run;
-    }
-    __syncthreads();
-    auto seg_p = [&](uint32_t i) { return segp_s[i] & ~3u; };
-    auto seg_n = [&](uint32_t i) { const uint32_t w = segp_s[i]; return (segp_s[i + 1u] & ~3u) - (w & ~3u) - (w & 3u); };
-    const uint32_t l_pad = segp_s[n_seg];                                // padded records of the producer
-    // start in the stream, the segment that holds it; one: the tile's records all lie in that segment (the rule where segments are long: the tile
-    // is then described by two wave-uniform words, tn records from the segment's offset v0 - start on, like rounds 3-4's tiles -- the per-group
-    // meta words below cost the partition of N = 1e10 6 % when every tile used them)
-    struct Tile { uint32_t v0, w0, tn, binoff; bool any, one; };
-    auto tile_at = [&](uint32_t v0, uint32_t w0) {
-        Tile t; t.v0 = v0; t.w0 = w0; t.any = v0 < l_pad; t.one = false; t.tn = 0u; t.binoff = 0u;
-        if (t.any) {
-            while (seg_p(t.w0 + 1u) <= v0) ++t.w0;
-            const uint32_t end = v0 + PART_TILE < l_pad ? v0 + PART_TILE : l_pad;
-            t.one = end <= seg_p(t.w0 + 1u);
-            if (t.one) { const uint32_t left = seg_n(t.w0) - (v0 - seg_p(t.w0)); t.tn = left < PART_TILE ? left : PART_TILE; t.binoff = rec_bin_off(t.w0 % a.n_sub, sh); }
-        }
-        return t;
-    };
-    auto next_tile = [&](const Tile &c) { return tile_at(c.v0 + PART_TILE, c.w0); };
-    // records 4 (j * PART_WG + tid) .. + 3 of the tile (16-byte loads); meta: per group of four how many of them are records (0 .. 4) and the
-    // number of their sub-region (= high part of the cell), six bits a group
-    auto load_tile = [&](const Tile &t, uint4 (&r)[PART_PER / 4], uint32_t &meta) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        meta = 0u;
-        if (t.one) {                                                     // (groups past the tile's end read its last group again: never used, the passes look at tn)
-            const u32x4 *src = reinterpret_cast<const u32x4 *>(a.pool + (size_t)(seg0 + t.w0) * a.cap_w + (t.v0 - seg_p(t.w0)));
-            const uint32_t lastq = (t.tn - 1u) >> 2;
-#pragma unroll
-            for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-                const uint32_t q = j * PART_WG + tid;
-                const u32x4 x = __builtin_nontemporal_load(src + (q < lastq ? q : lastq));
-                r[j] = make_uint4(x.x, x.y, x.z, x.w);
-            }
-            return;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-            const uint32_t v = t.v0 + 4u * (j * PART_WG + tid);
-            r[j] = make_uint4(0u, 0u, 0u, 0u);
-            if (v < l_pad) {
-                uint32_t w = t.w0;
-                while (seg_p(w + 1u) <= v) ++w;
-                const uint32_t off = v - seg_p(w), n = seg_n(w), vc = n - off < 4u ? n - off : 4u;
-                const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(a.pool + (size_t)(seg0 + w) * a.cap_w + off));
-                r[j] = make_uint4(x.x, x.y, x.z, x.w);
-                meta |= (vc | ((w % a.n_sub) << 3)) << (6u * j);
-            }
-        }
-    };
-    auto count_tile = [&](const Tile &t, const uint4 (&r)[PART_PER / 4], uint32_t meta) {
-        if (t.one) {
-#pragma unroll
-            for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-                const uint32_t i = 4u * (j * PART_WG + tid);
-                const uint32_t v[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
-#pragma unroll
-                for (uint32_t k = 0; k < 4; ++k) if (i + k < t.tn) atomicAdd(&cnt[rec_bin_at(v[k], sh, t.binoff)], 1u);
-            }
-            return;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-            const uint32_t vc = (meta >> (6u * j)) & 7u, bo = rec_bin_off((meta >> (6u * j + 3u)) & 7u, sh);
-            const uint32_t v[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) if (k < vc) atomicAdd(&cnt[rec_bin_at(v[k], sh, bo)], 1u);
-        }
-    };
-    Tile tc = tile_at(0u, 0u);
-    if (!tc.any) return;
-    uint4 rv[PART_PER / 4], v4[PART_PER / 4];
-    uint32_t mv = 0, m4 = 0;                                             // the groups' meta words of rv / v4
-    load_tile(tc, rv, mv);
-#pragma unroll
-    for (uint32_t j = 0; j < PART_PER / 4; ++j) v4[j] = rv[j];
-    m4 = mv;
-    count_tile(tc, v4, m4);
-    Tile tn_ = next_tile(tc);
-    if (tn_.any) load_tile(tn_, rv, mv);
-    PP_DECL
-    for (;;) {
-        // ---- scan of the tile's counts: bin cursors (LDS slots), position - slot per bin; the counters go back to zero
-        {
-            uint32_t c[PART_BPT], mine = 0;
-            PP(0)
-            __syncthreads();                                             // the counts are complete
-            PP(1)
-#pragma unroll
-            for (uint32_t k = 0; k < PART_BPT; ++k) { c[k] = (k < per && b0 + k < nb) ? cnt[b0 + k] : 0u; mine += c[k]; }
-            const uint32_t incl = wave_incl_scan(mine);
-            if (lane == 63u) wsum[wave] = incl;
-            __syncthreads();
-            uint32_t run = incl - mine;
-            for (uint32_t k = 0; k < wave; ++k) run += wsum[k];
-#pragma unroll
-            for (uint32_t k = 0; k < PART_BPT; ++k)
-                if (k < per && b0 + k < nb) {
-                    cur[b0 + k] = run;
-                    if (P64) delta64[b0 + k] = (uint64_t)G[k] - run; else delta[b0 + k] = (uint32_t)G[k] - run;
-                    G[k] += c[k]; cnt[b0 + k] = 0u; run += c[k];
-                }
-            if (tid == PART_WG - 1u) tile_n_s = run;                     // (the last thread's running sum: the tile's records)
-            __syncthreads();
-            PP(2)
-        }
-        const uint32_t tile_n = tile_n_s;
-        // ---- every record to the next slot of its bin, with its final position
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-            const uint32_t vc = tc.one ? (4u * (j * PART_WG + tid) < tc.tn ? (tc.tn - 4u * (j * PART_WG + tid) < 4u ? tc.tn - 4u * (j * PART_WG + tid) : 4u) : 0u) : (m4 >> (6u * j)) & 7u;
-            const uint32_t bo = tc.one ? tc.binoff : rec_bin_off((m4 >> (6u * j + 3u)) & 7u, sh);
-            const uint32_t v[4] = {v4[j].x, v4[j].y, v4[j].z, v4[j].w};
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k)
-                if (k < vc) {
-                    const uint32_t b = rec_bin_at(v[k], sh, bo);
-                    const uint32_t slot = atomicAdd(&cur[b], 1u);
-                    if (P64) {
-                        const uint64_t p = slot + delta64[b];
-                        stage[slot] = make_uint2((uint32_t)p, (v[k] & omask) | tbit | (((uint32_t)(p >> 32) << 1) << sh));
-                    } else
-                    stage[slot] = make_uint2(slot + delta[b], (v[k] & omask) | tbit);      // t = 1
-                }
-        }
-        PP(3)
-        __syncthreads();
-        PP(4)
-        // ---- the next tile is counted now (its records have landed; nobody reads the counters before the next scan) ...
-        const Tile tnext = tn_;
-        if (tnext.any) {
-#pragma unroll
-            for (uint32_t j = 0; j < PART_PER / 4; ++j) v4[j] = rv[j];
-            m4 = mv;
-            count_tile(tnext, v4, m4);
-            tn_ = next_tile(tnext);
-            if (tn_.any) load_tile(tn_, rv, mv);                         // ... and the one after it is on its way (in front of this tile's stores: behind them -- what helps k_part_lines -- configs[2] 468 -> 497 us: here the stores are many requests, and the loads queue behind them)
-        }
-        PP(5)
-        // ---- ... while this one leaves LDS, four slots a lane: consecutive positions as one 16-byte store
-        for (uint32_t q = tid; 4u * q < tile_n; q += PART_WG) {
-            const uint4 s0 = stage4[2u * q], s1 = stage4[2u * q + 1u];   // (p0, v0, p1, v1), (p2, v2, p3, v3)
-            if (P64) {                                                   // the positions' high parts ride in the records' bits above t
-                const uint32_t rm = (tbit << 1) - 1u;
-                const uint64_t h0 = (uint64_t)((s0.y >> sh) >> 1) << 32, h1 = (uint64_t)((s0.w >> sh) >> 1) << 32,
-                               h2 = (uint64_t)((s1.y >> sh) >> 1) << 32, h3 = (uint64_t)((s1.w >> sh) >> 1) << 32;
-                if (4u * q + 3u < tile_n && s1.z == s0.x + 3u && h3 == h0) {
-                    u32x4u o = {s0.y & rm, s0.w & rm, s1.y & rm, s1.w & rm};
-                    *reinterpret_cast<u32x4u *>(out + (h0 | s0.x)) = o;
-                } else {
-                    out[h0 | s0.x] = s0.y & rm;
-                    if (4u * q + 1u < tile_n) out[h1 | s0.z] = s0.w & rm;
-                    if (4u * q + 2u < tile_n) out[h2 | s1.x] = s1.y & rm;
-                    if (4u * q + 3u < tile_n) out[h3 | s1.z] = s1.w & rm;
-                }
-            } else
-            if (4u * q + 3u < tile_n && s1.z == s0.x + 3u) {
-                u32x4u o = {s0.y, s0.w, s1.y, s1.w};
-                *reinterpret_cast<u32x4u *>(out + s0.x) = o;
-            } else {
-                out[s0.x] = s0.y;
-                if (4u * q + 1u < tile_n) out[s0.z] = s0.w;
-                if (4u * q + 2u < tile_n) out[s1.x] = s1.y;
-                if (4u * q + 3u < tile_n) out[s1.z] = s1.w;
-            }
-        }
-        PP(6)
-        if (!tnext.any) break;
-        tc = tnext;
-    }
-    PP_END
-}
-
-// k_part_lines: k_part writing WHOLE 64-byte lines.  What bounds the scatter is not its instructions (the leaner kernel above runs
-// no faster than round 3's) but the memory side: stores are written through, every (store instruction, 64-byte line) pair is a
-// request of its own, and a request that does not cover its line is a read-modify-write at the memory: a tile's run of 7..17
-// records per bin costs two of those (tools/store_bench.hip: scattered pieces below 64 bytes write at 0.4 .. 2.9 TB/s, whole
-// lines at 7; WRITE_SIZE of round 3's k_part: 1.85 .. 2.06 x its records).  Here every bin keeps the records that do not fill
-// a line yet -- at most 15 -- in LDS (64 bytes per bin) until the next tiles complete it: after a producer's first, aligning
-// piece of a bin every store to that bin is an aligned 64-byte line (16 lanes), and each line is written once.  Per tile: count
-// per bin; scan (per bin: stage cursor, records to emit = up to the last line border, lines = tasks); records to their bins'
-// stage slots; one 16-lane group per line writes it from (carry, stage); the bins' owner threads move the tiles' tails into the
-// carries.  Needs 64 + 18 bytes of LDS per bin next to the 32 KB stage: up to ~1500 bins (launch_part falls back to k_part).
-constexpr uint32_t PL_TASKS = PART_TILE / 16u + 16u;                     // + one task per bin (a first, aligning piece)
-// (tasks of a tile: its lines -- at most (PART_TILE + 15 nb) / 16 -- plus one per bin whose first piece is not aligned)
-constexpr uint32_t PL_CS = 17;                                          // words per bin's carry row: 16 records on a stride that spreads the bins over the LDS banks (a stride of 16 put every bin's record i on two banks: 77 % of the LDS cycles were bank conflicts)
-__host__ __device__ inline size_t part_lines_lds(uint32_t nb, bool p64 = false) { return (size_t)nb * (16u + 4u * PL_CS) + ((size_t)PL_TASKS + 2u * nb) * 4u + (p64 ? 4u * (size_t)nb : 0u); }
-
-template <bool P64>           // P64: 64-bit positions in `out` (see k_part): the bins' cursors are 64-bit registers, a line's lanes read the high word from ghi[bin]
-__global__ __launch_bounds__(PART_WG) void k_part_lines(ScanArgs a, const uint64_t *binbase, uint32_t *out)
-{
-    __shared__ uint4 stage4[PART_TILE / 4];                              // the tile's records, grouped by bin
-    extern __shared__ __attribute__((aligned(16))) uint32_t part_lds_al[];
-    uint32_t *part_lds = part_lds_al;
-    __shared__ uint32_t wsum[PART_WG / 64], n_tasks_s;
-    uint32_t *stage = reinterpret_cast<uint32_t *>(stage4);
-    const uint32_t nb = a.n_bins, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    // dg[b]: (stage start | carried records << 14 | records to emit << 18, position of the bin's next record in out) -- what a line's lanes need
-    // of its bin, one 8-byte read; task[j]: bin | line of the bin << 11
-    uint32_t *cnt = part_lds, *cur = cnt + nb;
-    uint2 *dg = reinterpret_cast<uint2 *>(cur + nb);                     // (8-byte aligned: part_lds is, and cnt + cur are 2 nb words)
-    uint32_t *cb = reinterpret_cast<uint32_t *>(dg + nb);                // [nb][PL_CS]: the bins' carried records
-    uint32_t *task = cb + (size_t)nb * PL_CS;
-    uint32_t *ghi = task + PL_TASKS + 2u * nb;                           // P64: high word of the bin's next position (part_lines_lds(nb, true))
-    typedef typename std::conditional<P64, uint64_t, uint32_t>::type pos_t;
-    const uint32_t per = (nb + PART_WG - 1u) / PART_WG, b0 = tid * per;
-    constexpr uint32_t BPT = 3;                                          // bins a thread owns at most (launch_part: nb <= 3 * PART_WG)
-    pos_t G[BPT]; uint32_t C[BPT];                                       // per owned bin: position of its next record in out; records carried
-#pragma unroll
-    for (uint32_t k = 0; k < BPT; ++k) {
-        G[k] = 0u; C[k] = 0u;
-        if (k < per && b0 + k < nb) { G[k] = (pos_t)binbase[b0 + k] + a.counts[(size_t)(b0 + k) * gridDim.x + blockIdx.x]; cnt[b0 + k] = 0u; }
-    }
-    __syncthreads();
-    const uint32_t sh = a.bin_shift, omask = (1u << sh) - 1u, tbit = 1u << sh;
-    const uint32_t n_seg = a.prod_waves * a.n_sub, seg0 = blockIdx.x * n_seg;
-    // (the producer's segments as ONE stream cut into tiles, like k_part)
-    // (one word per segment: its padded start | the segment's padding, 0 .. 3 records, in the two low bits -- a second array of counts was the 512 bytes
-    // by which k_part_lines<true> at 477 bins no longer fitted a CU twice)
-    __shared__ uint32_t segp_s[16u * MAX_SUB + 1u];
-    for (uint32_t i = tid; i < n_seg; i += PART_WG) segp_s[i] = a.wave_cnt[seg0 + i];
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        for (uint32_t i = 0; i < n_seg; ++i) { const uint32_t n = segp_s[i]; segp_s[i] = run | ((0u - n) & 3u); run += (n + 3u) & ~3u; }
-        segp_s[n_seg] = run;
-    }
-    __syncthreads();
-    auto seg_p = [&](uint32_t i) { return segp_s[i] & ~3u; };
-    auto seg_n = [&](uint32_t i) { const uint32_t w = segp_s[i]; return (segp_s[i + 1u] & ~3u) - (w & ~3u) - (w & 3u); };
-    const uint32_t l_pad = segp_s[n_seg];                                // padded records of the producer
-    // start in the stream, the segment that holds it; one: the tile's records all lie in that segment (the rule where segments are long: the tile
-    // is then described by two wave-uniform words, tn records from the segment's offset v0 - start on, like rounds 3-4's tiles -- the per-group
-    // meta words below cost the partition of N = 1e10 6 % when every tile used them)
-    struct Tile { uint32_t v0, w0, tn, binoff; bool any, one; };
-    auto tile_at = [&](uint32_t v0, uint32_t w0) {
-        Tile t; t.v0 = v0; t.w0 = w0; t.any = v0 < l_pad; t.one = false; t.tn = 0u; t.binoff = 0u;
-        if (t.any) {
-            while (seg_p(t.w0 + 1u) <= v0) ++t.w0;
-            const uint32_t end = v0 + PART_TILE < l_pad ? v0 + PART_TILE : l_pad;
-            t.one = end <= seg_p(t.w0 + 1u);
-            if (t.one) { const uint32_t left = seg_n(t.w0) - (v0 - seg_p(t.w0)); t.tn = left < PART_TILE ? left : PART_TILE; t.binoff = rec_bin_off(t.w0 % a.n_sub, sh); }
-        }
-        return t;
-    };
-    auto next_tile = [&](const Tile &c) { return tile_at(c.v0 + PART_TILE, c.w0); };
-    // records 4 (j * PART_WG + tid) .. + 3 of the tile (16-byte loads); meta: per group of four how many of them are records (0 .. 4) and the
-    // number of their sub-region (= high part of the cell), six bits a group
-    auto load_tile = [&](const Tile &t, uint4 (&r)[PART_PER / 4], uint32_t &meta) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        meta = 0u;
-        if (t.one) {                                                     // (groups past the tile's end read its last group again: never used, the passes look at tn)
-            const u32x4 *src = reinterpret_cast<const u32x4 *>(a.pool + (size_t)(seg0 + t.w0) * a.cap_w + (t.v0 - seg_p(t.w0)));
-            const uint32_t lastq = (t.tn - 1u) >> 2;
-#pragma unroll
-            for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-                const uint32_t q = j * PART_WG + tid;
-                const u32x4 x = __builtin_nontemporal_load(src + (q < lastq ? q : lastq));
-                r[j] = make_uint4(x.x, x.y, x.z, x.w);
-            }
-            return;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-            const uint32_t v = t.v0 + 4u * (j * PART_WG + tid);
-            r[j] = make_uint4(0u, 0u, 0u, 0u);
-            if (v < l_pad) {
-                uint32_t w = t.w0;
-                while (seg_p(w + 1u) <= v) ++w;
-                const uint32_t off = v - seg_p(w), n = seg_n(w), vc = n - off < 4u ? n - off : 4u;
-                const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(a.pool + (size_t)(seg0 + w) * a.cap_w + off));
-                r[j] = make_uint4(x.x, x.y, x.z, x.w);
-                meta |= (vc | ((w % a.n_sub) << 3)) << (6u * j);
-            }
-        }
-    };
-    auto count_tile = [&](const Tile &t, const uint4 (&r)[PART_PER / 4], uint32_t meta) {
-        if (t.one) {
-#pragma unroll
-            for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-                const uint32_t i = 4u * (j * PART_WG + tid);
-                const uint32_t v[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
-#pragma unroll
-                for (uint32_t k = 0; k < 4; ++k) if (i + k < t.tn) atomicAdd(&cnt[rec_bin_at(v[k], sh, t.binoff)], 1u);
-            }
-            return;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-            const uint32_t vc = (meta >> (6u * j)) & 7u, bo = rec_bin_off((meta >> (6u * j + 3u)) & 7u, sh);
-            const uint32_t v[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) if (k < vc) atomicAdd(&cnt[rec_bin_at(v[k], sh, bo)], 1u);
-        }
-    };
-    Tile tc = tile_at(0u, 0u);
-    if (!tc.any) return;
-    uint4 rv[PART_PER / 4], v4[PART_PER / 4];
-    uint32_t mv = 0, m4 = 0;                                             // the groups' meta words of rv / v4
-    load_tile(tc, rv, mv);
-#pragma unroll
-    for (uint32_t j = 0; j < PART_PER / 4; ++j) v4[j] = rv[j];
-    m4 = mv;
-    count_tile(tc, v4, m4);
-    Tile tn_ = next_tile(tc);
-    if (tn_.any) load_tile(tn_, rv, mv);
-    __syncthreads();                                                     // the first tile's counts are complete
-    PP_DECL
-    for (;;) {
-        uint32_t N[BPT], S[BPT], E[BPT], Cold[BPT];
-        // ---- scan: per owned bin the tile's records n, with the carried ones T; emit E = up to the last line border reached;
-        // L lines = tasks.  One prefix sum over (n | L << 16).
-        {
-            uint32_t L[BPT], mine = 0;
-            PP(0)
-            // (no barrier here: the tile was counted in front of the barrier that ended the last write-out, and the carries the owner threads
-            // have just moved are read by nobody before three more barriers)
-            PP(1)
-#pragma unroll
-            for (uint32_t k = 0; k < BPT; ++k) {
-                N[k] = 0u; E[k] = 0u; L[k] = 0u; Cold[k] = C[k];
-                if (k < per && b0 + k < nb) {
-                    N[k] = cnt[b0 + k]; cnt[b0 + k] = 0u;
-                    const pos_t end = G[k] + C[k] + N[k], border = end & ~(pos_t)15u;
-                    if (border > G[k]) { E[k] = (uint32_t)(border - G[k]); L[k] = (uint32_t)((border >> 4) - (G[k] >> 4)); }
-                }
-                mine += N[k] | (L[k] << 16);
-            }
-            const uint32_t incl = wave_incl_scan(mine);
-            if (lane == 63u) wsum[wave] = incl;
-            __syncthreads();
-            uint32_t run = incl - mine;
-            for (uint32_t k = 0; k < wave; ++k) run += wsum[k];
-#pragma unroll
-            for (uint32_t k = 0; k < BPT; ++k)
-                if (k < per && b0 + k < nb) {
-                    const uint32_t b = b0 + k, s0 = run & 0xFFFFu, t0_ = run >> 16;
-                    S[k] = s0; cur[b] = s0; dg[b] = make_uint2(s0 | (C[k] << 14) | (E[k] << 18), (uint32_t)G[k]);
-                    if (P64) ghi[b] = (uint32_t)((uint64_t)G[k] >> 32);
-                    for (uint32_t i = 0; i < L[k]; ++i) task[t0_ + i] = b | (i << 11);
-                    G[k] += E[k]; C[k] = C[k] + N[k] - E[k];
-                    run += N[k] | (L[k] << 16);
-                }
-            if (tid == PART_WG - 1u) n_tasks_s = run >> 16;              // (the last thread's running sum is the total)
-            __syncthreads();
-            PP(2)
-        }
-        // ---- every record to the next stage slot of its bin
-        if (tc.one) {
-#pragma unroll
-            for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-                const uint32_t i = 4u * (j * PART_WG + tid);
-                const uint32_t v[4] = {v4[j].x, v4[j].y, v4[j].z, v4[j].w};
-#pragma unroll
-                for (uint32_t k = 0; k < 4; ++k)
-                    if (i + k < tc.tn) stage[atomicAdd(&cur[rec_bin_at(v[k], sh, tc.binoff)], 1u)] = (v[k] & omask) | tbit;      // t = 1
-            }
-        } else
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER / 4; ++j) {
-            const uint32_t vc = (m4 >> (6u * j)) & 7u, bo = rec_bin_off((m4 >> (6u * j + 3u)) & 7u, sh);
-            const uint32_t v[4] = {v4[j].x, v4[j].y, v4[j].z, v4[j].w};
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k)
-                if (k < vc) stage[atomicAdd(&cur[rec_bin_at(v[k], sh, bo)], 1u)] = (v[k] & omask) | tbit;      // t = 1
-        }
-        PP(3)
-        __syncthreads();
-        PP(4)
-        // ---- the next tile is counted now (only the counters are touched; its records were loaded a tile ago) -- BEFORE this tile's lines are
-        // stored: the wait for loaded registers is a wait for every older memory operation of the wave, and right behind the stores it was a wait
-        // for their round trip (23 % of the kernel's cycles, tools/r04_part_phases.sh)
-        const Tile tnext = tn_;
-        if (tnext.any) {
-#pragma unroll
-            for (uint32_t j = 0; j < PART_PER / 4; ++j) v4[j] = rv[j];
-            m4 = mv;
-            count_tile(tnext, v4, m4);
-        }
-        PP(5)
-        // ---- a line per 16-lane group: element e of the bin's stream (its carried records, then the tile's) goes to g + e
-        {
-            // (four lines a turn: each is a chain of dependent LDS reads -- task -> bin -> its descriptors -> the record -- and one at a
-            // time the write-out was the longest phase of the kernel)
-            constexpr uint32_t GRPS = PART_WG / 16u, UT = 4;
-            const uint32_t grp = tid >> 4, l16 = tid & 15u, n_tasks = n_tasks_s;
-            for (uint32_t j0 = grp; j0 < n_tasks; j0 += GRPS * UT) {
-                uint32_t tt[UT], val[UT], gh[UT];
-                pos_t pp[UT];
-                uint2 dd[UT];
-                bool on[UT];
-#pragma unroll
-                for (uint32_t u = 0; u < UT; ++u) { const uint32_t j = j0 + u * GRPS; on[u] = j < n_tasks; tt[u] = task[on[u] ? j : 0u]; }
-#pragma unroll
-                for (uint32_t u = 0; u < UT; ++u) { dd[u] = dg[tt[u] & 0x7FFu]; gh[u] = P64 ? ghi[tt[u] & 0x7FFu] : 0u; }
-#pragma unroll
-                for (uint32_t u = 0; u < UT; ++u) {
-                    const uint32_t bq = tt[u] & 0x7FFu, d = dd[u].x, g = dd[u].y;
-                    const uint32_t s0 = d & 0x3FFFu, c = (d >> 14) & 15u, e_n = d >> 18;
-                    const uint32_t e = ((tt[u] >> 11) << 4) + l16 - (g & 15u);      // the lane's element of the bin's stream (before the first one: wraps)
-                    pp[u] = P64 ? (pos_t)((((uint64_t)gh[u] << 32) | g) + e) : (pos_t)(g + e);      // (e < e_n <= 8207 where it is used: no wrap)
-                    on[u] = on[u] && e < e_n;
-                    const uint32_t *srcp = e < c ? cb + (bq * PL_CS + e) : stage + (s0 + e - c);
-                    val[u] = on[u] ? *srcp : 0u;
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < UT; ++u) if (on[u]) __builtin_nontemporal_store(val[u], out + pp[u]);      // (whole lines, read once by the next kernel: -1.5 % against plain stores)
-            }
-        }
-
-        // ---- ... and the tile after it is on its way (behind the stores: by the time its registers are waited for, both are long done)
-        if (tnext.any) {
-            tn_ = next_tile(tnext);
-            if (tn_.any) load_tile(tn_, rv, mv);
-        }
-        PP(6)
-        __syncthreads();                                                 // the lines have been read from the carries and the stage
-        // ---- the tails into the carries: a bin that emitted keeps the last C records of the tile, one that did not appends all of them
-#pragma unroll
-        for (uint32_t k = 0; k < BPT; ++k)
-            if (k < per && b0 + k < nb) {
-                uint32_t *cbb = cb + (size_t)(b0 + k) * PL_CS;
-                if (E[k]) { for (uint32_t i = 0; i < C[k]; ++i) cbb[i] = stage[S[k] + N[k] - C[k] + i]; }
-                else      { for (uint32_t i = 0; i < N[k]; ++i) cbb[Cold[k] + i] = stage[S[k] + i]; }
-            }
-        PP(7)
-        if (!tnext.any) break;
-        tc = tnext;
-    }
-    PP_END
-    // ---- the end of the producer's records: what the bins still carry (a last, partial line each)
-#pragma unroll
-    for (uint32_t k = 0; k < BPT; ++k)
-        if (k < per && b0 + k < nb) for (uint32_t i = 0; i < C[k]; ++i) out[G[k] + i] = cb[(size_t)(b0 + k) * PL_CS + i];
-}
-
-// k_part2: second level, one workgroup per bin (bins wider than a region only): the bin's records are counted per
-// 64 KB region of the table, the regions' bases go to regbase[bin * F2 + sub] (F2 = regions per bin), and a second
-// sweep (served by the L2: a bin's records are a few hundred KB) moves each record to its region's range of `out`,
-// tile by tile through LDS like k_part.
-__global__ __launch_bounds__(PART_WG) void k_part2(const uint32_t *recs, const uint64_t *binbase, uint32_t bin_shift,
-                                                   uint64_t *regbase, uint32_t *out)
-{
-    constexpr uint32_t F2MAX = 1u << (BIN_SHIFT_MAX - REGION_SHIFT);
-    __shared__ uint2 stage[PART_TILE];
-    __shared__ uint32_t cnt[F2MAX], toff[F2MAX], gcur[F2MAX];
-    __shared__ uint32_t wsum[PART_WG / 64];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t f2 = 1u << (bin_shift - REGION_SHIFT), omask = (1u << bin_shift) - 1u;
-    const uint32_t bin = blockIdx.x;
-    const uint64_t lo = binbase[bin], hi = binbase[bin + 1];
-    for (uint32_t i = tid; i < f2; i += PART_WG) cnt[i] = 0u;
-    __syncthreads();
-    // ---- sweep 1: records per region.  Aligned groups of four records (16-byte loads); records outside [lo, hi)
-    // read as 0 = no record (t == 0)
-    {
-        const uint64_t q0 = lo >> 2, q1 = (hi + 3u) >> 2;
-        const uint4 *rq = reinterpret_cast<const uint4 *>(recs);
-        constexpr uint32_t U = 4;
-        for (uint64_t qb = q0; qb < q1; qb += (uint64_t)PART_WG * U) {
-            uint4 r[U];
-#pragma unroll
-            for (uint32_t u = 0; u < U; ++u) {
-                const uint64_t q = qb + (uint64_t)PART_WG * u + tid;
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (q < q1) {
-                    v = rq[q];
-                    const uint64_t i = q << 2;
-                    if (i < lo || i + 3u >= hi) {
-                        v.x = (i >= lo && i < hi) ? v.x : 0u; v.y = (i + 1u >= lo && i + 1u < hi) ? v.y : 0u;
-                        v.z = (i + 2u >= lo && i + 2u < hi) ? v.z : 0u; v.w = (i + 3u >= lo && i + 3u < hi) ? v.w : 0u;
-                    }
-                }
-                r[u] = v;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < U; ++u) {
-                const uint32_t wv[4] = {r[u].x, r[u].y, r[u].z, r[u].w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (wv[k] >> bin_shift) atomicAdd(&cnt[(wv[k] & omask) >> REGION_SHIFT], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    part_scan(cnt, gcur, f2, wsum);                                  // gcur[sub] = where region sub starts inside the bin
-    for (uint32_t i = tid; i < f2; i += PART_WG) { regbase[(size_t)bin * f2 + i] = lo + gcur[i]; cnt[i] = 0u; }
-    __syncthreads();
-    // ---- sweep 2: tile by tile into the regions' ranges (the next tile's records are loaded meanwhile)
-    auto load_tile = [&](uint64_t t0, uint32_t (&v)[PART_PER]) {
-        const uint32_t tn = hi - t0 < PART_TILE ? (uint32_t)(hi - t0) : PART_TILE;
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER; ++j) {
-            const uint32_t i = j * PART_WG + tid;
-            v[j] = i < tn ? recs[t0 + i] : 0u;
-        }
-    };
-    uint32_t nxt[PART_PER];
-    if (lo < hi) load_tile(lo, nxt);
-    for (uint64_t t0 = lo; t0 < hi; t0 += PART_TILE) {
-        const uint32_t tn = hi - t0 < PART_TILE ? (uint32_t)(hi - t0) : PART_TILE;
-        uint32_t val[PART_PER], dr[PART_PER];
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER; ++j) {
-            val[j] = nxt[j]; dr[j] = ~0u;
-            if (val[j] >> bin_shift) {
-                const uint32_t d = (val[j] & omask) >> REGION_SHIFT;
-                dr[j] = d | (atomicAdd(&cnt[d], 1u) << 12);
-            }
-        }
-        if (t0 + PART_TILE < hi) load_tile(t0 + PART_TILE, nxt);
-        __syncthreads();
-        part_scan(cnt, toff, f2, wsum);
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER; ++j)
-            if (dr[j] != ~0u) {
-                const uint32_t d = dr[j] & 0xFFFu, r = dr[j] >> 12;
-                stage[toff[d] + r] = make_uint2(gcur[d] + r, val[j]);
-            }
-        __syncthreads();
-        for (uint32_t i = tid; i < tn; i += PART_WG) { const uint2 sv = stage[i]; out[lo + sv.x] = sv.y; }
-        __syncthreads();
-        for (uint32_t i = tid; i < f2; i += PART_WG) { gcur[i] += cnt[i]; cnt[i] = 0u; }
-        __syncthreads();
-    }
-}
-
-// ---- second level without a second sweep -------------------------------------------------------------------------
-// k_part2 reads a bin's records twice (count per region, then move) because every region's range of the output must be
-// known before the first record moves.  k_sort_tiles does not move records between tiles at all: a bin's records are
-// taken TILE by TILE (8192), each tile is sorted by region in LDS and leaves as 16-bit offsets inside the region (the
-// region is what the position says), 16 KB per tile at out16[row * PART_TILE ..], row = the tile's number over all bins
-// (tbase[bin] + tile of the bin); where the regions' runs start inside the tile goes to the bin's index,
-// idx[(tbase[bin] + t) * (f2 + 1) + sub] (t: the tile of the bin; entry f2: the tile's record count).  k_apply_tiles
-// then builds a region from its run of every tile of the bin.  One read of 4 bytes and one write of 2 per record here,
-// one read of 2 there (k_part2 + k_apply: 8 + 4 and 4).
-__global__ __launch_bounds__(PART_WG) void k_tile_bases(const uint64_t *binbase, uint32_t n_bins, uint32_t *tbase)
-{
-    __shared__ uint32_t cnt[BIN_MAX], toff[BIN_MAX];
-    __shared__ uint32_t wsum[PART_WG / 64];
-    for (uint32_t b = threadIdx.x; b < n_bins; b += PART_WG) cnt[b] = (uint32_t)((binbase[b + 1] - binbase[b] + PART_TILE - 1u) / PART_TILE);
-    __syncthreads();
-    part_scan(cnt, toff, n_bins, wsum);
-    for (uint32_t b = threadIdx.x; b < n_bins; b += PART_WG) { tbase[b] = toff[b]; if (b == n_bins - 1u) tbase[n_bins] = toff[b] + cnt[b]; }
-}
-
-__global__ __launch_bounds__(PART_WG) void k_sort_tiles(const uint32_t *recs, const uint64_t *binbase, uint32_t bin_shift,
-                                                        const uint32_t *tbase, uint16_t *idx, uint16_t *out16, uint32_t nt_rows)
-{
-    constexpr uint32_t F2MAX = 1u << (BIN_SHIFT_MAX - REGION_SHIFT);
-    __shared__ uint4 stage4[PART_TILE / 8];                              // the tile's 16-bit offsets, sorted by region
-    __shared__ uint32_t cnt[F2MAX], toff[F2MAX];
-    __shared__ uint32_t wsum[PART_WG / 64];
-    uint16_t *stage = reinterpret_cast<uint16_t *>(stage4);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t f2 = 1u << (bin_shift - REGION_SHIFT), omask = (1u << bin_shift) - 1u;
-    // every region's counter comes in R copies, a lane uses copy lane % R: 64 lanes on 32 counters is what an LDS add is slowest at (10 cycles
-    // an instruction against 6.5 on 128 and more, tools/lds_bench.hip), and the ranks were a third of the kernel's cycles (tools/r04_sort_phases.sh).
-    // The copies of a region lie next to each other, so the scan hands each its own piece of the region's run.
-    const uint32_t rsh = f2 <= 32u ? 4u : f2 <= 64u ? 3u : f2 <= 128u ? 2u : f2 <= 256u ? 1u : 0u, nc = f2 << rsh;      // nc <= F2MAX counters
-    const uint32_t mycopy = (threadIdx.x & 63u) & ((1u << rsh) - 1u);
-    // workgroup (bin, k) of gridDim.y takes the bin's tiles k, k + gridDim.y, ...: tiles are independent of each other, and a
-    // workgroup per BIN left the CUs unevenly loaded (477 or 1193 workgroups of 8 waves over 256 CUs, 292 on the text workload)
-    const uint32_t bin = blockIdx.x, kq = blockIdx.y, nq = gridDim.y;
-    const uint64_t lo = binbase[bin], hi = binbase[bin + 1];
-    const uint32_t row0 = tbase[bin];
-    uint16_t *bidx = idx + (size_t)row0 * (f2 + 1u);
-    for (uint32_t i = tid; i < nc; i += PART_WG) cnt[i] = 0u;
-    __syncthreads();
-    const uint64_t step = (uint64_t)PART_TILE * nq, first = lo + (uint64_t)PART_TILE * kq;
-    auto load_tile = [&](uint64_t t0, uint32_t (&v)[PART_PER]) {
-        const uint32_t tn = hi - t0 < PART_TILE ? (uint32_t)(hi - t0) : PART_TILE;
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER; ++j) {
-            const uint32_t i = j * PART_WG + tid;
-            v[j] = i < tn ? __builtin_nontemporal_load(recs + t0 + i) : 0u;
-        }
-    };
-    uint32_t nxt[PART_PER];
-    if (first < hi) load_tile(first, nxt);
-    uint32_t row = kq;
-    __shared__ uint32_t nv_s;
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    ST_DECL
-    for (uint64_t t0 = first; t0 < hi; t0 += step, row += nq) {
-        ST_WAITVM ST(0)
-        uint32_t val[PART_PER], dr[PART_PER];
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER; ++j) {
-            val[j] = nxt[j]; dr[j] = ~0u;
-            if (val[j] >> bin_shift) {                                   // (0: no record)
-                const uint32_t d = (((val[j] & omask) >> REGION_SHIFT) << rsh) | mycopy;
-                dr[j] = d | (atomicAdd(&cnt[d], 1u) << 12);
-            }
-        }
-        ST(1)
-        if (t0 + step < hi) load_tile(t0 + step, nxt);
-        ST(2)
-        __syncthreads();
-        ST(3)
-        // the regions' starts inside the tile: f2 <= 512 counters, one per thread; the counters go back to zero right here (round 3 cleared them in
-        // a pass of their own behind two more barriers: four barriers a tile now instead of six)
-        {
-            static_assert(F2MAX <= PART_WG, "a region's counter per thread");
-            const uint32_t c = tid < nc ? cnt[tid] : 0u;
-            const uint32_t incl = wave_incl_scan(c);
-            if (lane == 63u) wsum[wave] = incl;
-            __syncthreads();
-            uint32_t run = incl - c;
-            for (uint32_t k = 0; k < wave; ++k) run += wsum[k];
-            // (the tile's f2 + 1 entries lie together -- idx[(row0 + row) * (f2 + 1) + region] --: one or a few whole lines per tile.  Until round 6 the index
-            // was region-major, every tile writing f2 + 1 two-byte entries a row stride apart: 0.5 ms of k_sort_tiles' 2.85 at 512 regions per bin)
-            if (tid < nc) { toff[tid] = run; cnt[tid] = 0u; if (!(tid & ((1u << rsh) - 1u))) bidx[(size_t)row * (f2 + 1u) + (tid >> rsh)] = (uint16_t)run; }
-            if (tid == nc - 1u) { nv_s = run + c; bidx[(size_t)row * (f2 + 1u) + f2] = (uint16_t)(run + c); }
-            __syncthreads();
-        }
-        ST(4)
-#pragma unroll
-        for (uint32_t j = 0; j < PART_PER; ++j)
-            if (dr[j] != ~0u) stage[toff[dr[j] & 0xFFFu] + (dr[j] >> 12)] = (uint16_t)(val[j] & ((1u << REGION_SHIFT) - 1u));
-        ST(5)
-        __syncthreads();
-        ST(6)
-        const uint32_t nv = nv_s;                                        // records of the tile
-        uint4 *dst = reinterpret_cast<uint4 *>(out16 + (size_t)(row0 + row) * ROW_STRIDE);
-        // (whole 16-byte groups: the row is the tile's alone.  Non-temporal where the rows of the pass do not fit the Infinity Cache anyway -- N = 1e10
-        // 1.56 -> 1.50 ms and 3 % in k_apply_tiles, configs[4]'s shape 433 -> 391 us --; where they do, plain stores leave them there for
-        // k_apply_tiles: the text workload's 48 MB of rows 65 against 101 us in that kernel)
-        if (nt_rows) {
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            for (uint32_t i = tid; i < (nv + 7u) / 8u; i += PART_WG) { const uint4 v = stage4[i]; const u32x4 x = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(x, reinterpret_cast<u32x4 *>(dst + i)); }
-        } else
-            for (uint32_t i = tid; i < (nv + 7u) / 8u; i += PART_WG) dst[i] = stage4[i];
-        // (no barrier here: the next tile's ranks touch the counters only -- cleared above -- and its staging comes behind two barriers)
-        ST(7)
-    }
-    ST_END
-}
-
-// k_apply_tiles: k_apply on the output of k_sort_tiles: the region's records are its run in every tile of its bin.
-// Wave w takes the tiles w, w + 8, ... of the bin (a lane reads one tile's two index entries), then their runs one after
-// the other, four 16-bit records per lane and step from 8-byte-aligned loads (and the 65th group of a run with them); the
-// loads of the next four runs are in flight while four are added.
-// MODE (round 5; clusterChoose without the table, ClusterBWT_DA.cpp:385-423): 0 -- the finished region is written to the table; 1 -- nothing is
-// written: the region's row segments give row maxima and non-zero counts (whole rows: plain stores; rows that cross a region border: atomic max /
-// add on the zeroed arrays) and the count of its last segment; 2 -- the regions are built once more and the rows that passed the host's test
-// (row_off[r + 1] > row_off[r]) leave their non-zero cells as (idRef, sim) pairs in ascending idRef at pairs[row_off[r] ..] (regions without a passing
-// row are skipped before a record is read).  Both need n_refs >= 256 (at most 257 row segments per 64 KB region, a wave each).
-// bytes wb .. wb + 3 of a word that lie in [s, e)
-__device__ __forceinline__ uint32_t keep_bytes(uint32_t x, uint32_t wb, uint32_t s, uint32_t e)
-{
-    uint32_t m = 0xFFFFFFFFu;
-    if (wb < s) { const uint32_t d = s - wb; m = d >= 4u ? 0u : m << (8u * d); }
-    if (wb + 4u > e) { const uint32_t d = e > wb ? e - wb : 0u; m &= d >= 4u ? 0xFFFFFFFFu : ((1u << (8u * d)) - 1u); }
-    return x & m;
-}
-__device__ __forceinline__ uint32_t nz_bytes(uint32_t x) { return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; }   // bit 7 of every non-zero byte
-
-// MODE 1 with at most FIN_SEGS row segments per region (n_refs >= 256): every thread looks at its eight 16-byte pieces of the region -- 97 % of
-// them are zero on configs[2] --, finds the row segment of a non-zero piece with one multiplication by 1 / n_refs (corrected by one) and adds the
-// piece's maximum / non-zero count to the segment's two LDS words; a piece that holds a row border goes byte by byte.  (The first version gave every
-// segment to a wave -- 14 segments of 5000 bytes on 8 waves, each a chain of dependent LDS reads and wave reductions: 1.27 ms on configs[2]
-// against 0.89 for the kernel that WRITES the table.)
-constexpr uint32_t FIN_SEGS = 258;
-// the segments' owner threads: whole rows are stored, rows that cross a region border added atomically (the arrays were zeroed); seg_acc is left zero
-__device__ __forceinline__ void fin_region_store(uint32_t *seg_acc, const ApplyFin &f, uint32_t region, uint64_t r0, uint32_t o0, uint32_t nseg, uint32_t len)
-{
-    for (uint32_t j = threadIdx.x; j < nseg; j += APPLY_WG) {
-        const uint32_t mx = seg_acc[j], nz = seg_acc[nseg + j];
-        seg_acc[j] = 0u; seg_acc[nseg + j] = 0u;
-        const uint64_t row = r0 + j, e64 = (uint64_t)(j + 1u) * f.n_refs - o0;
-        const bool whole = (j != 0u || o0 == 0u) && e64 <= len;
-        if (whole) { f.row_max[row] = mx; f.row_nnz[row] = nz; }
-        else { if (mx) atomicMax(&f.row_max[row], mx); if (nz) atomicAdd(&f.row_nnz[row], nz); }
-        if (j == nseg - 1u) f.last_nnz[region] = nz;
-    }
-}
-__device__ __forceinline__ void fin_region_rows(uint4 *reg4, uint32_t *seg_acc, const ApplyFin &f, uint32_t region, uint64_t r0, uint32_t o0, uint32_t nseg, uint32_t len)
-{
-    // (seg_acc is all zero on entry: cleared at the kernel's start, and by the loop at the end of this function behind every use; the region's LDS copy
-    // is left all zero too -- a piece that is looked at and not zero is zeroed right there: the next region needs no clearing pass)
-    const uint32_t tid = threadIdx.x;
-    const float invf = 1.0f / (float)f.n_refs;
-    const uint32_t nq = (len + 15u) >> 4;
-    for (uint32_t c = tid; c < nq; c += APPLY_WG) {
-        const uint4 v = reg4[c];
-        if (!(v.x | v.y | v.z | v.w)) continue;
-        reg4[c] = make_uint4(0u, 0u, 0u, 0u);
-        const uint32_t x0 = o0 + 16u * c;                          // position of the piece's first byte counted from the start of row r0 (< 2^26)
-        uint32_t seg = (uint32_t)((float)x0 * invf);
-        if (seg * f.n_refs > x0) --seg; else if ((seg + 1u) * f.n_refs <= x0) ++seg;      // (float: off by one at most)
-        const uint32_t border = (seg + 1u) * f.n_refs - o0;        // where the next row starts, in region bytes
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        if (border >= 16u * c + 16u) {                             // the whole piece lies in one row
-            uint32_t m = 0, z = 0;
-#pragma unroll
-            for (uint32_t i = 0; i < 4; ++i) {
-                const uint32_t a0 = w[i] & 255u, a1 = (w[i] >> 8) & 255u, a2 = (w[i] >> 16) & 255u, a3 = w[i] >> 24;
-                const uint32_t m01 = a0 > a1 ? a0 : a1, m23 = a2 > a3 ? a2 : a3, mm = m01 > m23 ? m01 : m23;
-                m = mm > m ? mm : m;
-                z += (uint32_t)__popc(nz_bytes(w[i]));
-            }
-            atomicMax(&seg_acc[seg], m); atomicAdd(&seg_acc[nseg + seg], z);
-        } else {                                                   // a row border inside (n_refs >= 256: at most one)
-            for (uint32_t b = 0; b < 16u; ++b) {
-                const uint32_t val = (w[b >> 2] >> (8u * (b & 3u))) & 255u;
-                if (!val) continue;
-                const uint32_t sg = seg + (16u * c + b >= border ? 1u : 0u);
-                atomicMax(&seg_acc[sg], val); atomicAdd(&seg_acc[nseg + sg], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    fin_region_store(seg_acc, f, region, r0, o0, nseg, len);
-}
-
-template <int MODE>
-__device__ __forceinline__ void fin_region(const uint4 *reg4, const ApplyFin &f, uint32_t region, uint64_t r0, uint32_t o0, uint32_t nseg, uint32_t len)
-{
-    constexpr uint32_t NWV = APPLY_WG / 64;
-    const uint32_t lane = lane_id(), wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint64_t reg_base = (uint64_t)region << REGION_SHIFT;
-    for (uint32_t j = wave; j < nseg; j += NWV) {                 // a wave per row segment: row r0 + j, bytes [s, e) of the region
-        const uint64_t row = r0 + j;
-        const uint32_t s = j ? (uint32_t)((uint64_t)j * f.n_refs - o0) : 0u;
-        const uint64_t e64 = (uint64_t)(j + 1u) * f.n_refs - o0;
-        const uint32_t e = e64 < len ? (uint32_t)e64 : len;
-        if (MODE == 1) {
-            uint32_t mx = 0, nz = 0;
-            for (uint32_t c = (s >> 4) + lane; 16u * c < e; c += 64u) {
-                uint4 v = reg4[c];
-                if (16u * c < s || 16u * c + 16u > e) {
-                    v.x = keep_bytes(v.x, 16u * c, s, e); v.y = keep_bytes(v.y, 16u * c + 4u, s, e);
-                    v.z = keep_bytes(v.z, 16u * c + 8u, s, e); v.w = keep_bytes(v.w, 16u * c + 12u, s, e);
-                }
-                if (v.x | v.y | v.z | v.w) {
-                    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (uint32_t i = 0; i < 4; ++i) {
-                        const uint32_t a0 = w[i] & 255u, a1 = (w[i] >> 8) & 255u, a2 = (w[i] >> 16) & 255u, a3 = w[i] >> 24;
-                        const uint32_t m01 = a0 > a1 ? a0 : a1, m23 = a2 > a3 ? a2 : a3, m = m01 > m23 ? m01 : m23;
-                        mx = m > mx ? m : mx;
-                        nz += (uint32_t)__popc(nz_bytes(w[i]));
-                    }
-                }
-            }
-            mx = wave_max(mx); nz = wave_sum(nz);
-            if (lane == 0) {
-                const bool whole = (j != 0u || o0 == 0u) && e64 <= len;
-                if (whole) { f.row_max[row] = mx; f.row_nnz[row] = nz; }
-                else { if (mx) atomicMax(&f.row_max[row], mx); if (nz) atomicAdd(&f.row_nnz[row], nz); }
-                if (j == nseg - 1u) f.last_nnz[region] = nz;
-            }
-        } else {
-            const uint64_t p0 = f.row_off[row], p1 = f.row_off[row + 1u];
-            if (p1 == p0) continue;                                // the read did not pass (wave-uniform)
-            uint64_t run = p0;
-            if (j == 0u && o0 != 0u) {                             // the row began in an earlier region: its cells there come first
-                const uint32_t k0 = (uint32_t)((row * f.n_refs) >> REGION_SHIFT);
-                for (uint32_t kk = k0; kk < region; ++kk) run += f.last_nnz[kk];
-            }
-            const uint32_t id0 = (uint32_t)(reg_base - row * f.n_refs);      // idRef of the region's byte 0 in this row (wraps for j > 0: added back below)
-            for (uint32_t c0 = s >> 4; 16u * c0 < e; c0 += 64u) {
-                const uint32_t c = c0 + lane;
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (16u * c < e) {
-                    v = reg4[c];
-                    if (16u * c < s || 16u * c + 16u > e) {
-                        v.x = keep_bytes(v.x, 16u * c, s, e); v.y = keep_bytes(v.y, 16u * c + 4u, s, e);
-                        v.z = keep_bytes(v.z, 16u * c + 8u, s, e); v.w = keep_bytes(v.w, 16u * c + 12u, s, e);
-                    }
-                }
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                const uint32_t cnt = (uint32_t)(__popc(nz_bytes(w[0])) + __popc(nz_bytes(w[1])) + __popc(nz_bytes(w[2])) + __popc(nz_bytes(w[3])));
-                if (!__ballot(cnt != 0u)) continue;
-                const uint32_t incl = wave_incl_scan(cnt);
-                uint64_t at = run + (incl - cnt);
-                if (cnt) {
-#pragma unroll
-                    for (uint32_t i = 0; i < 4; ++i)
-#pragma unroll
-                        for (uint32_t b = 0; b < 4; ++b) {
-                            const uint32_t val = (w[i] >> (8u * b)) & 255u;
-                            if (val) { lime_pair_t pr; pr.id_ref = id0 + 16u * c + 4u * i + b; pr.sim = val; f.pairs[at++] = pr; }
-                        }
-                }
-                run += rl32(incl, 63);
-            }
-        }
-    }
-}
-
-template <bool WIDE, int MODE> __global__ __launch_bounds__(APPLY_WG) void k_apply_tiles(uint8_t *sim, size_t sim_bytes, const uint16_t *recs16, const uint32_t *tbase,
-                                                          const uint16_t *idx, uint32_t bin_shift, uint32_t n_regions, ApplyFin fin, uint32_t lg_in)
-{
-    constexpr uint32_t RW = (1u << REGION_SHIFT) / 4u;           // words per region
-    constexpr uint32_t NWV = APPLY_WG / 64, UR = 4;
-    __shared__ uint4 reg4[RW / 4];
-    __shared__ uint32_t seg_acc[MODE == 1 ? 2 * FIN_SEGS : 2];   // MODE 1: maximum and non-zero count of the region's row segments
-    // MODE 1: every wave queues the cells its adds found at 0 -- each non-zero cell of the region exactly once, as long as none wraps (a wrap raises
-    // ovf_s and the region is rebuilt) -- and the look at the region is a walk over those queues instead of over 64 KB (below)
-    constexpr uint32_t QW = 768;                                 // cells a wave can queue per region (more: the region is looked at piece by piece); two workgroups per CU: 64 + 12 + 2 KB each
-    __shared__ uint16_t cell_q[MODE == 1 ? NWV * QW : 2];
-    __shared__ uint32_t qovf_s[2];                               // by the parity of the workgroup's region count: set during a region's adds, read behind them, cleared a region later
-    uint32_t par = 0;
-    uint32_t qn = 0;                                             // cells in this wave's queue (wave-uniform)
-    uint32_t pf = 0, po01 = 0, po23 = 0;                         // a lane's first adds of the last add4 (a bit each) and their cells, until qflush() queues them
-    uint32_t *reg = reinterpret_cast<uint32_t *>(reg4);
-    const uint32_t lane = lane_id(), wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: the runs' borders and sources stay scalar
-    const uint32_t f2 = 1u << (bin_shift - REGION_SHIFT);
-    // one record: + 1 modulo 256 on byte o of the region.  Fast form: ONE returning LDS add of 1 << (8 x byte) on the word -- exact as long
-    // as no cell of the word passes 255 (a carry would run into its neighbour); an add that finds its cell at 255 raises the region's
-    // flag, and the region is then built again with the exact form, a compare-and-swap per record (real collections never get
-    // there: a cell's sum is bounded by the read length; the wrap-around fixtures and the iid generator at few reads do).
-    __shared__ uint32_t ovf_s;
-    bool exact = false;
-    auto add_exact = [&](uint32_t o, uint32_t t = 1u) {
-        const uint32_t sh = (o & 3u) * 8u;
-        uint32_t *w = &reg[o >> 2];
-        uint32_t seen = *w;
-        for (;;) {
-            const uint32_t b = ((seen >> sh) + t) & 255u;
-            const uint32_t old = atomicCAS(w, seen, (seen & ~(255u << sh)) | (b << sh));
-            if (old == seen) break;
-            seen = old;
-        }
-    };
-    // the four records of a lane's group [p, p + 4), those inside [fa, fe) only.  The four adds leave together and are looked at together: a
-    // record outside the run adds 0 to whatever word its bits name (one add at a time behind its own branch, each waiting for its answer,
-    // the adds were 77 % of the kernel's cycles at N = 1e10 and 19 .. 34 % elsewhere: tools/r04_apply_phases.sh)
-    // (`on`: MODE 1 calls with all the wave's lanes and says which of them hold a group -- its queue count is wave-uniform state that a call
-    // under a divergent branch would leave stale in the lanes that sat out)
-    auto add4 = [&](uint32_t p, uint2 w, uint32_t fa, uint32_t fe, bool on = true) {
-        const uint32_t o[4] = {w.x & 0xFFFFu, w.x >> 16, w.y & 0xFFFFu, w.y >> 16};
-        if (exact) {
-#pragma unroll
-            for (uint32_t i = 0; i < 4; ++i) if (on && p + i >= fa && p + i < fe) add_exact(o[i]);
-            return;
-        }
-        // (the valid slots as a 4-bit mask: lo .. hi of the group; p + 4 > fa and p < fe hold for every group that gets here.  The flag is
-        // also raised by an add of 0 that meets a cell at 255 -- harmless: the exact pass follows)
-        const uint32_t lo = fa > p ? fa - p : 0u, hi = fe - p < 4u ? fe - p : 4u;
-        const uint32_t m = on ? ((1u << hi) - 1u) & (~0u << lo) : 0u;
-        uint32_t old[4], sh[4];
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-            sh[i] = (o[i] << 3) & 24u;
-            old[i] = atomicAdd(&reg[o[i] >> 2], ((m >> i) & 1u) << sh[i]);
-        }
-        bool over = false;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) over |= __builtin_amdgcn_ubfe(old[i], sh[i], 8u) == 255u;
-        if (over) ovf_s = 1u;
-        if (MODE == 1) {                                          // first adds to their cells: noted here, queued by qflush() -- the callers' lanes differ, and
-            pf = 0u;                                              // the queue's count is wave-uniform state that must be kept by ALL lanes
-#pragma unroll
-            for (uint32_t i = 0; i < 4; ++i) pf |= (uint32_t)(((m >> i) & 1u) != 0u && __builtin_amdgcn_ubfe(old[i], sh[i], 8u) == 0u) << i;
-            po01 = o[0] | (o[1] << 16); po23 = o[2] | (o[3] << 16);
-        }
-    };
-    // (called by all lanes of the wave, right behind an add4 under its condition)
-    auto qflush = [&]() {
-        if (MODE != 1) return;
-        uint16_t *myq = cell_q + wave * QW;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-            const bool first = (pf >> i) & 1u;
-            const uint64_t mf = __ballot(first);
-            if (first) { const uint32_t at = qn + rank_in(mf); if (at < QW) myq[at] = (uint16_t)((i & 2u ? po23 : po01) >> (16u * (i & 1u))); }
-            // (the count is ONE number per wave: taken through a scalar register, not a per-lane copy -- the compiler lets lanes that have no further
-            // groups leave the callers' `while (__ballot(..))` loops on their own, and a lane that sat a round out would come back with a stale count and
-            // write over queued cells: round 6, the run loop of grouped_runs with 16 runs an instruction lost 60 % of a dense region's cells that way)
-            qn = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qn + (uint32_t)__popcll(mf)));
-        }
-        pf = 0u;
-    };
-    auto add4c = [&](bool on, uint32_t p, uint2 w, uint32_t fa, uint32_t fe) {
-        if (on) add4(p, w, fa, fe);
-        qflush();
-    };
-    static_assert(UR == 4, "a step's four runs share one pass over their groups 64 .. 79: sixteen lanes each");
-    struct Step { uint2 v[UR], v2[UR], vx; uint32_t fa[UR], fe[UR], q[UR], fax, fex, qx; const uint16_t *src[UR]; };
-    if (threadIdx.x == 0) { ovf_s = 0u; qovf_s[0] = 0u; qovf_s[1] = 0u; }
-    // A workgroup walks regions blockIdx.x, + gridDim.x, ... (two workgroups per CU).  What a region needs before its records
-    // can be read -- its bin's tile range, then its index entries -- is fetched while the region before it is worked on: a
-    // workgroup per region paid that chain of dependent loads per region (configs[2]: 76 k regions of 1.6 k records each).
-    const uint32_t bsh = bin_shift - REGION_SHIFT;
-    auto index_of = [&](uint32_t r, uint32_t r0, uint32_t nr, uint32_t outer, uint32_t &a_, uint32_t &e_) {   // lane l: the index entries of tile outer + wave + NWV * l of the region's bin
-        const uint32_t t = outer + wave + NWV * lane;
-        a_ = 0u; e_ = 0u;
-        if (t < nr) { const uint16_t *ia = idx + (size_t)(r0 + t) * (f2 + 1u) + (r & (f2 - 1u)); a_ = ia[0]; e_ = ia[1]; }      // (tile-major: the lanes' entries lie a tile's f2 + 1 apart; the 64 regions an XCD works on at a time share their lines)
-    };
-    auto runs_of = [&](uint32_t nr, uint32_t outer) {             // tiles of this round: the wave's are wave, wave + NWV, ... < left
-        const uint32_t left = nr - outer;
-        return left > wave ? ((left - wave + NWV - 1u) / NWV < 64u ? (left - wave + NWV - 1u) / NWV : 64u) : 0u;
-    };
-    auto load_step = [&](uint32_t l0, Step &s, uint32_t a_, uint32_t e_, uint32_t nl_, uint32_t row_w) {   // the first 256 records of the runs l0 .. l0 + UR of this wave (row_w: the wave's first tile row)
-#pragma unroll
-        for (uint32_t u = 0; u < UR; ++u) {
-            const uint32_t l = l0 + u;
-            s.fa[u] = l < nl_ ? rl32(a_, l) : 0u; s.fe[u] = l < nl_ ? rl32(e_, l) : 0u;
-            s.q[u] = (s.fa[u] >> 2) + lane;                       // this lane's group of four records
-            s.src[u] = recs16 + (size_t)(row_w + NWV * l) * ROW_STRIDE;
-            s.v[u] = make_uint2(0u, 0u);
-            if (s.q[u] * 4u < s.fe[u]) s.v[u] = *reinterpret_cast<const uint2 *>(s.src[u] + (size_t)s.q[u] * 4u);
-            if (!WIDE) {                                          // the run's 65th group, fetched with the step
-                s.v2[u] = make_uint2(0u, 0u);
-                if ((s.q[u] + 64u) * 4u < s.fe[u]) s.v2[u] = *reinterpret_cast<const uint2 *>(s.src[u] + (size_t)(s.q[u] + 64u) * 4u);
-            }
-        }
-        // WIDE (many records: chosen at the launch).  The groups 64 .. 79 of the step's four runs, sixteen lanes a run, come with the step and are added in ONE pass: a run is 256 records on
-        // average at 32 regions per bin and few start on a group border, so every second run has a 65th group -- fetched when its turn came it
-        // was a memory round trip, and added in a pass of its own it cost the instructions of a full pass for one or two lanes.
-        if (WIDE) {
-            const uint32_t ux = lane >> 4, lx = l0 + ux;
-            // (the shuffles by ALL lanes, then the select: under the condition the compiler branches, and a lane reading from a lane the branch
-            // has switched off gets 0 -- with 33 .. 63 runs per wave and a last step of fewer than four, the source lanes l0 + ux sit in lane groups
-            // whose own run does not exist: the groups 64 .. 79 of the step's runs were dropped, silently -- a bin of 257 .. 511 tiles whose count
-            // is not a multiple of 32, e.g. the N = 1e10 series' 307 tiles per bin; found in round 5 by the clustered full-size test)
-            const uint32_t sa = (uint32_t)__shfl((int)a_, (int)(lx & 63u)), se = (uint32_t)__shfl((int)e_, (int)(lx & 63u));
-            s.fax = lx < nl_ ? sa : 0u; s.fex = lx < nl_ ? se : 0u;
-            s.qx = (s.fax >> 2) + 64u + (lane & 15u);
-            s.vx = make_uint2(0u, 0u);
-            if (s.qx * 4u < s.fex) s.vx = *reinterpret_cast<const uint2 *>(recs16 + (size_t)(row_w + NWV * lx) * ROW_STRIDE + (size_t)s.qx * 4u);
-        }
-    };
-    // Short runs (round 6).  A tile row holds 8192 records of its bin, so a region's run in it has 8192 / (regions per bin) records on average: 256 at 32
-    // regions per bin (the N = 1e10 series), 64 at 128 (tables of 10 GB), 16 at 512 -- and with a whole wave per run, a lane a group of four, such runs
-    // keep 16 or 4 of the 64 lanes busy: the kernel's time followed the NUMBER of runs, not of records (configs[4]'s shape, clustered: 4.5 ms at 128
-    // regions per bin, 7.2 at 256, 13.0 at 512 for the same 1.7e9 records).  Here 2^lg lanes share a run, a lane two groups of four: 64 >> lg runs per
-    // instruction, 8 << lg records of each per pass (the mean run x 2); longer runs take further passes.
-    const uint32_t lg = lg_in ? lg_in : (f2 >= 512u ? 2u : f2 == 256u ? 3u : f2 == 128u ? 4u : f2 == 64u ? 5u : 6u);      // 6: a wave per run (below)
-    struct GStep { uint2 v0, v1; uint32_t fa, fe, q; const uint16_t *src; };
-    auto grouped_runs = [&](uint32_t a_, uint32_t e_, uint32_t nl_, uint32_t row_w) {
-        const uint32_t LG = 1u << lg, rpi = 64u >> lg, lr_in = lane >> lg, li = lane & (LG - 1u);
-        auto gload = [&](uint32_t l0, GStep &s) {
-            const uint32_t lr = l0 + lr_in;
-            const uint32_t sa = (uint32_t)__shfl((int)a_, (int)(lr & 63u)), se = (uint32_t)__shfl((int)e_, (int)(lr & 63u));      // (by all lanes, the select behind)
-            const bool valid = lr < nl_;
-            s.fa = valid ? sa : 0u; s.fe = valid ? se : 0u;
-            s.q = (s.fa >> 2) + 2u * li;                          // this lane's two groups of four: q, q + 1
-            s.src = recs16 + (size_t)(row_w + NWV * (valid ? lr : 0u)) * ROW_STRIDE;
-            s.v0 = make_uint2(0u, 0u); s.v1 = make_uint2(0u, 0u);
-            if (s.q * 4u < s.fe) s.v0 = *reinterpret_cast<const uint2 *>(s.src + (size_t)s.q * 4u);
-            if ((s.q + 1u) * 4u < s.fe) s.v1 = *reinterpret_cast<const uint2 *>(s.src + (size_t)(s.q + 1u) * 4u);
-        };
-        GStep nxt;
-        gload(0u, nxt);
-        for (uint32_t l0 = 0; l0 < nl_; l0 += rpi) {
-            const GStep cur = nxt;
-            if (l0 + rpi < nl_) gload(l0 + rpi, nxt);              // the next runs' loads go out before these are added
-            add4c(cur.q * 4u < cur.fe, cur.q * 4u, cur.v0, cur.fa, cur.fe);
-            add4c((cur.q + 1u) * 4u < cur.fe, (cur.q + 1u) * 4u, cur.v1, cur.fa, cur.fe);
-            for (uint32_t q = cur.q + 2u * LG; __ballot(q * 4u < cur.fe); q += 2u * LG) {      // runs beyond 8 << lg records
-                uint2 w0 = make_uint2(0u, 0u), w1 = make_uint2(0u, 0u);
-                if (q * 4u < cur.fe) w0 = *reinterpret_cast<const uint2 *>(cur.src + (size_t)q * 4u);
-                if ((q + 1u) * 4u < cur.fe) w1 = *reinterpret_cast<const uint2 *>(cur.src + (size_t)(q + 1u) * 4u);
-                add4c(q * 4u < cur.fe, q * 4u, w0, cur.fa, cur.fe);
-                add4c((q + 1u) * 4u < cur.fe, (q + 1u) * 4u, w1, cur.fa, cur.fe);
-            }
-        }
-    };
-    // Workgroup b runs on XCD b % 8 (round-robin dispatch), and the runs of neighbouring regions are neighbours in every tile row -- 32 to 128 bytes each
-    // at 128 to 512 regions per bin: with region = b the eight XCDs each fetched the same 128-byte lines into their own L2.  Each XCD takes a block of
-    // consecutive regions instead: its 64 resident workgroups work on 64 neighbouring regions at a time.
-    uint32_t region = (gridDim.x & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    if (region >= n_regions) return;
-    uint32_t row0 = tbase[region >> bsh], n_rows = tbase[(region >> bsh) + 1u] - row0;
-    uint32_t a, e;
-    index_of(region, row0, n_rows, 0u, a, e);
-    // MODE 1, 2: the region's rows -- first row, offset of the region's first byte in it, row segments, bytes inside the table | (MODE 2: no row of
-    // it passed) << 31 -- from k_region_rows' array: a scalar load per region, the next region's in flight while this one is built
-    uint4 ri = make_uint4(0u, 0u, 0u, 0u);
-    if (MODE != 0) ri = fin.region_rows[region];
-    if (MODE == 1) for (uint32_t i = threadIdx.x; i < 2u * FIN_SEGS; i += APPLY_WG) seg_acc[i] = 0u;
-    bool clean = false;                                           // the LDS copy is all zero already (MODE 1: the last region's look at it left it so)
-    __syncthreads();                                              // (everybody sees the cleared flag)
-    AP_DECL
-    for (;;) {
-        const uint32_t next = region + gridDim.x;
-        const bool more = next < n_regions;
-        uint32_t nrow0 = 0, nrow1 = 0;                            // the next region's tile range: needed only after this one's records
-        if (more) { nrow0 = tbase[next >> bsh]; nrow1 = tbase[(next >> bsh) + 1u]; }
-        uint4 nri = make_uint4(0u, 0u, 0u, 0u);
-        if (MODE != 0 && more) nri = fin.region_rows[next];
-        const bool skip = MODE == 2 && (ri.w >> 31) != 0u;
-        if (MODE == 1 && threadIdx.x == 0) qovf_s[par ^ 1u] = 0u;  // (last read a region ago, set again only behind this region's last barrier)
-        if (!skip)
-        for (exact = false;; exact = true) {                      // once; twice if a cell passed 255 under the fast adds
-        qn = 0u;
-        if (!(MODE == 1 && clean && !exact)) {
-            for (uint32_t i = threadIdx.x; i < RW / 4; i += APPLY_WG) reg4[i] = make_uint4(0u, 0u, 0u, 0u);
-            __syncthreads();
-        }
-        AP(0)
-        for (uint32_t outer = 0; outer < n_rows; outer += NWV * 64u) {
-            const uint32_t nl = runs_of(n_rows, outer);
-            if (outer || exact) index_of(region, row0, n_rows, outer, a, e);
-            // (wave-uniform.  The modes without the table take this path for every group size, a wave per run included: with both paths compiled in they
-            // pass 128 registers and a CU holds one workgroup of them instead of two)
-            if (MODE != 0 || lg < 6u) { if (nl) grouped_runs(a, e, nl, row0 + outer + wave); continue; }
-            Step nxt;
-            if (nl) load_step(0u, nxt, a, e, nl, row0 + outer + wave);
-            AP(1)
-            for (uint32_t l0 = 0; l0 < nl; l0 += UR) {
-                AP_WAITVM AP(2)
-                Step cur = nxt;
-                if (l0 + UR < nl) load_step(l0 + UR, nxt, a, e, nl, row0 + outer + wave);     // the next runs' loads go out before these are added
-                AP(3)
-                if (WIDE) {
-#pragma unroll
-                    for (uint32_t u = 0; u < UR; ++u)
-                        add4c(cur.q[u] * 4u < cur.fe[u], cur.q[u] * 4u, cur.v[u], cur.fa[u], cur.fe[u]);
-                    if (__ballot(cur.qx * 4u < cur.fex)) {
-                        add4c(cur.qx * 4u < cur.fex, cur.qx * 4u, cur.vx, cur.fax, cur.fex);
-#pragma unroll
-                        for (uint32_t u = 0; u < UR; ++u) {        // runs beyond 320 records (groups from 80 on): loaded here, rare
-                            const uint32_t fa = cur.fa[u], fe = cur.fe[u];
-                            for (uint32_t q = cur.q[u] + 80u; __ballot(q * 4u < fe); q += 64u)
-                                { uint2 wq = make_uint2(0u, 0u); if (q * 4u < fe) wq = *reinterpret_cast<const uint2 *>(cur.src[u] + (size_t)q * 4u); add4c(q * 4u < fe, q * 4u, wq, fa, fe); }
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (uint32_t u = 0; u < UR; ++u) {
-                        uint32_t q = cur.q[u];
-                        uint2 w = cur.v[u], w2 = cur.v2[u];
-                        const uint32_t fa = cur.fa[u], fe = cur.fe[u];
-                        while (__ballot(q * 4u < fe)) {
-                            add4c(q * 4u < fe, q * 4u, w, fa, fe);
-                            q += 64u;
-                            w = w2;
-                            if ((q + 64u) * 4u < fe) w2 = *reinterpret_cast<const uint2 *>(cur.src[u] + (size_t)(q + 64u) * 4u);   // (runs beyond 512 records: further groups, loaded here)
-                        }
-                    }
-                }
-                AP(4)
-            }
-        }
-        if (MODE == 1 && qn > QW && lane == 0u) qovf_s[par] = 1u;      // (a wave found more first adds than its queue holds: this region is looked at piece by piece)
-        __syncthreads();
-        AP(5)
-        if (exact || !ovf_s) break;
-        __syncthreads();                                          // (everybody has seen the flag)
-        if (threadIdx.x == 0) ovf_s = 0u;
-        }
-        if (MODE != 0 && !skip && fin.big_off) {                  // the long clusters' updates of this region (bucketed by region: k_bigrec_*), exact
-            const uint64_t lo = fin.big_off[region], hi = fin.big_off[region + 1u];
-            for (uint64_t i = lo + threadIdx.x; i < hi; i += APPLY_WG) {
-                const uint64_t r = fin.bigrecs[i];
-                add_exact((uint32_t)r & ((1u << REGION_SHIFT) - 1u), (uint32_t)(r >> CELL_BITS));
-            }
-            __syncthreads();
-        }
-        // the next region's index entries go out now and land while this region is written
-        uint32_t na = 0, ne = 0;
-        if (more) index_of(next, nrow0, nrow1 - nrow0, 0u, na, ne);
-        if (MODE != 0) {
-            if (!skip) {
-                const uint32_t len = ri.w & 0x7FFFFFFFu;
-                clean = false;
-                const bool has_big = fin.big_off && fin.big_off[region + 1u] != fin.big_off[region];
-                if (MODE == 1 && ri.z <= FIN_SEGS && fin.n_refs >= 16u && !exact && !has_big && qovf_s[par] == 0u) {
-                    // the walk over the queued cells: final value of the cell (a byte read), the cell zeroed (a byte store: the LDS copy is left all zero),
-                    // its row segment by one multiplication, two LDS adds -- about 30 instructions per 64 cells against 640 per wave for the look at all pieces
-                    const uint16_t *myq = cell_q + wave * QW;
-                    uint8_t *regb = reinterpret_cast<uint8_t *>(reg4);
-                    const float invf = 1.0f / (float)fin.n_refs;
-                    for (uint32_t i0 = 0; i0 < qn; i0 += 64u) {
-                        const uint32_t i = i0 + lane;
-                        if (i < qn) {
-                            const uint32_t o = myq[i], val = regb[o];
-                            regb[o] = 0;
-                            const uint32_t x0 = ri.y + o;
-                            uint32_t seg = (uint32_t)((float)x0 * invf);
-                            if (seg * fin.n_refs > x0) --seg; else if ((seg + 1u) * fin.n_refs <= x0) ++seg;
-                            if (val) { atomicMax(&seg_acc[seg], val); atomicAdd(&seg_acc[ri.z + seg], 1u); }
-                        }
-                    }
-                    __syncthreads();
-                    fin_region_store(seg_acc, fin, region, (uint64_t)ri.x, ri.y, ri.z, len);
-                    clean = true;
-                }
-                else if (MODE == 1 && ri.z <= FIN_SEGS && fin.n_refs >= 16u) {
-                    fin_region_rows(reg4, seg_acc, fin, region, (uint64_t)ri.x, ri.y, ri.z, len); clean = true;
-                }
-                else fin_region<MODE>(reg4, fin, region, (uint64_t)ri.x, ri.y, ri.z, len);
-            }
-        } else {
-        const size_t reg_base = (size_t)region << REGION_SHIFT;  // regions start inside the table
-        uint4 *dst = reinterpret_cast<uint4 *>(sim + reg_base);
-        const size_t left16 = (sim_bytes - reg_base) / 16u;      // sim_bytes is a multiple of 16
-        constexpr uint32_t NST = RW / 4 / APPLY_WG;
-        static_assert(RW / 4 % APPLY_WG == 0, "whole rounds of 16-byte stores");
-        if (left16 >= RW / 4) {
-            // the thread's eight 16-byte pieces: read together, then stored together (one after the other every piece waited for its LDS
-            // read; named registers, not an array: the array went to scratch memory)
-            static_assert(NST == 8, "eight 16-byte stores per thread below");
-            uint4 *rp = reg4 + threadIdx.x, *dp = dst + threadIdx.x;
-#define LIME_RD(J) const uint4 o##J = rp[J * APPLY_WG];
-            LIME_RD(0) LIME_RD(1) LIME_RD(2) LIME_RD(3) LIME_RD(4) LIME_RD(5) LIME_RD(6) LIME_RD(7)
-#undef LIME_RD
-            // (non-temporal: the table is written once and not read again by the pass -- configs[2] 0.98 -> 0.91 ms, the text workload 83 -> 64 us,
-            // configs[4]'s shape 2.06 -> 1.93 ms against plain stores, ABAB in one run)
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define LIME_ST(J) { const u32x4 x = {o##J.x, o##J.y, o##J.z, o##J.w}; __builtin_nontemporal_store(x, reinterpret_cast<u32x4 *>(dp + J * APPLY_WG)); }
-            LIME_ST(0) LIME_ST(1) LIME_ST(2) LIME_ST(3) LIME_ST(4) LIME_ST(5) LIME_ST(6) LIME_ST(7)
-#undef LIME_ST
-        } else {                                                  // the table's last region, cut short (it is its workgroup's last one)
-            for (uint32_t i = threadIdx.x; i < left16; i += APPLY_WG) dst[i] = reg4[i];
-        }
-        }
-        AP(6)
-        if (!more) break;
-        __syncthreads();                                          // (the region's LDS copy has been read: it may be cleared)
-        ri = nri; par ^= 1u;
-        AP(7)
-        region = next; row0 = nrow0; n_rows = nrow1 - nrow0; a = na; e = ne;
-    }
-    AP_END
-}
-
-// k_apply: one workgroup builds one 64 KB region of the table in LDS -- zero, add the region's records (exact
-// modulo 256 per byte cell: an LDS compare-and-swap on the containing word), write it out once with 16-byte
-// stores.  Two workgroups fit a CU, so one region's write-out overlaps the next one's accumulation.  The table
-// needs no clearing beforehand: every byte of it is written here.  Record: offset in its bin | t << bin_shift.
-__global__ __launch_bounds__(APPLY_WG) void k_apply(uint8_t *sim, size_t sim_bytes, const uint32_t *recs, const uint64_t *regbase,
-                                                    uint32_t bin_shift)
-{
-    constexpr uint32_t RW = (1u << REGION_SHIFT) / 4u;           // words per region
-    __shared__ uint4 reg4[RW / 4];
-    uint32_t *reg = reinterpret_cast<uint32_t *>(reg4);
-    const uint32_t region = blockIdx.x;
-    const size_t reg_base = (size_t)region << REGION_SHIFT;      // grid = regions that start inside the table
-    for (uint32_t i = threadIdx.x; i < RW / 4; i += APPLY_WG) reg4[i] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-    const uint64_t lo = regbase[region], hi = regbase[region + 1];
-    const uint32_t rmask = (1u << REGION_SHIFT) - 1u;
-    constexpr uint32_t U = 4;
-    for (uint64_t i0 = lo; i0 < hi; i0 += (uint64_t)APPLY_WG * U) {
-        uint32_t r[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; ++u) {
-            const uint64_t i = i0 + (uint64_t)APPLY_WG * u + threadIdx.x;
-            r[u] = i < hi ? recs[i] : 0u;                        // t == 0: no record
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < U; ++u) {
-            const uint32_t t = r[u] >> bin_shift;
-            if (t != 0u) {
-                const uint32_t o = r[u] & rmask, sh = (o & 3u) * 8u;
-                uint32_t *w = &reg[o >> 2];
-                uint32_t seen = *w;
-                for (;;) {
-                    const uint32_t b = ((seen >> sh) + t) & 255u;
-                    const uint32_t old = atomicCAS(w, seen, (seen & ~(255u << sh)) | (b << sh));
-                    if (old == seen) break;
-                    seen = old;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    uint4 *dst = reinterpret_cast<uint4 *>(sim + reg_base);
-    const size_t left = (sim_bytes - reg_base) / 16u;            // sim_bytes is a multiple of 16
-    for (uint32_t i = threadIdx.x; i < RW / 4 && i < left; i += APPLY_WG) dst[i] = reg4[i];     // (non-temporal stores here: no gain, tools/r03_ab2.sh)
-}
-
 // =========================================================================================
 // k_score_list: scores clusters given as (pStart,len) records.  Each wave gathers 64 clusters
 // (each <= SMALL_MAX long) side by side into its LDS, files them under their length class and
@@ -3472,50 +2047,8 @@ __global__ void k_fill_u32(uint32_t *p, size_t n, uint32_t v, size_t pitch)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = v;
 }
 
-// =========================================================================================
-// Owner-partitioned exchange of table updates (several GPUs, large tables): every rank leaves its updates as records
-// grouped by table bin (k_part); the owner of a range of bins receives, from every rank, the slice of records of its
-// bins and builds ITS block of the table alone.  k_regroup: the received slices (source-major, each grouped by bin) into
-// one array grouped by bin -- a workgroup per bin copies the sources' runs one after the other.
-// srcoff[s * (nb + 1) + b]: where source s's records of local bin b start in rx; dstbase[b]: where bin b starts in dst.
-// =========================================================================================
-__global__ __launch_bounds__(256) void k_regroup(const uint32_t *rx, const uint64_t *srcoff, uint32_t n_src, uint32_t nb,
-                                                 const uint64_t *dstbase, uint32_t *dst)
-{
-    const uint32_t b = blockIdx.x;
-    uint64_t at = dstbase[b];
-    for (uint32_t s = 0; s < n_src; ++s) {
-        const uint64_t lo = srcoff[(size_t)s * (nb + 1u) + b], hi = srcoff[(size_t)s * (nb + 1u) + b + 1u];
-        for (uint64_t i = lo + threadIdx.x; i < hi; i += 256u) dst[at + (i - lo)] = rx[i];
-        at += hi - lo;
-    }
-}
-
-// the long clusters' updates of ALL ranks (cell | t << CELL_BITS): the ones that fall into this rank's block are added
-// to it (exact modulo 256 per byte cell, like k_score_big on a whole table)
-__global__ __launch_bounds__(256) void k_apply_bigrecs(const uint64_t *recs, uint64_t n, uint64_t cell_lo, uint64_t cell_hi, uint8_t *block)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * 256u;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += stride) {
-        const uint64_t r = recs[i], cell = r & ((1ull << CELL_BITS) - 1ull);
-        if (cell >= cell_lo && cell < cell_hi) sim_add(block, cell - cell_lo, (uint32_t)(r >> CELL_BITS));
-    }
-}
-
 // ---- launch wrappers (host) ------------------------------------------------------------
-template <typename K> static uint32_t resident_blocks(K kernel, int block)
-{
-    int per_cu = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 1024u;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-    return (uint32_t)per_cu * (uint32_t)prop.multiProcessorCount;
-}
-
 // ID: one per instantiation of k_scan (they share one function type, so K alone would share the static)
-// per-device caches of the launch wrappers (one process may drive several GPUs from several host threads)
-constexpr int MAX_DEV = 64;
-static int cur_device() { int d = 0; (void)hipGetDevice(&d); return d >= 0 && d < MAX_DEV ? d : 0; }
 
 // (probe_shift: only every 2^probe_shift-th chunk is scanned -- the density probe)
 template <int ID, int WG, typename K> static uint32_t scan_grid_of(K kernel, uint32_t n_tiles, uint32_t max_blocks, uint32_t probe_shift = 0)
@@ -3545,7 +2078,6 @@ template <int ID, int WG, typename K> static void launch_scan_kernel(K kernel, c
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(WG), 0, st, b);
 }
 
-static uint32_t apply_tiles_grid(uint32_t n_regions);
 // lime_init: every kernel's code is loaded and the launch wrappers' per-device figures (resident workgroups, LDS attributes) are worked out
 // now, not inside a context's first pass (LiME_paired.sh runs a collection once: the first pass IS the run; on configs[1] the first launches'
 // lazy loading and occupancy queries were 0.2 ms of a 0.25 ms pass)
@@ -3556,12 +2088,11 @@ void launch_preload()
     if (d.load(std::memory_order_relaxed)) return;
     for (int e = 0; e < 2; ++e) for (int b = 0; b < 3; ++b) (void)scan_grid(e, 0, b, 1u << 20, 0, 0);
     (void)scan_grid(0, 1, 0, 1u << 20, 0, 0);
-    (void)apply_tiles_grid(1u << 20);
+    preload_partition(); preload_apply();
     hipFuncAttributes fa;
 #define LIME_PRELOAD(K) (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(K));
     LIME_PRELOAD(k_resolve_open) LIME_PRELOAD(k_rowscan_resolve) LIME_PRELOAD(k_bin_bases) LIME_PRELOAD(k_resolve<1>) LIME_PRELOAD(k_emit) LIME_PRELOAD(k_scan_tiles) LIME_PRELOAD(k_bin_rowscan)
-    LIME_PRELOAD((k_part<PART_WG, BIN_MAX, false>)) LIME_PRELOAD((k_part<PART_WG, BIN_MAX, true>)) LIME_PRELOAD(k_part_lines<false>) LIME_PRELOAD(k_part_lines<true>)
-    LIME_PRELOAD(k_tile_bases) LIME_PRELOAD(k_sort_tiles) LIME_PRELOAD((k_apply_tiles<true, 0>)) LIME_PRELOAD(k_apply) LIME_PRELOAD(k_score_big<0>) LIME_PRELOAD(k_score_big<1>)
+    LIME_PRELOAD(k_score_big<0>) LIME_PRELOAD(k_score_big<1>)
     LIME_PRELOAD(k_choose) LIME_PRELOAD(k_gather_pairs) LIME_PRELOAD((k_score_list<0, 0>)) LIME_PRELOAD((k_score_list<1, 0>))
 #undef LIME_PRELOAD
     (void)hipGetLastError();
@@ -3588,166 +2119,6 @@ void launch_bin_bases(const uint32_t *totals, uint64_t *binbase, uint32_t *tbase
 void launch_bin_rowscan(uint32_t *counts, uint32_t *totals, uint32_t n_bins, uint32_t n_prod, hipStream_t st)
 {
     hipLaunchKernelGGL(k_bin_rowscan, dim3((n_bins + 3u) / 4u), dim3(256), 0, st, counts, totals, n_bins, n_prod);
-}
-
-void launch_part(const ScanArgs &a, uint32_t n_prod, const uint64_t *binbase, uint32_t *out, hipStream_t st, bool p64, bool lines_ok)
-{
-    static std::atomic<bool> attr_set[MAX_DEV];              // the attribute is per device
-    std::atomic<bool> &set = attr_set[cur_device()];
-    if (!set.load(std::memory_order_relaxed)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_part<PART_WG, BIN_MAX, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BIN_MAX * 12u));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_part<PART_WG, BIN_MAX, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BIN_MAX * 16u));
-        set.store(true, std::memory_order_relaxed);
-    }
-    // whole-line writes (k_part_lines) wherever the bins' line buffers fit the LDS next to the stage; LIME_PART_LINES=0: comparison runs
-    static std::atomic<uint32_t> lines_room[MAX_DEV][2];     // dynamic LDS k_part_lines may ask for on this device (0: not asked yet)
-    const size_t lds_lines = part_lines_lds(a.n_bins, p64);
-    const void *kl = p64 ? reinterpret_cast<const void *>(k_part_lines<true>) : reinterpret_cast<const void *>(k_part_lines<false>);
-    if (lines_ok && a.n_bins <= 3u * PART_WG) {
-        std::atomic<uint32_t> &room = lines_room[cur_device()][p64 ? 1 : 0];
-        uint32_t r = room.load(std::memory_order_relaxed);
-        if (!r) {
-            hipFuncAttributes fa;
-            r = 1u;
-            if (hipFuncGetAttributes(&fa, kl) == hipSuccess && fa.sharedSizeBytes < 160u * 1024u) {
-                const uint32_t dyn = 160u * 1024u - (uint32_t)fa.sharedSizeBytes;
-                if (hipFuncSetAttribute(kl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) == hipSuccess) r = dyn;
-            }
-            (void)hipGetLastError();
-            room.store(r, std::memory_order_relaxed);
-        }
-        // two workgroups per CU must fit (the kernel is a chain of short phases: alone on a CU it is slower than k_part -- configs[2], 1193 bins:
-        // 0.72 against 0.48 ms; N = 1e10, 477 bins, two per CU: 3.8 against 4.2 .. 4.7 ms)
-        const size_t stat = 160u * 1024u - (r > 1u ? r : 0u);               // the kernel's static LDS
-        if (lds_lines <= r && 2u * (lds_lines + stat + 512u) <= 160u * 1024u) {
-            if (p64) hipLaunchKernelGGL(k_part_lines<true>, dim3(n_prod), dim3(PART_WG), lds_lines, st, a, binbase, out);
-            else     hipLaunchKernelGGL(k_part_lines<false>, dim3(n_prod), dim3(PART_WG), lds_lines, st, a, binbase, out);
-            return;
-        }
-    }
-    if (p64) hipLaunchKernelGGL((k_part<PART_WG, BIN_MAX, true>), dim3(n_prod), dim3(PART_WG), (size_t)a.n_bins * 16u, st, a, binbase, out);
-    else     hipLaunchKernelGGL((k_part<PART_WG, BIN_MAX, false>), dim3(n_prod), dim3(PART_WG), (size_t)a.n_bins * 12u, st, a, binbase, out);
-}
-
-void launch_part2(const uint32_t *recs, const uint64_t *binbase, uint32_t n_bins, uint32_t bin_shift, uint64_t *regbase,
-                  uint32_t *out, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_part2, dim3(n_bins), dim3(PART_WG), 0, st, recs, binbase, bin_shift, regbase, out);
-}
-
-void launch_apply(uint8_t *sim, size_t sim_bytes, const uint32_t *recs, const uint64_t *regbase, uint32_t bin_shift, hipStream_t st)
-{
-    const uint32_t grid = (uint32_t)((sim_bytes + ((size_t)1 << REGION_SHIFT) - 1) >> REGION_SHIFT);
-    hipLaunchKernelGGL(k_apply, dim3(grid), dim3(APPLY_WG), 0, st, sim, sim_bytes, recs, regbase, bin_shift);
-}
-
-// second level by tiles (k_sort_tiles + k_apply_tiles).  tbase: n_bins + 1 words; idx: (tiles + n_bins) * (f2 + 1) 16-bit entries;
-// out16: PART_TILE 16-bit records per tile row (tiles_bound() rows at most)
-void launch_sort_tiles(const uint32_t *recs, const uint64_t *binbase, uint32_t n_bins, uint32_t bin_shift, uint32_t *tbase, uint16_t *idx, uint16_t *out16,
-                       hipStream_t st, bool big_rows, bool tbase_ready)
-{
-    if (!tbase_ready) hipLaunchKernelGGL(k_tile_bases, dim3(1), dim3(PART_WG), 0, st, binbase, n_bins, tbase);
-    // enough workgroups to fill the device evenly: about 8 per CU (two are resident at a time)
-    const uint32_t per_bin = n_bins >= 2048u ? 1u : (2048u + n_bins - 1u) / n_bins;
-    hipLaunchKernelGGL(k_sort_tiles, dim3(n_bins, per_bin), dim3(PART_WG), 0, st, recs, binbase, bin_shift, tbase, idx, out16, big_rows ? 1u : 0u);
-}
-
-// option apply_group (comparison runs): lanes per run of k_apply_tiles as a power of two, 1 .. 6 (6: a wave per run); 0: by the regions per bin
-static std::atomic<uint32_t> g_apply_group{0};
-void set_apply_group(uint32_t lg) { g_apply_group.store(lg >= 1u && lg <= 6u ? lg : 0u, std::memory_order_relaxed); }
-static uint32_t apply_tiles_grid(uint32_t n_regions)
-{
-    static std::atomic<uint32_t> resident_of[MAX_DEV];           // workgroups that fit the device at once (two per CU: 64 KB of LDS each)
-    std::atomic<uint32_t> &slot = resident_of[cur_device()];
-    uint32_t resident = slot.load(std::memory_order_relaxed);
-    if (!resident) { resident = resident_blocks(k_apply_tiles<false, 0>, APPLY_WG); slot.store(resident, std::memory_order_relaxed); }
-    const uint32_t grid = n_regions < resident ? n_regions : resident;
-    return grid ? grid : 1u;
-}
-
-void launch_apply_tiles_fin(int mode, size_t sim_bytes, uint32_t bin_shift, const uint32_t *tbase, const uint16_t *idx, const uint16_t *out16, bool many_records,
-                            const ApplyFin &fin, hipStream_t st)
-{
-    const uint32_t n_regions = (uint32_t)((sim_bytes + ((size_t)1 << REGION_SHIFT) - 1) >> REGION_SHIFT);
-    const dim3 grid(apply_tiles_grid(n_regions)), wg(APPLY_WG);
-    if (mode == 1) {
-        if (many_records) hipLaunchKernelGGL((k_apply_tiles<true, 1>), grid, wg, 0, st, nullptr, sim_bytes, out16, tbase, idx, bin_shift, n_regions, fin, g_apply_group.load(std::memory_order_relaxed));
-        else              hipLaunchKernelGGL((k_apply_tiles<false, 1>), grid, wg, 0, st, nullptr, sim_bytes, out16, tbase, idx, bin_shift, n_regions, fin, g_apply_group.load(std::memory_order_relaxed));
-    } else {
-        if (many_records) hipLaunchKernelGGL((k_apply_tiles<true, 2>), grid, wg, 0, st, nullptr, sim_bytes, out16, tbase, idx, bin_shift, n_regions, fin, g_apply_group.load(std::memory_order_relaxed));
-        else              hipLaunchKernelGGL((k_apply_tiles<false, 2>), grid, wg, 0, st, nullptr, sim_bytes, out16, tbase, idx, bin_shift, n_regions, fin, g_apply_group.load(std::memory_order_relaxed));
-    }
-}
-
-void launch_apply_by_tiles(uint8_t *sim, size_t sim_bytes, const uint32_t *recs, const uint64_t *binbase, uint32_t n_bins, uint32_t bin_shift,
-                           uint32_t *tbase, uint16_t *idx, uint16_t *out16, bool many_records, hipStream_t st, bool big_rows, bool tbase_ready)
-{
-    launch_sort_tiles(recs, binbase, n_bins, bin_shift, tbase, idx, out16, st, big_rows, tbase_ready);
-    const uint32_t n_regions = (uint32_t)((sim_bytes + ((size_t)1 << REGION_SHIFT) - 1) >> REGION_SHIFT);
-    const uint32_t grid = apply_tiles_grid(n_regions);
-    ApplyFin none; memset(&none, 0, sizeof none);
-    // the variant for many records (a step's groups 64 .. 79 in one pass): N = 1e10 (1.2e9 records) 1.09 -> 0.84 ms, configs[4]'s shape (3.2e8)
-    // 2.43 -> 2.08; the other one where there are fewer: configs[2] (1.2e8) +3 %, configs[3]'s shape +3 %, text +7 % with the first
-    if (many_records) hipLaunchKernelGGL((k_apply_tiles<true, 0>), dim3(grid), dim3(APPLY_WG), 0, st, sim, sim_bytes, out16, tbase, idx, bin_shift, n_regions, none, g_apply_group.load(std::memory_order_relaxed));
-    else hipLaunchKernelGGL((k_apply_tiles<false, 0>), dim3(grid), dim3(APPLY_WG), 0, st, sim, sim_bytes, out16, tbase, idx, bin_shift, n_regions, none, g_apply_group.load(std::memory_order_relaxed));
-}
-
-// the rows of every 64 KB region of the table (k_apply_tiles, modes 1 and 2): first row, offset of the region's first byte in it, row segments,
-// bytes of the region inside the table | (row_off given: none of its rows passed) << 31
-__global__ __launch_bounds__(256) void k_region_rows(uint32_t n_regions, uint32_t n_refs, uint64_t table_bytes, const uint64_t *row_off, uint4 *out)
-{
-    const uint32_t region = blockIdx.x * 256u + threadIdx.x;
-    if (region >= n_regions) return;
-    const uint64_t rb = (uint64_t)region << REGION_SHIFT;
-    const uint32_t len = table_bytes - rb < (1ull << REGION_SHIFT) ? (uint32_t)(table_bytes - rb) : (1u << REGION_SHIFT);
-    const uint64_t r0 = rb / n_refs, r1 = (rb + len - 1u) / n_refs;
-    const uint32_t skip = row_off && row_off[r1 + 1u] == row_off[r0] ? 1u : 0u;
-    out[region] = make_uint4((uint32_t)r0, (uint32_t)(rb - r0 * n_refs), (uint32_t)(r1 - r0) + 1u, len | (skip << 31));
-}
-void launch_region_rows(uint32_t n_regions, uint32_t n_refs, uint64_t table_bytes, const uint64_t *row_off, void *out, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_region_rows, dim3((n_regions + 255u) / 256u), dim3(256), 0, st, n_regions, n_refs, table_bytes, row_off, static_cast<uint4 *>(out));
-}
-
-// the long clusters' update records bucketed by table region (a few, rarely millions): count, prefix, scatter
-__global__ __launch_bounds__(256) void k_bigrec_count(const uint64_t *recs, uint32_t n, uint32_t *cnt)
-{
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u)
-        atomicAdd(&cnt[(uint32_t)((recs[i] & ((1ull << CELL_BITS) - 1ull)) >> REGION_SHIFT)], 1u);
-}
-__global__ __launch_bounds__(256) void k_bigrec_scatter(const uint64_t *recs, uint32_t n, const uint64_t *off, uint32_t *cursor, uint64_t *out)
-{
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-        const uint64_t r = recs[i];
-        const uint32_t reg = (uint32_t)((r & ((1ull << CELL_BITS) - 1ull)) >> REGION_SHIFT);
-        out[off[reg] + atomicAdd(&cursor[reg], 1u)] = r;
-    }
-}
-void launch_bigrec_buckets(const uint64_t *recs, uint32_t n, uint32_t n_regions, uint32_t *cnt, uint32_t *cursor, uint64_t *off, uint64_t *out, hipStream_t st)
-{
-    launch_zero2(cnt, (size_t)n_regions * 4u, nullptr, 0, st);
-    launch_zero2(cursor, (size_t)n_regions * 4u, nullptr, 0, st);
-    const uint32_t grid = n ? ((n + 255u) / 256u < 1024u ? (n + 255u) / 256u : 1024u) : 1u;
-    if (n) hipLaunchKernelGGL(k_bigrec_count, dim3(grid), dim3(256), 0, st, recs, n, cnt);
-    launch_scan_tiles(cnt, off, n_regions, reinterpret_cast<unsigned long long *>(off + n_regions), st);
-    if (n) hipLaunchKernelGGL(k_bigrec_scatter, dim3(grid), dim3(256), 0, st, recs, n, off, cursor, out);
-}
-
-uint64_t tiles_bound(uint64_t n_records, uint32_t n_bins) { return n_records / PART_TILE + n_bins; }
-
-uint32_t part_tile() { return PART_TILE; }
-uint32_t row_stride() { return ROW_STRIDE; }
-
-void launch_regroup(const uint32_t *rx, const uint64_t *srcoff, uint32_t n_src, uint32_t nb, const uint64_t *dstbase, uint32_t *dst, hipStream_t st)
-{
-    if (nb) hipLaunchKernelGGL(k_regroup, dim3(nb), dim3(256), 0, st, rx, srcoff, n_src, nb, dstbase, dst);
-}
-
-void launch_apply_bigrecs(const uint64_t *recs, uint64_t n, uint64_t cell_lo, uint64_t cell_hi, uint8_t *block, hipStream_t st)
-{
-    if (!n) return;
-    const uint64_t want = (n + 255u) / 256u;
-    hipLaunchKernelGGL(k_apply_bigrecs, dim3((uint32_t)(want < 4096u ? want : 4096u)), dim3(256), 0, st, recs, n, cell_lo, cell_hi, block);
 }
 
 void launch_tile(int ebwt, int mode, const ScanArgs &a, uint32_t max_blocks, hipStream_t st)

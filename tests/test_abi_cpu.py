@@ -158,16 +158,16 @@ def test_exec_lint_catches_a_shuffle_under_a_condition(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
-    src = open(os.path.join(ROOT, "lime_amd", "csrc", "lime_kernels.hip")).read()
+    src = open(os.path.join(ROOT, "lime_amd", "csrc", "lime_apply.hip")).read()
     fixed = ("            const uint32_t sa = (uint32_t)__shfl((int)a_, (int)(lx & 63u)), se = (uint32_t)__shfl((int)e_, (int)(lx & 63u));\n"
              "            s.fax = lx < nl_ ? sa : 0u; s.fex = lx < nl_ ? se : 0u;")
     buggy = "            s.fax = lx < nl_ ? (uint32_t)__shfl((int)a_, (int)lx) : 0u; s.fex = lx < nl_ ? (uint32_t)__shfl((int)e_, (int)lx) : 0u;"
     assert src.count(fixed) == 1, "the site the test puts the bug back into has moved: update the test"
-    (tmp_path / "lime_kernels.hip").write_text(src.replace(fixed, buggy))
-    asm = tmp_path / "lime_kernels.s"
+    (tmp_path / "lime_apply.hip").write_text(src.replace(fixed, buggy))
+    asm = tmp_path / "lime_apply.s"
     r = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "--offload-arch=gfx950", "-Wno-unused-function", "-w",
                         "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "lime_amd", "csrc"), "--cuda-device-only", "-S",
-                        "-gline-tables-only", str(tmp_path / "lime_kernels.hip"), "-o", str(asm)], capture_output=True, timeout=600)
+                        "-gline-tables-only", str(tmp_path / "lime_apply.hip"), "-o", str(asm)], capture_output=True, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "exec_lint.py"), str(asm), "--allow", os.path.join(ROOT, "tools", "exec_lint_allow.txt")],
                        capture_output=True, timeout=300)

@@ -14,7 +14,8 @@ import pytest
 from lime_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = os.path.join(ROOT, "lime_amd", "csrc", "lime_kernels.hip")
+# the kernel files: all the scan, scorer, partition and apply code, joined
+KERNELS = [os.path.join(ROOT, "lime_amd", "csrc", f) for f in ("lime_kernels.hip", "lime_partition.hip", "lime_apply.hip")]
 
 
 class Layout(C.Structure):
@@ -163,19 +164,19 @@ def _block_after(src, pos):
 
 
 def test_every_genome_index_passes_the_shared_validity_test():
-    """Every site of lime_kernels.hip that turns a da value into a genome index (`- a.n_reads`) calls genome_ok (lime_device.h) in the same
+    """Every site of the kernel files (KERNELS) that turns a da value into a genome index (`- a.n_reads`) calls genome_ok (lime_device.h) in the same
     block, before anything is stored for it -- a new fast emitter cannot silently skip the test.  The queue / record stores of the scorers
     come only after it."""
-    src = open(KERNELS).read()
+    src = "\n".join(open(f).read() for f in KERNELS)
     src = re.sub(r"//[^\n]*", "", src)
     sites = [m.start() for m in re.finditer(r"-\s*a\.n_reads\b", src)]
     assert len(sites) >= 6, len(sites)                                     # emit, score_len2, score_small3 (two), score_rows3, k_score_big
     for pos in sites:
         blk = _block_after(src, pos)
         line = src.count("\n", 0, pos) + 1
-        assert "genome_ok(" in blk, f"lime_kernels.hip:{line}: a genome index is computed and never passed through genome_ok"
+        assert "genome_ok(" in blk, f"kernel files, joined, line {line}: a genome index is computed and never passed through genome_ok"
         for store in re.finditer(r"q[u]?\.q[rg]\[[^\]]*\]\s*=|put_rec\(", blk):
-            assert "genome_ok(" in blk[:store.end() + 80], f"lime_kernels.hip:{line}: stored before the validity test"
+            assert "genome_ok(" in blk[:store.end() + 80], f"kernel files, joined, line {line}: stored before the validity test"
     # and no scorer packs a genome index into a queue entry by masking alone
     assert not re.search(r"q[u]?\.bad\s*\|=\s*\(uint32_t\)\s*\([^;]*>=\s*a\.n_refs", src), "a validity test written out by hand: use genome_ok"
     dev = open(os.path.join(ROOT, "lime_amd", "csrc", "lime_device.h")).read()

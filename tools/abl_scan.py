@@ -2,8 +2,8 @@
 """tools/abl_scan.py WORKLOAD[,WORKLOAD..] [cuts] -- where the scan's time goes: a library built with -DLIME_ABLATE_BUILD (select it with LIME_LIB) cuts
 k_scan after phase LIME_ABLATE=k (RESULTS INVALID): 1 = loads + staging, 3 = + chunk acceptance, 4 = + cluster lists, 12 = + the rounds of a dense
 window's 2-symbol clusters, 10 = + the other clusters' lengths, 11 = + 2-4-symbol scoring, 8 = everything but the record drains, 0 = everything.
-  make -C lime_amd/csrc EXTRA=-DLIME_ABLATE_BUILD OUT=/tmp/abl ...   (or hipcc by hand into variants/lib_abl.so)
-  LIME_LIB=$PWD/variants/lib_abl.so python3 tools/abl_scan.py text_spread,c3"""
+  make -C lime_amd/csrc -j16 EXTRA=-DLIME_ABLATE_BUILD OUT=$PWD/variants/abl $PWD/variants/abl/liblime_hip.so
+  LIME_LIB=$PWD/variants/abl/liblime_hip.so python3 tools/abl_scan.py text_spread,c3"""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

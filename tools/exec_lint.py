@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/exec_lint.py FILE.s [--allow tools/exec_lint_allow.txt] [--list]
+"""tools/exec_lint.py FILE.s [FILE.s ..] [--allow tools/exec_lint_allow.txt] [--list]
 
 Cross-lane operations under a partial EXEC mask, found in hipcc's assembly output (compile with -gline-tables-only so that the
 instructions carry `.loc` source lines).
@@ -23,6 +23,9 @@ How: per kernel, basic blocks from labels and branches; a forward data flow over
 joins take the longer stack (a loop header inherits the back edge's restrictions).  A cross-lane operation in a block position whose stack is not
 empty is reported as (kernel, source file:line, mnemonic).  v_readlane / v_readfirstlane / v_writelane are NOT reported: they ignore EXEC and
 move the register as it is (the compiler's SGPR spills use them everywhere).
+
+Several files (one per translation unit) give ONE report: each file is parsed on its own -- its `.file` numbers and `.LBB<n>_<m>` labels are
+its own -- and a function keeps the labels of the file it came from; a function defined in two of the files is an error.
 
 The compiler cannot know that a condition is the same for all 64 lanes (a wave's window number, `while (__ballot(..))`), so code under such a
 condition is reported too: the allow list (tools/exec_lint_allow.txt) holds every site that has been LOOKED AT and is meant to run that way --
@@ -203,7 +206,6 @@ def main():
     if "--allow" in sys.argv:
         allow_path = sys.argv[sys.argv.index("--allow") + 1]
         args = [a for a in args if a != allow_path]
-    txt = open(args[0]).read()
     allow, head = [], []
     if allow_path:
         try:
@@ -217,7 +219,12 @@ def main():
                 allow.append((sym, where, int(count), reason))
         except FileNotFoundError:
             pass
-    funcs = parse_functions(txt)
+    funcs = {}
+    for path in args:
+        for sym, items in parse_functions(open(path).read()).items():
+            if sym in funcs:
+                sys.exit(f"{sym}: defined in more than one assembly file")
+            funcs[sym] = items
     sites = defaultdict(int)
     for sym, items in funcs.items():
         for loc, op, depth in lint_function(items):

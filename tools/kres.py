@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
-"""tools/kres.py FILE.s [regex] -- per-kernel resources from the amdhsa metadata of hipcc's assembly output:
-VGPRs, SGPRs, spills, LDS bytes, scratch; waves per SIMD the register count allows."""
+"""tools/kres.py FILE.s [FILE.s ..] [regex [OUT.json]] [--gate] -- per-kernel resources from the amdhsa metadata of hipcc's assembly output
+(one file per translation unit; every leading argument that ends in .s is one): VGPRs, SGPRs, spills, LDS bytes, scratch; waves per
+SIMD the register count allows.  One table, one JSON and one gate result over all the files; a kernel named in two of them is an error."""
 import re, sys, json
-txt = open(sys.argv[1]).read()
+files = [a for a in sys.argv[1:] if a.endswith(".s")]
+sys.argv[1:] = [files[0]] + [a for a in sys.argv[1:] if a not in files]
+txts = [open(f).read() for f in files]
+txt = "\n".join(txts)                     # (the gate's instruction checks below read every file's text)
 pat = re.compile(sys.argv[2]) if len(sys.argv) > 2 else None
-md = txt[txt.index("amdhsa.kernels:"):]
 out = {}
-for blk in re.split(r"\n  - \.agpr_count:", md)[1:]:
+for blk in [b for t in txts for b in re.split(r"\n  - \.agpr_count:", t[t.index("amdhsa.kernels:"):])[1:]]:
     g = lambda k: (re.search(r"\." + k + r":\s+(\S+)", blk) or [None, None])[1]
     name = g("name")
     if pat and not pat.search(name): continue
+    if name in out: sys.exit(f"{name}: in more than one assembly file")
     v = int(g("vgpr_count")); alloc = (v + 7) // 8 * 8
     out[name] = dict(vgpr=v, sgpr=int(g("sgpr_count")), sgpr_spill=int(g("sgpr_spill_count")), vgpr_spill=int(g("vgpr_spill_count")),
                      lds=int(g("group_segment_fixed_size")), scratch=int(g("private_segment_fixed_size")), waves_by_vgpr=min(8, 512 // alloc))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/part_phases.py WORKLOAD[,..] -- where k_part_lines' cycles go: a library built with -DLIME_PART_TIMING (select it with LIME_LIB) sums, over wave 0 of
-every workgroup, the cycles between the kernel's phase marks (PP(i) in lime_kernels.hip):
-  hipcc ... -DLIME_PART_TIMING -shared -o variants/lib_ppt.so ...;  LIME_LIB=$PWD/variants/lib_ppt.so python3 tools/part_phases.py n1e10"""
+every workgroup, the cycles between the kernel's phase marks (PP(i) in lime_amd/csrc/lime_partition.hip; the macros: lime_debug.h):
+  make -C lime_amd/csrc -j16 EXTRA=-DLIME_PART_TIMING OUT=$PWD/variants/ppt $PWD/variants/ppt/liblime_hip.so;  LIME_LIB=$PWD/variants/ppt/liblime_hip.so python3 tools/part_phases.py n1e10"""
 import ctypes
 import os
 import sys
