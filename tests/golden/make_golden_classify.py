@@ -9,6 +9,12 @@ files themselves are rebuilt from them with the oracle's writers, which tests/te
 pins to the reference's ClusterBWT_DA byte for byte), norm, beta, the taxonomy file's bytes, and
 for every (binary, higher, rank) combination the bytes of the classification file the reference
 wrote.  Data only; nothing of the reference's source is stored.
+
+The wide cases (WIDE below) come from the generators of tests/classify_cases.py, at the widths of k_classify: reads of more than 64 and
+more than 256 elements, rows of more than 64 pairs, more than 64 genomes, counts one or two units apart at norm 50 and 100 (on the 0.02
+tolerance in float32), beta 0 with reads whose best sum is below the tolerance.  tests/test_classify_cases_cpu.py states what they must
+cover.  The reference took every shape asked of it; nothing was shrunk.  A file that exists is left alone (the four first cases are never
+rewritten): delete a file to make it again.
 """
 import os
 import subprocess
@@ -21,7 +27,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = os.path.join(ROOT, "oracle", "_ref")
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import oracle_py as O  # noqa: E402
+import classify_cases as CC  # noqa: E402
 
 RANKS = (0, 1, 2, 4)
 
@@ -102,6 +110,30 @@ def run_reference(sims, norm, beta, tax_bytes, n_targ):
     return res
 
 
+WIDE = {
+    "wide_single": lambda: CC.near_tie_tables(2, 200, 130, seed=21),
+    "wide_paired": lambda: CC.near_tie_tables(4, 200, 200, seed=22),
+    "tol50": lambda: CC.tolerance_tables(4, 200, 70, seed=23, norm=50),
+    "tol100_single": lambda: CC.tolerance_tables(2, 200, 70, seed=24, norm=100),
+    "beta0_wide": lambda: CC.beta0_tables(4, 100, 129, seed=25),
+}
+
+
+def save(name, sims, norm, beta, tax, n_targ):
+    path = os.path.join(HERE, f"classify_{name}.npz")
+    if os.path.exists(path):
+        print(name, "exists: left as it is")
+        return
+    ref = run_reference(sims, norm, beta, tax, n_targ)
+    np.savez_compressed(path, sims=np.stack(sims), norm=norm, beta=beta, tax=np.frombuffer(tax, dtype=np.uint8), **ref)
+    kinds = {}
+    for k, v in ref.items():
+        for line in v.tobytes().decode().splitlines()[1:]:
+            kinds.setdefault(k, {}).setdefault(line[0], 0)
+            kinds[k][line[0]] += 1
+    print(name, os.path.getsize(path), "bytes;", {k: kinds[k] for k in list(kinds)[:4]})
+
+
 def main():
     cases = {
         "single": dict(n_files=2, n_reads=300, n_targ=12, seed=1, holes=False, norm=85, beta=0.25),
@@ -113,16 +145,10 @@ def main():
         rng = np.random.default_rng(c["seed"])
         tax = taxonomy(c["n_targ"], rng, c["holes"])
         sims = tables(c["n_files"], c["n_reads"], c["n_targ"], rng, c["norm"])
-        ref = run_reference(sims, c["norm"], c["beta"], tax, c["n_targ"])
-        path = os.path.join(HERE, f"classify_{name}.npz")
-        np.savez_compressed(path, sims=np.stack(sims), norm=c["norm"], beta=c["beta"],
-                            tax=np.frombuffer(tax, dtype=np.uint8), **ref)
-        kinds = {}
-        for k, v in ref.items():
-            for line in v.tobytes().decode().splitlines()[1:]:
-                kinds.setdefault(k, {}).setdefault(line[0], 0)
-                kinds[k][line[0]] += 1
-        print(name, os.path.getsize(path), "bytes;", {k: kinds[k] for k in list(kinds)[:4]})
+        save(name, sims, c["norm"], c["beta"], tax, c["n_targ"])
+    for name, make in WIDE.items():
+        c = make()
+        save(name, c["sims"], c["norm"], c["beta"], c["tax"], c["n_targ"])
 
 
 if __name__ == "__main__":
