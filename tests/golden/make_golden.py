@@ -4,7 +4,7 @@
 Run in the build container only (needs oracle/_ref/, built by `make -C oracle` from the
 sources under /root/reference):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [case ...]        (no case named: all of them)
 
 For every case it writes <case>.npz holding the inputs (lcp, da, ebwt, parameters) and the
 bytes the reference programs produced for them:
@@ -182,17 +182,31 @@ def case_tiny(rng):
     return dict(lcp=lcp, da=da, ebwt=ebwt, n_reads=2, n_refs=2, alpha=16, read_len=18, beta=0.0)
 
 
+def case_long_counts(rng):
+    """tests/long_cases.py count_edges(True): per-cluster occurrence counts of 254 .. 257 and 511 .. 513 (reads: they wrap, :123, :206) and of
+    254, 255, 256, 300 (genomes: they saturate, :96-97, :222-223), per document and per symbol; pairs whose t is 256 and 512 + 3 (:133-144 in
+    unsigned char); IUPAC codes beside saturated counts (:146-177); clusters of 15 .. 18 symbols.  The generator has its own seed."""
+    from tests.long_cases import count_edges
+    lcp, da, ebwt, n_reads, n_refs, _ = count_edges(True)
+    return dict(lcp=lcp, da=da, ebwt=ebwt, n_reads=n_reads, n_refs=n_refs, alpha=16, read_len=250, beta=0.5)
+
+
 CASES = {
     "toy_text": case_toy_text, "iid_wrap": case_iid_wrap, "long_runs": case_long_runs,
     "medium": case_medium, "edges": case_edges, "iupac": case_iupac,
-    "synth_c2": case_synth_c2, "tiny": case_tiny,
+    "synth_c2": case_synth_c2, "tiny": case_tiny, "long_counts": case_long_counts,
 }
 
 
 def main():
     if not os.path.exists(f"{REF}/ClusterLCP"):
         sys.exit("oracle/_ref missing: run `make -C oracle` in the build container first")
+    only = sys.argv[1:]
+    if set(only) - set(CASES):
+        sys.exit(f"unknown case(s) {sorted(set(only) - set(CASES))}: {', '.join(CASES)}")
     for k, (name, fn) in enumerate(CASES.items()):
+        if only and name not in only:
+            continue
         rng = np.random.default_rng(1234 + k)
         c = fn(rng)
         ref = reference_outputs(c["lcp"], c["da"], c["ebwt"], c["n_reads"], c["n_refs"],
