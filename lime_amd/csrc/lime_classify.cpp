@@ -12,7 +12,7 @@
 //      otherwise (HIGHER) the lowest higher rank they share -> H, or A        (:642-690, :168-302)
 // float arithmetic, the 0.02 tolerance and the text/binary difference (text values are the %.5f
 // roundings) are kept as they are.  read_taxonomy, value_tables, decide and write_verdict (lime_classify.h) are shared with
-// the device path (lime_api.cpp: lime_classify_lists_dev), lime_classify_mem runs decide over lists held in memory.
+// the device path (lime_choose.cpp: lime_classify_lists_dev), lime_classify_mem runs decide over lists held in memory.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>

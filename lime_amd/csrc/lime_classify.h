@@ -1,5 +1,5 @@
 // lime_classify.h -- what the read-assignment step's host code (lime_classify.cpp, HIP-free: bin/Classify is built from it
-// with g++ alone) shares with the device path (lime_api.cpp, lime_classify_kernel.hip): the lineage parser, the value
+// with g++ alone) shares with the device path (lime_choose.cpp, lime_classify_kernel.hip): the lineage parser, the value
 // tables, decide() and the classification file's line writer.  Not part of the public ABI (include/lime_hip.h is).
 #pragma once
 #include <stdint.h>

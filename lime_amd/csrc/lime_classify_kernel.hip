@@ -1,5 +1,5 @@
 // lime_classify_kernel.hip -- the read-assignment decision (lime_classify.cpp's decide(); reference: src/Classify.cpp:503-690) on the
-// device, over the clusterChoose lists that lime_choose_lists_dev / lime_fused_choose_lists_dev left in HBM (lime_api.cpp:
+// device, over the clusterChoose lists that lime_choose_lists_dev / lime_fused_choose_lists_dev left in HBM (lime_choose.cpp:
 // lime_classify_lists_dev).  One wave64 per read, grid-stride over the reads; the lanes stride over the read's rows of the 2 or 4
 // lists taken one after the other ("elements": list i, genome g, count k).  Per read, in order, each pass only if the ones before
 // decided nothing:

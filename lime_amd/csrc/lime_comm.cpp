@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "lime_ctx.h"
 #include "lime_hip.h"
 
 // the part of rccl.h this file uses (rccl/rccl.h:40-64, 448-470), declared here so that building the
@@ -190,7 +191,6 @@ extern "C" int lime_comm_combine_counters(lime_comm *c, uint64_t *d_sum_max, voi
 // all ranks return the same error together; the row also carries the rank's buffer capacities, so that every rank knows
 // whether ANY rank has to grow a buffer -- only then a second one-word agreement follows the allocations.  Once the sizes
 // have settled an exchange allocates nothing and synchronises the stream ONCE (the slice sizes have to reach the host).
-int lime_internal_records_peek(lime_ctx *c, lime_records_t *out, const uint32_t **d_bigrec_n, uint32_t *bigrec_cap);   // lime_api.cpp: no synchronisation
 
 namespace {
 template <typename T> int grow_dev(T *&p, size_t &cap, size_t want)
@@ -342,9 +342,7 @@ static int multi_comms(int n_dev, const int *devs, std::vector<ncclComm_t> **out
     return LIME_OK;
 }
 
-int lime_internal_upload(int n_arr, const void *const *src, void *const *dst, const size_t *bytes, hipStream_t st);   // lime_api.cpp: through the pinned staging ring
-
-// all devices of one process: device k ends with block k of the summed tables (internal; lime_api.cpp uses it too)
+// all devices of one process: device k ends with block k of the summed tables (internal; lime_choose.cpp uses it too)
 int lime_internal_reduce_scatter(int n_dev, const int *devs, uint8_t *const *d_sim, uint8_t *const *d_blk, size_t blk)
 {
     int rc = load_rccl(); if (rc) return rc;

@@ -1,5 +1,5 @@
 // lime_index.h -- what the index builder's three parts share: the kernels (lime_index_kernel.hip), the rocPRIM sorts and
-// prefix sums (lime_index_sort.hip, a translation unit of its own) and the host sequencing (lime_api.cpp: lime_build_index_dev).
+// prefix sums (lime_index_sort.hip, a translation unit of its own) and the host sequencing (lime_build.cpp: lime_build_index_dev).
 // Not part of the public ABI (include/lime_hip.h is).
 //
 // Positions: the collection with one terminator after every document has N = n_text + n_docs positions; document k owns

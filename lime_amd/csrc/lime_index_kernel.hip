@@ -1,4 +1,4 @@
-// lime_index_kernel.hip -- the project's own kernels of the index builder (lime_build_index_dev, lime_api.cpp): ebwt / lcp / da of
+// lime_index_kernel.hip -- the project's own kernels of the index builder (lime_build_index_dev, lime_build.cpp): ebwt / lcp / da of
 // reads + genomes by a generalized suffix sort on the device, in the convention of lime_amd/builder.py (every document followed by
 // its own terminator; a terminator sorts below every symbol, two terminators by document id; lcp counts non-terminator symbols).
 //   1  k_idx_check / k_idx_present / k_idx_codes   doc_off is checked, the bytes that occur get dense codes 1 .. sigma (0 = terminator)

@@ -1,5 +1,5 @@
 // lime_kernels.h -- declarations shared by the kernel files (lime_kernels.hip, lime_partition.hip, lime_apply.hip)
-// and the C-ABI implementation (lime_api.cpp).  Not part of the public ABI (include/lime_hip.h is).
+// and the C-ABI implementation (lime_api.cpp and the host files beside it: lime_ctx.h).  Not part of the public ABI (include/lime_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -100,7 +100,7 @@ struct ScanArgs {
     uint32_t *edge;                              // LIME_EDGE_* word of this shard (default: &stats->edge)
     uint32_t no_direct;                          // binned updates: 1 = through the update queue (k_scan<., 0, 1>) even where the scorers could write the records themselves (option no_direct: comparison runs, tests)
     uint32_t dense_min;                          // k_scan: a window with more accepted clusters than this lists its 2-symbol clusters apart (64)
-    uint32_t probe_shift;                        // density probe (lime_api.cpp): only every 2^probe_shift-th chunk of a workgroup's wave count of windows is scanned; 0 = a pass
+    uint32_t probe_shift;                        // density probe (lime_pass.cpp): only every 2^probe_shift-th chunk of a workgroup's wave count of windows is scanned; 0 = a pass
     uint32_t *dyn; uint32_t n_static, static_pct;           // k_scan: rounds of round-robin window chunks before the chunks come from the counter dyn[0] (dyn[1]: workgroups done; both are left at 0); set by the launch wrapper from static_pct
     uint32_t sub_rb, sub_gb;                     // binned, two sub-regions: cell >= 2^32 <=> read > sub_rb or (read == sub_rb and genome >= sub_gb); one sub-region: sub_rb = ~0
     uint32_t *sticky;                            // passes whose record pool overflowed and that lime_get_stats has not settled yet (never cleared by a pass)
@@ -169,7 +169,7 @@ void launch_fill_u32(uint32_t *p, size_t n, uint32_t v, hipStream_t st, uint32_t
 void launch_add_u64(uint64_t *p, size_t n, uint64_t v, hipStream_t st);             // p[i] += v (tests: LIME_P64_TEST_BASE)
 void launch_zero2(void *a, size_t a_bytes, void *b, size_t b_bytes, hipStream_t st);   // a: a multiple of 4 bytes; b: 16-byte aligned, a multiple of 16 bytes
 
-// the read-assignment decision over 2 or 4 lists in HBM (lime_classify_kernel.hip; lime_api.cpp lime_classify_lists_dev)
+// the read-assignment decision over 2 or 4 lists in HBM (lime_classify_kernel.hip; lime_choose.cpp lime_classify_lists_dev)
 struct ClsArgs {
     const uint8_t *row_max[4]; const uint64_t *row_off[4]; const lime_pair_t *pairs[4];
     const float *tabs;                              // [4][2][256]: per list the values of the counts 0..255 and the record tops (0: no record)

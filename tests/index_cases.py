@@ -11,7 +11,7 @@ BOUNDARY_LENGTHS = ((1, -1), (1, 0), (1, 1), (2, -1), (2, 0), (2, 1), (4, -1), (
 
 def width_of(sigma):
     """(bits, k_syms) of lime_build_index_dev for `sigma` distinct bytes: codes 0 (terminator) .. sigma need bits_for(sigma) bits, never
-    fewer than 2; as many codes as fit in 64 bits, at most 32 (lime_api.cpp, lime_build_index_dev:
+    fewer than 2; as many codes as fit in 64 bits, at most 32 (lime_build.cpp, lime_build_index_dev:
     `bits = std::max(2u, bits_for(hw[1])), k_syms = std::min(64u / bits, 32u)`)"""
     bits = max(2, int(sigma).bit_length())
     return bits, min(64 // bits, 32)

@@ -9,7 +9,7 @@ with lcp >= 16 (src/ClusterLCP.cpp:214-227: the run is opened at the position be
 import numpy as np
 
 ALPHA = 16
-HT_BITS = 17                                   # lime_kernels.h: HT_BITS, HT_SIZE, BIG_GRID, SMALL_MAX; lime_kernels.hip: MID_MAX; lime_api.cpp: bigrec_cap
+HT_BITS = 17                                   # lime_kernels.h: HT_BITS, HT_SIZE, BIG_GRID, SMALL_MAX; lime_kernels.hip: MID_MAX; lime_pass.cpp: bigrec_cap
 HT_SIZE = 1 << HT_BITS
 HT_MULT = 2654435761
 BIG_GRID = 32

@@ -91,3 +91,43 @@ def test_reserved_block_serves_the_passes_and_goes_back_with_a_trim():
     assert lime_amd.trim_cache() >= (4 << 30)                         # nothing carved: both reservations go back to the driver
     torch.cuda.synchronize()
     assert torch.cuda.mem_get_info()[0] >= free2 + (3 << 30) - (512 << 20)       # (free2: with the first reservation held and this test's arrays allocated)
+
+
+def test_a_context_survives_a_growth_that_fails():
+    """A grow-only buffer of the ctx that cannot be grown is left empty -- no pointer, no capacity (lime_ctx.h: DevArr) --, so the next, smaller
+    request on the same ctx allocates again instead of handing the kernels what is left of the failed attempt.  The failure is hipMalloc's error
+    return for a record pool no device holds (nothing is launched on it): n = 1e6 symbols x 5e5 records per symbol x 1.35 = 6.75e11 records of
+    4 bytes, twice (pool + binned records) -- 5.4 TB --, while a wave's sub-region stays below ensure_binned's limit of 4e9 records: the scan of
+    245 windows runs 245 .. 256 waves, 6.75e11 / 245 = 2.8e9.  The pass falls back to compare-and-swap and says so; with the default density
+    the same ctx then takes the binned path, and closing it returns everything."""
+    import torch
+    import lime_amd
+    from oracle import oracle_py as O
+    n, nr, ng = 1_000_000, 2000, 64
+    lcp, da, eb = O.synth(29, 0, n, nr, ng, 16, 1)
+    cl, nc, ml = O.detect(lcp, da, nr, 16)
+    exp = O.score(da, eb, cl, nr, ng, threads=8)
+    lime_amd.trim_cache()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    c = lime_amd.Context()
+    try:
+        c.set_option("update_path", "bin")
+        c.set_option("pool_density", "500000")
+        sim, gnc, gml = c.fused(lcp, da, eb, nr, ng, 16)
+        assert (gnc, gml) == (nc, ml) and np.array_equal(sim, exp)
+        s, rc = c.stats()
+        assert rc == 0 and (s.flags & 128) and s.wave_records_max == 0    # LIME_FLAG_CAS_FALLBACK: no record was stored
+        fallbacks = c.host_times()["cas_fallbacks"]
+        assert fallbacks >= 1
+        c.set_option("pool_density", "0.45")
+        sim, gnc, gml = c.fused(lcp, da, eb, nr, ng, 16)
+        assert (gnc, gml) == (nc, ml) and np.array_equal(sim, exp)
+        s, rc = c.stats()
+        assert rc == 0 and s.wave_records_max > 0 and not (s.flags & 128)
+        assert c.host_times()["cas_fallbacks"] == fallbacks
+    finally:
+        c.close()
+    lime_amd.trim_cache()
+    torch.cuda.synchronize()
+    assert torch.cuda.mem_get_info()[0] >= free0 - (512 << 20), (free0, torch.cuda.mem_get_info()[0])
