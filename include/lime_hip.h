@@ -453,7 +453,8 @@ int lime_write_classification(const char *path, const lime_verdict_t *verdicts, 
  * Cost: a radix sort of N 64-bit keys, then one sort per doubling round over the suffixes whose rank is not unique yet (repeats
  * longer than the 64-bit key's symbols: genome repeats; a run of L equal symbols takes log2 L rounds); the LCP step compares
  * sum(lcp) / 8 words of text in the worst case (near-identical genomes), at most N * lcp_cap / 8 with a cap.
- * Out of scope: merging with a prebuilt genome index, several GPUs, collections larger than HBM. */
+ * Reads can be merged into a genome index that was built once: lime_gindex_build / lime_merge_index below.
+ * Out of scope: several GPUs, collections larger than HBM. */
 uint64_t lime_index_size(const uint64_t *doc_off, uint32_t n_docs);
 /* host arrays, staged through HBM like the other host calls */
 int lime_build_index(lime_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, uint8_t term, uint32_t lcp_cap,
@@ -470,6 +471,60 @@ int lime_get_index_info(lime_ctx *ctx, double out[8]);
  * every other byte unchanged, case kept).  *text (at least one byte) and *doc_off[*n_docs + 1] are library-owned (lime_free).
  * Pure host code.  LIME_ERR_IO when the file cannot be read. */
 int lime_fasta_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs);
+
+/* ---- reads merged into a prebuilt genome index (eGap's role when the genome database is indexed once) ---------- *
+ * lime_gindex: the index of the genome collection alone, left in HBM (ctx-owned, opaque; documents 0 .. n_refs - 1): text, doc_off,
+ * sa, lcp (capped at the lcp_cap it was built with), da, ebwt, term: 14 bytes per genome position + 8 per genome.  Any number may live
+ * at once; each is released by lime_gindex_free, or by lime_shutdown of its ctx (not both).  lime_gindex_build[_dev] are
+ * lime_build_index[_dev] run on the genomes alone, keeping the suffix array (same arguments, limits, scratch and errors).
+ *
+ * The file (lime_gindex_save / _load / _probe), little-endian, written under a temporary name and renamed:
+ *   header, 64 bytes:  0 magic "LGIX"   4 u16 version (1)   6 u8 term   7 u8 0   8 u32 n_docs   12 u32 lcp_cap   16 u64 n_text
+ *                     24 u64 doc_off bytes = (n_docs + 1) * 8   32 u64 sa bytes   40 u64 lcp bytes   48 u64 da bytes (each N * 4,
+ *                     N = n_text + n_docs)   56 u32 text bytes = n_text   60 u32 ebwt bytes = N
+ *   body: the sections doc_off, sa, lcp, da, text, ebwt in this order, each padded with zeros to a multiple of 16 bytes; the file
+ *         ends with the last section's padding.
+ * load and probe check the magic, the version, every section size against n_docs and n_text, N <= 2^32 - 1 and the file's length;
+ * load also checks doc_off by lime_build_index's rules before anything is indexed with it.  A file that is too short or cannot be
+ * read: LIME_ERR_IO; one that is inconsistent: LIME_ERR_ARG; nothing stays allocated.  sa is NOT verified to be the sorted permutation
+ * (the file is trusted as a .da file is): the merge clamps every value it indexes with, so a damaged file gives wrong output, no fault. */
+typedef struct lime_gindex lime_gindex;
+int lime_gindex_build(lime_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, uint8_t term, uint32_t lcp_cap,
+                      lime_gindex **out);
+int lime_gindex_build_dev(lime_ctx *ctx, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
+                          uint8_t term, uint32_t lcp_cap, void *stream, lime_gindex **out);
+int lime_gindex_save(const lime_gindex *gi, const char *path);
+int lime_gindex_load(lime_ctx *ctx, const char *path, lime_gindex **out);
+int lime_gindex_info(const lime_gindex *gi, uint32_t *n_docs, uint64_t *n_text, uint32_t *lcp_cap, uint8_t *term);
+/* the header and size checks of lime_gindex_load without a device (pure host code) */
+int lime_gindex_probe(const char *path, uint32_t *n_docs, uint64_t *n_text, uint32_t *lcp_cap, uint8_t *term);
+void lime_gindex_free(lime_gindex *gi);
+
+/* ebwt / lcp / da of the collection reads + genomes, bit for bit what lime_build_index[_dev] gives for it with the index's term and
+ * the same lcp_cap, without sorting the genomes again: the reads are sorted alone (lime_build_index_dev's scratch, 52 bytes per READ
+ * position, given back before the next step), every read suffix finds its place among the genome suffixes by a binary search over the
+ * index's suffix array that compares text (a read suffix ends at its terminator, so a probe costs at most readLen / 8 word
+ * compares), and both sides are written to their slots; the lcp of two neighbours of the same side is that side's own.
+ * reads_text / reads_doc_off: the reads alone, as lime_build_index takes a collection (doc_off[0] = 0).  Outputs:
+ * lime_merge_size elements each (reads' positions + the index's); any may be NULL.
+ * lcp_cap must be servable from the index: an index built with cap 0 serves any cap, one built with cap c > 0 serves 1 .. c; anything
+ * else, and more than 2^32 - 1 positions in all, is LIME_ERR_ARG before any launch.
+ * Device memory next to the inputs and outputs, taken like lime_build_index_dev's and given back before the call returns: 17 bytes
+ * per read position (the reads' sa, da, lcp, ebwt and j) and 8 per genome position (c and the words it is scanned from), after the
+ * reads' build has returned its own scratch.  Synchronises `stream`.
+ * Cost: the reads' own sort + about log2(genome positions) probes per read position + one pass over both sides.  Where the reads are most
+ * of the collection this is SLOWER than lime_build_index_dev on reads + genomes (measured: DESIGN.md section 9 f7). */
+uint64_t lime_merge_size(const lime_gindex *gi, const uint64_t *reads_doc_off, uint32_t n_reads);
+int lime_merge_index_dev(lime_ctx *ctx, const uint8_t *d_reads_text, const uint64_t *d_reads_doc_off, uint32_t n_reads,
+                         uint64_t n_reads_text, const lime_gindex *gi, uint32_t lcp_cap, uint8_t *d_ebwt, uint32_t *d_lcp,
+                         uint32_t *d_da, void *stream);
+/* host arrays, staged through HBM like lime_build_index */
+int lime_merge_index(lime_ctx *ctx, const uint8_t *reads_text, const uint64_t *reads_doc_off, uint32_t n_reads,
+                     const lime_gindex *gi, uint32_t lcp_cap, uint8_t *ebwt, uint32_t *lcp, uint32_t *da);
+/* the last merge of the ctx: out[0] doubling rounds of the reads' build, out[1] read suffixes, out[2] runs of read suffixes in the
+ * merged order; with lime_set_timing on, HIP-event ms of out[3] the reads' build, out[4] the rank search, out[5] placement + the lcp
+ * across the sides; out[6], out[7] are 0 */
+int lime_get_merge_info(lime_ctx *ctx, double out[8]);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,17 @@ SYMBOLS = {
     "lime_build_index_dev": (_i, [_vp, _vp, _vp, _u32, _u64, C.c_uint8, _u32, _vp, _vp, _vp, _vp]),
     "lime_get_index_info": (_i, [_vp, C.POINTER(C.c_double)]),
     "lime_fasta_read": (_i, [C.c_char_p, _i, _pp, _pp, C.POINTER(_u32)]),
+    "lime_gindex_build": (_i, [_vp, _vp, _vp, _u32, C.c_uint8, _u32, _pp]),
+    "lime_gindex_build_dev": (_i, [_vp, _vp, _vp, _u32, _u64, C.c_uint8, _u32, _vp, _pp]),
+    "lime_gindex_save": (_i, [_vp, C.c_char_p]),
+    "lime_gindex_load": (_i, [_vp, C.c_char_p, _pp]),
+    "lime_gindex_info": (_i, [_vp, C.POINTER(_u32), _pu64, C.POINTER(_u32), C.POINTER(C.c_uint8)]),
+    "lime_gindex_probe": (_i, [C.c_char_p, C.POINTER(_u32), _pu64, C.POINTER(_u32), C.POINTER(C.c_uint8)]),
+    "lime_gindex_free": (None, [_vp]),
+    "lime_merge_size": (_u64, [_vp, _vp, _u32]),
+    "lime_merge_index_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "lime_merge_index": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "lime_get_merge_info": (_i, [_vp, C.POINTER(C.c_double)]),
 }
 
 _LIB = None

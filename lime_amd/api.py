@@ -42,7 +42,7 @@ class Context:
         h = C.c_void_p()
         check(self.lib.lime_init(-1 if device is None else int(device), C.byref(h)))
         self.h = h
-        self._lists = []                     # Lists of this ctx still alive: lime_shutdown frees them
+        self._lists = []                     # Lists and GenomeIndex objects of this ctx still alive: lime_shutdown frees them
 
     def set_option(self, key, value=""):
         """a tuning / test knob of the ctx by name (lime_set_option; include/lime_hip.h lists them); "" = the library's own choice"""
@@ -322,6 +322,89 @@ class Context:
         return {"rounds": int(v[0]), "unresolved": [int(v[1]), int(v[2]), int(v[3]), int(v[4])], "sort_ms": v[5], "doubling_ms": v[6], "lcp_ms": v[7]}
 
 
+    # ---- reads merged into a prebuilt genome index (include/lime_hip.h: lime_gindex, lime_merge_index) ----
+    def _gindex_of(self, h):
+        import weakref
+        gi = GenomeIndex(self, h)
+        self._lists = [r for r in self._lists if r() is not None] + [weakref.ref(gi)]
+        return gi
+
+    def build_genome_index(self, genomes, term=0, lcp_cap=0):
+        """the genomes alone, sorted once and left in HBM -> GenomeIndex"""
+        text, off = pack_documents([], genomes)
+        h = C.c_void_p()
+        check(self.lib.lime_gindex_build(self.h, text.ctypes.data, off.ctypes.data, len(off) - 1, int(term), int(lcp_cap), C.byref(h)))
+        return self._gindex_of(h)
+
+    def build_genome_index_dev(self, text_t, doc_off_t, n_docs, n_text, term=0, lcp_cap=0, stream=None):
+        """the same from torch device tensors (build_index_dev's arguments)"""
+        h = C.c_void_p()
+        check(self.lib.lime_gindex_build_dev(self.h, _ptr(text_t), _ptr(doc_off_t), int(n_docs), int(n_text), int(term), int(lcp_cap), stream, C.byref(h)))
+        return self._gindex_of(h)
+
+    def load_genome_index(self, path):
+        """a file written by GenomeIndex.save (or BuildIndex --refs) -> GenomeIndex"""
+        h = C.c_void_p()
+        check(self.lib.lime_gindex_load(self.h, os.fsencode(path), C.byref(h)))
+        return self._gindex_of(h)
+
+    def merge_index(self, reads, gi, lcp_cap=0):
+        """build_index(reads, the index's genomes, the index's term, lcp_cap) without sorting the genomes again -> (ebwt, lcp, da)"""
+        text, off = pack_documents(reads, [])
+        n = int(self.lib.lime_merge_size(gi.h, off.ctypes.data, len(off) - 1))
+        ebwt, lcp, da = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        check(self.lib.lime_merge_index(self.h, text.ctypes.data, off.ctypes.data, len(off) - 1, gi.h, int(lcp_cap),
+                                        ebwt.ctypes.data, lcp.ctypes.data, da.ctypes.data))
+        return ebwt[:n], lcp[:n], da[:n]
+
+    def merge_index_dev(self, text_t, doc_off_t, n_reads, n_text, gi, lcp_cap=0, stream=None, out=None):
+        """the same on torch device tensors: the reads' text_t uint8[n_text] and doc_off_t int64[n_reads + 1] -> (ebwt_t uint8[N], lcp_t,
+        da_t int32[N] holding the u32 values), N = read positions + the index's; fresh tensors unless `out` gives the three (any None: not computed)"""
+        import torch
+        n = int(n_text) + int(n_reads) + gi.info()["positions"]
+        if out is None:
+            dev = doc_off_t.device
+            out = (torch.empty(max(n, 1), dtype=torch.uint8, device=dev), torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+                   torch.empty(max(n, 1), dtype=torch.int32, device=dev))
+        ebwt_t, lcp_t, da_t = out
+        check(self.lib.lime_merge_index_dev(self.h, _ptr(text_t), _ptr(doc_off_t), int(n_reads), int(n_text), gi.h, int(lcp_cap),
+                                            _ptr(ebwt_t), _ptr(lcp_t), _ptr(da_t), stream))
+        return tuple(None if t is None else t[:n] for t in out)
+
+    def merge_info(self):
+        """the last merge_index* of this context (lime_get_merge_info); the ms need set_timing(True)"""
+        v = (C.c_double * 8)()
+        check(self.lib.lime_get_merge_info(self.h, v))
+        return {"reads_rounds": int(v[0]), "read_suffixes": int(v[1]), "read_runs": int(v[2]), "reads_build_ms": v[3], "rank_ms": v[4], "place_ms": v[5]}
+
+
+class GenomeIndex:
+    """a genome collection's index resident in HBM (lime_gindex), owned by its Context"""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def info(self):
+        nd, nt, cap, term = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint8()
+        check(self.ctx.lib.lime_gindex_info(self.h, C.byref(nd), C.byref(nt), C.byref(cap), C.byref(term)))
+        return {"n_docs": int(nd.value), "n_text": int(nt.value), "lcp_cap": int(cap.value), "term": int(term.value),
+                "positions": int(nt.value) + int(nd.value)}
+
+    def save(self, path):
+        check(self.ctx.lib.lime_gindex_save(self.h, os.fsencode(path)))
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lime_gindex_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Lists:
     """one collection's clusterChoose result resident in HBM (lime_lists), owned by its Context"""
 
@@ -429,6 +512,33 @@ def build_index(reads, genomes, term=0, lcp_cap=0, ctx=None):
 def build_index_dev(ctx, text_t, doc_off_t, n_docs, n_text, term=0, lcp_cap=0, stream=None, out=None):
     """Context.build_index_dev"""
     return ctx.build_index_dev(text_t, doc_off_t, n_docs, n_text, term, lcp_cap, stream, out)
+
+
+def build_genome_index(ctx, genomes, term=0, lcp_cap=0):
+    """Context.build_genome_index"""
+    return ctx.build_genome_index(genomes, term, lcp_cap)
+
+
+def load_genome_index(ctx, path):
+    """Context.load_genome_index"""
+    return ctx.load_genome_index(path)
+
+
+def merge_index(ctx, reads, gi, lcp_cap=0):
+    """Context.merge_index"""
+    return ctx.merge_index(reads, gi, lcp_cap)
+
+
+def merge_index_dev(ctx, text_t, doc_off_t, n_reads, n_text, gi, lcp_cap=0, stream=None, out=None):
+    """Context.merge_index_dev"""
+    return ctx.merge_index_dev(text_t, doc_off_t, n_reads, n_text, gi, lcp_cap, stream, out)
+
+
+def gindex_probe(path):
+    """the header and size checks of a genome index file without a device -> {n_docs, n_text, lcp_cap, term}"""
+    nd, nt, cap, term = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint8()
+    check(_lib.load().lime_gindex_probe(os.fsencode(path), C.byref(nd), C.byref(nt), C.byref(cap), C.byref(term)))
+    return {"n_docs": int(nd.value), "n_text": int(nt.value), "lcp_cap": int(cap.value), "term": int(term.value)}
 
 
 def index_size(doc_off):

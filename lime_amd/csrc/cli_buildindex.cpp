@@ -4,6 +4,9 @@
 // read) of the collection reads + genomes and prints numReads and numGenomes.  --rc reverse-complements the READS only (the script's
 // `seqtk seq -r`): four runs (reads_1, reads_1 --rc, reads_2, reads_2 --rc) give the four collections of LiME_paired.  --trlcp k stores
 // min(lcp, k) (eGap's option; k >= alpha changes no result downstream).  A thin shell over lime_fasta_read / lime_build_index.
+// The genome database indexed once and every read set merged into it (the script's eGSA once, eGap four times):
+//   BuildIndex --refs refs.fasta outBase [--trlcp k]               writes outBase.gidx (lime_gindex_build / _save), prints numGenomes
+//   BuildIndex reads.fasta --gidx file.gidx outBase [--rc] [--trlcp k]   the one-step form's three files and output (lime_merge_index)
 #include <string.h>
 #include <iostream>
 #include <string>
@@ -19,24 +22,79 @@ static bool write_file(const std::string &path, const void *data, size_t bytes)
     return (fclose(f) == 0) && ok;
 }
 
+// the two forms around a genome index file: refs.fasta -> outBase.gidx, and reads.fasta + file.gidx -> the three files
+static int two_step(CliClock &clk, bool refs_only, const char *gidx, const char *fasta, const std::string &base, int rc_reads, unsigned trlcp)
+{
+    uint8_t *text = nullptr;
+    uint64_t *off = nullptr;
+    uint32_t nd = 0;
+    const int rc = lime_fasta_read(fasta, refs_only ? 0 : rc_reads, &text, &off, &nd);
+    if (rc != LIME_OK) { std::cerr << "Error reading " << fasta << "." << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
+    clk.mark("FASTA file");
+    lime_ctx *ctx = nullptr;
+    if (lime_init(pick_device(), &ctx) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(EXIT_FAILURE); }
+    clk.mark("lime_init (HIP runtime)");
+    lime_gindex *gi = nullptr;
+    if (refs_only) {
+        if (lime_gindex_build(ctx, text, off, nd, 0, trlcp, &gi) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
+        clk.mark("index");
+        if (lime_gindex_save(gi, (base + ".gidx").c_str()) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; return -LIME_ERR_IO; }
+        clk.mark("output file");
+        lime_shutdown(ctx);
+        std::cout << "numGenomes: " << nd << "\nsymbols: " << off[nd] + nd << std::endl;
+        lime_free(text); lime_free(off);
+        return 0;
+    }
+    if (lime_gindex_load(ctx, gidx, &gi) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
+    clk.mark("genome index");
+    uint32_t n_refs = 0;
+    lime_gindex_info(gi, &n_refs, nullptr, nullptr, nullptr);
+    if ((uint64_t)nd + n_refs > 0xFFFFFFFFull) { std::cerr << "Error: too many sequences." << std::endl; return 1; }
+    const uint64_t n = lime_merge_size(gi, off, nd);
+    std::vector<uint8_t> ebwt(n ? n : 1);
+    std::vector<uint32_t> lcp(n ? n : 1), da(n ? n : 1);
+    if (lime_merge_index(ctx, text, off, nd, gi, trlcp, ebwt.data(), lcp.data(), da.data()) != LIME_OK) {
+        std::cerr << "Error: " << lime_last_error() << std::endl; exit(1);
+    }
+    clk.mark("merge");
+    lime_shutdown(ctx);
+    lime_free(text); lime_free(off);
+    if (!write_file(base + ".ebwt", ebwt.data(), n) || !write_file(base + ".lcp", lcp.data(), n * 4) || !write_file(base + ".da", da.data(), n * 4)) {
+        std::cerr << "Error writing " << base << ".ebwt / .lcp / .da." << std::endl;
+        return -LIME_ERR_IO;
+    }
+    clk.mark("output files");
+    std::cout << "numReads: " << nd << "\nnumGenomes: " << n_refs << "\nsymbols: " << n << std::endl;
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     CliClock clk;
     std::vector<const char *> pos;
     int rc_reads = 0;
     unsigned trlcp = 0;
-    bool bad = false;
+    bool bad = false, refs_only = false;
+    const char *gidx = nullptr;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--rc")) rc_reads = 1;
+        else if (!strcmp(argv[i], "--refs")) refs_only = true;
+        else if (!strcmp(argv[i], "--gidx")) { if (i + 1 < argc) gidx = argv[++i]; else bad = true; }
         else if (!strcmp(argv[i], "--trlcp")) { if (i + 1 < argc && sscanf(argv[i + 1], "%u", &trlcp) == 1) ++i; else bad = true; }
         else pos.push_back(argv[i]);
     }
-    if (bad || pos.size() != 3) {
+    if ((refs_only && (gidx || rc_reads)) || pos.size() != ((refs_only || gidx) ? 2u : 3u)) bad = true;
+    if (bad) {
         std::cerr << "Error usage " << argv[0] << " reads.fasta refs.fasta outBase [--rc] [--trlcp k]\n"
                   << "  writes outBase.ebwt, outBase.lcp, outBase.da of the collection reads + genomes; --rc: the reads' reverse complements;\n"
-                  << "  --trlcp k: lcp values truncated at k." << std::endl;
+                  << "  --trlcp k: lcp values truncated at k.\n"
+                  << "or " << argv[0] << " --refs refs.fasta outBase [--trlcp k]\n"
+                  << "  writes outBase.gidx, the index of the genomes alone;\n"
+                  << "or " << argv[0] << " reads.fasta --gidx file.gidx outBase [--rc] [--trlcp k]\n"
+                  << "  writes the three files from the reads and a genome index (--trlcp: at most the index's)." << std::endl;
         exit(1);
     }
+    if (refs_only || gidx) return two_step(clk, refs_only, gidx, pos[0], pos[1], rc_reads, trlcp);
     const std::string base = pos[2];
     uint8_t *text[2] = {nullptr, nullptr};
     uint64_t *off[2] = {nullptr, nullptr};

@@ -1,7 +1,7 @@
 // lime_api.cpp -- the core of the C ABI in include/lime_hip.h: error reporting, lime_init / lime_shutdown, the option table (set_option),
 // timing and statistics (lime_get_stats repeats a pass whose record pool was too small), and the small host-only exports.  The passes themselves
 // are in lime_pass.cpp, the host-pointer entry points in lime_stream.cpp, clusterChoose / Classify in lime_choose.cpp, the index builder in
-// lime_build.cpp, device memory in lime_alloc.cpp.  There is no CPU code path for the computation: every entry point needs a HIP device.
+// lime_build.cpp, the genome index and the merge into it in lime_merge.cpp, device memory in lime_alloc.cpp.  There is no CPU code path for the computation: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -164,6 +164,7 @@ extern "C" void lime_shutdown(lime_ctx *c)
     if (c->h_xoff) (void)hipHostFree(c->h_xoff);
     if (c->ev_xoff) (void)hipEventDestroy(c->ev_xoff);
     for (lime_lists *L : c->lists) delete L;
+    for (lime_gindex *g : c->gidx) delete g;
     delete c;                                            // (the device buffers go with their owners: DevArr / DevWords, lime_ctx.h)
 }
 

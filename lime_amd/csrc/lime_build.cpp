@@ -1,5 +1,6 @@
 // lime_build.cpp -- the index builder's host sequencing: ebwt / lcp / da from the sequences by prefix doubling, the kernels of
-// lime_index_kernel.hip and rocPRIM's sorts and prefix sums (lime_index_sort.hip) in order (lime_build_index_dev), and the host-array front end.
+// lime_index_kernel.hip and rocPRIM's sorts and prefix sums (lime_index_sort.hip) in order (build_index_impl, behind
+// lime_build_index_dev, lime_gindex_build_dev and the reads' side of lime_merge_index_dev), and the host-array front end.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 
@@ -21,20 +22,19 @@ extern "C" int lime_get_index_info(lime_ctx *c, double out[8])
 
 static uint32_t bits_for(uint64_t v) { uint32_t b = 0; while (b < 64u && (v >> b)) ++b; return b; }      // bits that hold 0 .. v
 
-extern "C" int lime_build_index_dev(lime_ctx *c, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
-                                    uint8_t term, uint32_t lcp_cap, uint8_t *d_ebwt, uint32_t *d_lcp, uint32_t *d_da, void *stream)
+int lime_host::build_index_impl(lime_ctx *c, const char *who, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
+                                uint8_t term, uint32_t lcp_cap, uint8_t *d_ebwt, uint32_t *d_lcp, uint32_t *d_da, uint32_t *d_sa, hipStream_t st)
 {
-    if (!c) return fail(LIME_ERR_ARG, "lime_build_index_dev: ctx is NULL");
+    if (!c) return fail(LIME_ERR_ARG, "%s: ctx is NULL", who);
     if (n_text > 0xFFFFFFFFull || n_text + n_docs > 0xFFFFFFFFull)
-        return fail(LIME_ERR_ARG, "lime_build_index_dev: %llu symbols + %u terminators exceed 2^32 - 1 positions (one GPU, 32-bit suffix positions)",
+        return fail(LIME_ERR_ARG, "%s: %llu symbols + %u terminators exceed 2^32 - 1 positions (one GPU, 32-bit suffix positions)", who,
                     (unsigned long long)n_text, n_docs);
-    if (!d_doc_off || (n_text && !d_text)) return fail(LIME_ERR_ARG, "lime_build_index_dev: NULL array");
-    if (!n_docs && n_text) return fail(LIME_ERR_ARG, "lime_build_index_dev: %llu symbols in no document", (unsigned long long)n_text);
-    int rc = check_ctx(c, "lime_build_index_dev"); if (rc) return rc;
+    if (!d_doc_off || (n_text && !d_text)) return fail(LIME_ERR_ARG, "%s: NULL array", who);
+    if (!n_docs && n_text) return fail(LIME_ERR_ARG, "%s: %llu symbols in no document", who, (unsigned long long)n_text);
+    int rc = check_ctx(c, who); if (rc) return rc;
     for (double &v : c->idx_info) v = 0.0;
     const uint32_t n = (uint32_t)(n_text + n_docs);
     if (!n) return LIME_OK;
-    hipStream_t st = (hipStream_t)stream;
 
     // rocPRIM's temporary storage: the largest of the calls below
     size_t tmp_bytes = 0;
@@ -52,7 +52,7 @@ extern "C" int lime_build_index_dev(lime_ctx *c, const uint8_t *d_text, const ui
     const size_t w4 = up((size_t)n * 4), w8 = up((size_t)n * 8), small_bytes = up(256 * 4 + 256 * 2 + 64);
     DevBuf blk;
     if ((rc = blk.alloc(2 * w8 + 9 * w4 + up(tmp_bytes) + small_bytes)))
-        return fail(rc, "lime_build_index_dev: no device memory for %u positions (52 bytes each): %s", n, lime_last_error());
+        return fail(rc, "%s: no device memory for %u positions (52 bytes each): %s", who, n, lime_last_error());
     uint8_t *at = static_cast<uint8_t *>(blk.p);
     auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
     IdxPairs pr;
@@ -78,7 +78,7 @@ extern "C" int lime_build_index_dev(lime_ctx *c, const uint8_t *d_text, const ui
     uint32_t hw[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(hw, words, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (hw[0]) return fail(LIME_ERR_ARG, "lime_build_index_dev: doc_off must start at 0, never decrease and end at n_text (%llu)", (unsigned long long)n_text);
+    if (hw[0]) return fail(LIME_ERR_ARG, "%s: doc_off must start at 0, never decrease and end at n_text (%llu)", who, (unsigned long long)n_text);
     const uint32_t bits = std::max(2u, bits_for(hw[1])), k_syms = std::min(64u / bits, 32u);
     const uint64_t low_mask = (1ull << bits) - 1u;
     const uint32_t nb = std::max(1u, bits_for((uint64_t)n - 1u));
@@ -105,11 +105,11 @@ extern "C" int lime_build_index_dev(lime_ctx *c, const uint8_t *d_text, const ui
         HIP_TRY(hipMemcpyAsync(&lastw[1], t2 + (m - 1), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const uint32_t left = lastw[0] + lastw[1];
-        if (left > m) return fail(LIME_ERR_HIP, "lime_build_index_dev: internal error (%u of %u suffixes left)", left, m);
+        if (left > m) return fail(LIME_ERR_HIP, "%s: internal error (%u of %u suffixes left)", who, left, m);
         if (rounds < 4) c->idx_info[1 + rounds] = (double)left;
         if (c->timing && rounds == 0) HIP_TRY(hipEventRecord(ev[1], st));
         if (!left) break;
-        if (++rounds > 64) return fail(LIME_ERR_HIP, "lime_build_index_dev: internal error (no end of the doubling rounds)");
+        if (++rounds > 64) return fail(LIME_ERR_HIP, "%s: internal error (no end of the doubling rounds)", who);
         uint32_t *out_slot = slots[slot == slots[0] ? 1 : 0];
         idx_launch_compact(pr.vals[pr.cur], slot, t1, t2, m, pr.vals[pr.cur ^ 1], out_slot, st);
         pr.cur ^= 1; slot = out_slot; m = left; mask = 0;
@@ -122,12 +122,19 @@ extern "C" int lime_build_index_dev(lime_ctx *c, const uint8_t *d_text, const ui
     if (c->timing) HIP_TRY(hipEventRecord(ev[2], st));
     if (d_da || d_ebwt) idx_launch_gather(tx, sa, term, d_da, d_ebwt, st);
     if (d_lcp) idx_launch_lcp(tx, sa, rank, lcp_cap, d_lcp, st);
+    if (d_sa) HIP_TRY(hipMemcpyAsync(d_sa, sa, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipGetLastError());
     if (c->timing) HIP_TRY(hipEventRecord(ev[3], st));
     HIP_TRY(hipStreamSynchronize(st));                                   // (the scratch goes back when this returns)
     if (c->timing)
         for (int k = 0; k < 3; ++k) { float ms = 0.0f; if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) c->idx_info[5 + k] = ms; }
     return LIME_OK;
+}
+
+extern "C" int lime_build_index_dev(lime_ctx *c, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
+                                    uint8_t term, uint32_t lcp_cap, uint8_t *d_ebwt, uint32_t *d_lcp, uint32_t *d_da, void *stream)
+{
+    return build_index_impl(c, "lime_build_index_dev", d_text, d_doc_off, n_docs, n_text, term, lcp_cap, d_ebwt, d_lcp, d_da, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int lime_build_index(lime_ctx *c, const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, uint8_t term, uint32_t lcp_cap,

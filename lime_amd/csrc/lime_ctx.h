@@ -1,5 +1,5 @@
 // lime_ctx.h -- what the host-side translation units of the library share (lime_api.cpp, lime_alloc.cpp, lime_pass.cpp, lime_stream.cpp,
-// lime_choose.cpp, lime_build.cpp, lime_comm.cpp): the context and the lists object, error reporting, the device-block helpers and the
+// lime_choose.cpp, lime_build.cpp, lime_merge.cpp, lime_comm.cpp): the context and the lists object, error reporting, the device-block helpers and the
 // declarations of the functions one file defines and another calls.  Internal: include/lime_hip.h is the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -170,7 +170,9 @@ struct __attribute__((visibility("hidden"))) lime_ctx {              // (hidden:
     size_t ev_used = 0;
     double cls_ms = 0.0;                    // the last lime_classify_lists_dev kernel (timing on)
     double idx_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // the last lime_build_index_dev (lime_get_index_info)
+    double mrg_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // the last lime_merge_index_dev (lime_get_merge_info)
     std::vector<lime_lists *> lists;        // clusterChoose results left in HBM that are still alive (lime_lists_free / lime_shutdown)
+    std::vector<lime_gindex *> gidx;        // genome indexes left in HBM that are still alive (lime_gindex_free / lime_shutdown)
 };
 
 // one collection's clusterChoose result in HBM: [row_off u64[n_reads + 1]][row_max u8[n_reads]] in one block, the pairs in another
@@ -182,6 +184,29 @@ struct __attribute__((visibility("hidden"))) lime_lists {
     lime_host::DevArr<lime_pair_t> pairs;
     const uint64_t *row_off() const { return reinterpret_cast<const uint64_t *>(rows.p); }
     const uint8_t *row_max() const { return rows.p + ((size_t)n_reads + 1) * 8; }
+};
+
+// a genome collection's index in HBM (lime_merge.cpp): one block, the sections in the order and at the offsets of the file's body
+// (doc_off, sa, lcp, da, text, ebwt, each 16-byte aligned), so that save and load are one copy each
+struct __attribute__((visibility("hidden"))) lime_gindex {
+    lime_ctx *ctx = nullptr;
+    uint32_t n_docs = 0, lcp_cap = 0; uint8_t term = 0;
+    uint64_t n_text = 0;
+    lime_host::DevArr<uint8_t> blk;
+    uint64_t n() const { return n_text + n_docs; }
+    static uint64_t up16(uint64_t b) { return (b + 15u) & ~(uint64_t)15; }
+    uint64_t off_sa() const { return up16(((uint64_t)n_docs + 1) * 8); }
+    uint64_t off_lcp() const { return off_sa() + up16(n() * 4); }
+    uint64_t off_da() const { return off_lcp() + up16(n() * 4); }
+    uint64_t off_text() const { return off_da() + up16(n() * 4); }
+    uint64_t off_ebwt() const { return off_text() + up16(n_text); }
+    uint64_t body_bytes() const { return off_ebwt() + up16(n()); }
+    uint64_t *doc_off() const { return reinterpret_cast<uint64_t *>(blk.p); }
+    uint32_t *sa() const { return reinterpret_cast<uint32_t *>(blk.p + off_sa()); }
+    uint32_t *lcp() const { return reinterpret_cast<uint32_t *>(blk.p + off_lcp()); }
+    uint32_t *da() const { return reinterpret_cast<uint32_t *>(blk.p + off_da()); }
+    uint8_t *text() const { return blk.p + off_text(); }
+    uint8_t *ebwt() const { return blk.p + off_ebwt(); }
 };
 
 namespace lime_host __attribute__((visibility("hidden"))) {
@@ -223,6 +248,10 @@ int fused_dev_impl(lime_ctx *c, const uint32_t *d_lcp, const uint32_t *d_da, con
 int score_dev_impl(lime_ctx *c, const uint32_t *d_da, const uint8_t *d_ebwt, uint64_t n,
                    const lime_cluster_t *d_clusters, uint64_t n_clusters, uint32_t n_reads,
                    uint32_t n_refs, uint8_t *d_sim, int zero_sim, uint64_t pos_base, hipStream_t st);
+// lime_build.cpp: the index builder behind lime_build_index_dev, lime_gindex_build* and the reads' side of lime_merge_index_dev;
+// d_sa (may be NULL) receives the suffix array (u32[N]); `who` names the public call in error messages
+int build_index_impl(lime_ctx *c, const char *who, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
+                     uint8_t term, uint32_t lcp_cap, uint8_t *d_ebwt, uint32_t *d_lcp, uint32_t *d_da, uint32_t *d_sa, hipStream_t st);
 // lime_stream.cpp
 int score_in_chunks(lime_ctx *c, const uint32_t *da, const uint8_t *ebwt, uint64_t n,
                     const lime_cluster_t *clusters, uint64_t n_clusters, uint32_t n_reads, uint32_t n_refs,

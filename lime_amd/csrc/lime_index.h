@@ -1,5 +1,6 @@
 // lime_index.h -- what the index builder's three parts share: the kernels (lime_index_kernel.hip), the rocPRIM sorts and
-// prefix sums (lime_index_sort.hip, a translation unit of its own) and the host sequencing (lime_build.cpp: lime_build_index_dev).
+// prefix sums (lime_index_sort.hip, a translation unit of its own) and the host sequencing (lime_build.cpp: build_index_impl), and
+// the kernels of the merge into a prebuilt genome index (lime_merge_kernel.hip; host sequencing in lime_merge.cpp).
 // Not part of the public ABI (include/lime_hip.h is).
 //
 // Positions: the collection with one terminator after every document has N = n_text + n_docs positions; document k owns
@@ -46,6 +47,31 @@ void idx_launch_double(const uint32_t *vals, uint32_t m, const uint32_t *rank, u
 void idx_launch_gather(const IdxText &t, const uint32_t *sa, uint8_t term, uint32_t *da, uint8_t *ebwt, hipStream_t st);
 // lcp[rank[p]] for every position p (rank = the inverse of sa), capped at lcp_cap when that is not 0
 void idx_launch_lcp(const IdxText &t, const uint32_t *sa, const uint32_t *rank, uint32_t lcp_cap, uint32_t *lcp, hipStream_t st);
+
+// ---- lime_merge_kernel.hip: read suffixes merged into a prebuilt genome index (lime_merge_index_dev, lime_merge.cpp) ----
+// One side of the merge as its kernels see it: a collection of its own (positions and doc_off count from 0 on each side) with its suffix
+// array and the document of every slot.  Every kernel clamps sa[s] to < n, da[s] to < n_docs and the position into its document, so a
+// genome index loaded from a damaged file gives wrong output and no read outside text / doc_off.
+struct MrgSide {
+    const uint8_t *text;                         // n_text symbols, no terminators
+    const uint64_t *doc_off;                     // [n_docs + 1], checked (k_idx_check / lime_gindex_load) before any of these kernels runs
+    const uint32_t *sa, *da;                     // [n] suffix position and its document, in sorted order
+    const uint8_t *ebwt;                         // [n] (may be NULL when no ebwt is asked for)
+    const uint32_t *lcp;                         // [n] lcp with the slot before on this side (may be NULL when no lcp is asked for)
+    uint64_t n_text;
+    uint32_t n_docs, n;
+};
+// j[i] = number of genome suffixes below read suffix i (i in the reads' sorted order): a lower bound over g.sa by text comparison.
+// Symbols compare as unsigned bytes, a suffix that ends is below one that goes on, and of two that end together the read is below.
+void mrg_launch_rank(const MrgSide &r, const MrgSide &g, uint32_t *j, hipStream_t st);
+// end[j[i]] = i + 1 wherever j[i] != j[i + 1] or i is the last read suffix (end: g.n + 1 words zeroed by the caller; its running maximum
+// is c[k] = number of read suffixes with j <= k); *runs += the number of such i
+void mrg_launch_ends(const uint32_t *j, uint32_t nr, uint32_t ng, uint32_t *end, uint32_t *runs, hipStream_t st);
+// read suffix i goes to slot i + j[i], genome suffix k to slot k + c[k]: da (the genomes' ids + n_reads), ebwt and lcp of the merged
+// order; lcp from the side's own array where the slot before is of the same side, else compared from the two texts; capped at lcp_cap
+// when that is not 0.  Any output may be NULL.
+void mrg_launch_write_reads(const MrgSide &r, const MrgSide &g, const uint32_t *j, uint32_t lcp_cap, uint8_t *ebwt, uint32_t *lcp, uint32_t *da, hipStream_t st);
+void mrg_launch_write_genomes(const MrgSide &r, const MrgSide &g, const uint32_t *c, uint32_t lcp_cap, uint8_t *ebwt, uint32_t *lcp, uint32_t *da, hipStream_t st);
 
 // ---- lime_index_sort.hip: rocPRIM's device primitives.  temp == NULL: only *temp_bytes is set (the size to pass next time) ----
 struct IdxPairs { uint64_t *keys[2]; uint32_t *vals[2]; int cur; };       // double buffers; cur = which holds the data (updated by the sort)
