@@ -42,6 +42,7 @@ extern "C" {
 
 #define LIME_MAX_CLUSTER  65536u /* Tools.h:33 sizeMaxBuf */
 #define LIME_TILE         4096u  /* positions per workgroup tile; shard cuts must be multiples */
+#define LIME_FASTA_BLOCK  4096u  /* input bytes one workgroup pass of the device FASTA parser handles (lime_docs_from_*) */
 
 typedef struct lime_ctx lime_ctx;
 
@@ -525,6 +526,47 @@ int lime_merge_index(lime_ctx *ctx, const uint8_t *reads_text, const uint64_t *r
  * merged order; with lime_set_timing on, HIP-event ms of out[3] the reads' build, out[4] the rank search, out[5] placement + the lcp
  * across the sides; out[6], out[7] are 0 */
 int lime_get_merge_info(lime_ctx *ctx, double out[8]);
+
+/* ---- FASTA to documents on the device, and a whole sample from documents to verdicts ------------------------------ *
+ * lime_docs: a document collection left in HBM (ctx-owned, opaque): text, the symbols back to back (16-byte aligned), and
+ * doc_off[n_docs + 1] -- what lime_build_index_dev / lime_gindex_build_dev / lime_merge_index_dev take.  Any number may live at once; each
+ * is released by lime_docs_free, or by lime_shutdown of its ctx (not both).
+ * The from_* calls parse the raw bytes of a FASTA file with kernels and give exactly lime_fasta_read(path, 0)'s text and doc_off (a file
+ * without a header line: n_docs = 0, doc_off = {0}).  The input is cut into blocks of LIME_FASTA_BLOCK bytes; three passes read it and
+ * one writes the kept bytes: at most 4 bytes of HBM traffic per input byte.  Inputs of 2^32 bytes and more: LIME_ERR_ARG before any
+ * launch.  Device memory next to the handle: the raw bytes (from_fasta / from_bytes; from_bytes_dev reads the caller's, at any alignment)
+ * and 24 bytes per block; all of it is given back before the call returns.  The calls synchronise `stream` (from_fasta and from_bytes
+ * work on the default stream). */
+typedef struct lime_docs lime_docs;
+int  lime_docs_from_fasta(lime_ctx *ctx, const char *path, lime_docs **out);   /* file -> pinned staging -> HBM -> parse; LIME_ERR_IO if unreadable */
+int  lime_docs_from_bytes(lime_ctx *ctx, const uint8_t *bytes, uint64_t n, lime_docs **out);   /* host bytes of a FASTA file */
+int  lime_docs_from_bytes_dev(lime_ctx *ctx, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out);
+/* documents that are parsed already (copied); doc_off is checked on the device by lime_build_index's rules: LIME_ERR_ARG */
+int  lime_docs_from_arrays_dev(lime_ctx *ctx, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
+                               void *stream, lime_docs **out);
+/* every document reversed and complemented, byte for byte lime_fasta_read(path, 1)'s text (its table; doc_off is the same) */
+int  lime_docs_revcomp(lime_ctx *ctx, const lime_docs *in, void *stream, lime_docs **out);
+int  lime_docs_info(const lime_docs *docs, uint32_t *n_docs, uint64_t *n_text);
+int  lime_docs_device(const lime_docs *docs, const uint8_t **d_text, const uint64_t **d_doc_off);
+int  lime_docs_get(const lime_docs *docs, uint8_t *text, uint64_t *doc_off);   /* host copies into the caller's n_text bytes / n_docs + 1 words */
+void lime_docs_free(lime_docs *docs);
+
+/* Preprocessing.sh + LiME_paired.sh for one sample whose reads and genome index are in HBM: n_mates = 1 (single-end) or 2 (paired-end)
+ * read sets of equally many reads; the collections are worked on in the script's order F, F_RC, R, R_RC.  Each one: the reverse complement
+ * (RC strands), lime_merge_index_dev into scratch arrays, lime_fused_choose_lists_dev (n_reads = the set's documents, n_refs = the
+ * index's; no ebwt when use_ebwt == 0); the three arrays and the reverse complement are given back before the next collection starts, only
+ * the lists stay.  Then lime_classify_lists_dev over the 2 or 4 lists, which are freed.  verdicts[n_reads], counts = {C, U, A, H};
+ * stats (may be NULL): 2 * n_mates entries, the collections' scan counters.  lcp_cap: 0 = the index's own; else it must be servable
+ * by the index (lime_merge_index_dev's rule).
+ * Peak device memory next to the read sets and the index: one collection's arrays (9 bytes per position of reads + genomes, 8 without
+ * ebwt) + the merge's scratch (17 bytes per read position + 8 per genome position, after the reads' build has returned its 52 per read
+ * position) + the reverse complement (1 byte per read symbol + 8 per read) + the lists made so far; afterwards the scan's own.
+ * LIME_ERR_ARG, with text in lime_last_error() and before any launch: n_mates other than 1 or 2, read sets with different document
+ * counts, a read set without documents, alpha == 0, a taxonomy of another n_targ than the index's genomes, a cap the index cannot
+ * serve or below alpha.  On any error nothing stays allocated.  Synchronises `stream`. */
+int lime_classify_sample_dev(lime_ctx *ctx, uint32_t n_mates, const lime_docs *const *mates, const lime_gindex *gi,
+                             const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
+                             uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream);
 
 #ifdef __cplusplus
 }

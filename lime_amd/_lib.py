@@ -17,6 +17,7 @@ LIME_OK = 0
 ERR_ARG, ERR_HIP, ERR_NOMEM, ERR_MAXLEN, ERR_HALO, ERR_DOCID, ERR_IO = -1, -2, -3, -4, -5, -6, -7
 MAX_CLUSTER = 65536
 TILE = 4096
+FASTA_BLOCK = 4096
 
 
 class Cluster(C.Structure):
@@ -136,6 +137,16 @@ SYMBOLS = {
     "lime_merge_index_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
     "lime_merge_index": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     "lime_get_merge_info": (_i, [_vp, C.POINTER(C.c_double)]),
+    "lime_docs_from_fasta": (_i, [_vp, C.c_char_p, _pp]),
+    "lime_docs_from_bytes": (_i, [_vp, _vp, _u64, _pp]),
+    "lime_docs_from_bytes_dev": (_i, [_vp, _vp, _u64, _vp, _pp]),
+    "lime_docs_from_arrays_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _pp]),
+    "lime_docs_revcomp": (_i, [_vp, _vp, _vp, _pp]),
+    "lime_docs_info": (_i, [_vp, C.POINTER(_u32), _pu64]),
+    "lime_docs_device": (_i, [_vp, _pp, _pp]),
+    "lime_docs_get": (_i, [_vp, _vp, _vp]),
+    "lime_docs_free": (None, [_vp]),
+    "lime_classify_sample_dev": (_i, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, C.c_float, _i, _i, _u32, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

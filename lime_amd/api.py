@@ -18,6 +18,7 @@ from . import _lib
 from ._lib import Cluster, LimeError, Stats, check, check_cls  # noqa: F401
 
 # lime_verdict_t: one read's classification (type C/U/A/H as a byte, rule 0 = U, 1, 2, 3)
+FASTA_BLOCK = _lib.FASTA_BLOCK          # LIME_FASTA_BLOCK: input bytes one workgroup pass of the device FASTA parser handles
 VERDICT = np.dtype([("taxon", "<u4"), ("sim", "<f4"), ("type", "u1"), ("rule", "u1"), ("pad", "u1", (2,))])
 
 
@@ -377,6 +378,95 @@ class Context:
         check(self.lib.lime_get_merge_info(self.h, v))
         return {"reads_rounds": int(v[0]), "read_suffixes": int(v[1]), "read_runs": int(v[2]), "reads_build_ms": v[3], "rank_ms": v[4], "place_ms": v[5]}
 
+    # ---- FASTA to documents on the device, a sample from documents to verdicts (include/lime_hip.h: lime_docs) ----
+    def _docs_of(self, h):
+        import weakref
+        d = Docs(self, h)
+        self._lists = [r for r in self._lists if r() is not None] + [weakref.ref(d)]
+        return d
+
+    def docs_from_fasta(self, path):
+        """a FASTA file, parsed on the device -> Docs (fasta_read(path)'s records, left in HBM)"""
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_fasta(self.h, os.fsencode(path), C.byref(h)))
+        return self._docs_of(h)
+
+    def docs_from_bytes(self, data):
+        """the bytes of a FASTA file (bytes or a uint8 array) -> Docs"""
+        a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_bytes(self.h, a.ctypes.data if len(a) else None, len(a), C.byref(h)))
+        return self._docs_of(h)
+
+    def docs_from_bytes_dev(self, bytes_t, n=None, stream=None):
+        """the same from a torch uint8 device tensor (a view at any alignment); n: its first n bytes, even beyond 2^32 (refused, nothing is read)"""
+        n = int(bytes_t.numel()) if n is None else int(n)
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_bytes_dev(self.h, _ptr(bytes_t), n, stream, C.byref(h)))
+        return self._docs_of(h)
+
+    def docs_from_arrays_dev(self, text_t, doc_off_t, n_docs, n_text, stream=None):
+        """documents that are parsed already: text_t uint8[n_text], doc_off_t int64[n_docs + 1] on the device (copied) -> Docs"""
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_arrays_dev(self.h, _ptr(text_t), _ptr(doc_off_t), int(n_docs), int(n_text), stream, C.byref(h)))
+        return self._docs_of(h)
+
+    def classify_sample(self, mates, gi, taxonomy, alpha, norm, beta, ebwt=True, binary=True, lcp_cap=0, stream=None):
+        """one sample from its read sets (1 or 2 Docs) and a GenomeIndex to verdicts, everything in HBM (lime_classify_sample_dev)
+        -> (verdicts: numpy VERDICT[n_reads], counts {C, U, A, H} as a list, stats: one Stats per collection F, F_RC[, R, R_RC])"""
+        k = len(mates)
+        hs = (C.c_void_p * max(k, 1))(*[m.h for m in mates])
+        n_reads = mates[0].info()[0] if k and mates[0].h else 0
+        v = np.zeros(max(n_reads, 1), dtype=VERDICT)
+        counts = (C.c_uint64 * 4)()
+        st = (Stats * 4)()
+        check(self.lib.lime_classify_sample_dev(self.h, k, hs, gi.h, taxonomy.h, int(alpha), int(norm) & 0xFFFFFFFF, float(beta), int(bool(ebwt)),
+                                                int(bool(binary)), int(lcp_cap), v.ctypes.data, counts, st, stream))
+        return v[:n_reads], list(counts), [st[i] for i in range(2 * k)]
+
+
+class Docs:
+    """a document collection resident in HBM (lime_docs), owned by its Context"""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def info(self):
+        """-> (n_docs, n_text)"""
+        nd, nt = C.c_uint32(), C.c_uint64()
+        check(self.ctx.lib.lime_docs_info(self.h, C.byref(nd), C.byref(nt)))
+        return int(nd.value), int(nt.value)
+
+    def device(self):
+        """-> (address of text, address of doc_off) in HBM, for the *_dev calls that take documents"""
+        pt, po = C.c_void_p(), C.c_void_p()
+        check(self.ctx.lib.lime_docs_device(self.h, C.byref(pt), C.byref(po)))
+        return pt.value, po.value
+
+    def get(self):
+        """host copies -> (text uint8[n_text], doc_off uint64[n_docs + 1])"""
+        nd, nt = self.info()
+        text, off = np.zeros(max(nt, 1), dtype=np.uint8), np.zeros(nd + 1, dtype=np.uint64)
+        check(self.ctx.lib.lime_docs_get(self.h, text.ctypes.data, off.ctypes.data))
+        return text[:nt], off
+
+    def revcomp(self, stream=None):
+        """every document reversed and complemented (fasta_read(path, rc=True)'s records) -> Docs"""
+        h = C.c_void_p()
+        check(self.ctx.lib.lime_docs_revcomp(self.ctx.h, self.h, stream, C.byref(h)))
+        return self.ctx._docs_of(h)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lime_docs_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class GenomeIndex:
     """a genome collection's index resident in HBM (lime_gindex), owned by its Context"""
@@ -636,6 +726,44 @@ def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, thread
         if own:
             ctx.close()
         tx.close()
+    write_classification(output, v)
+    return counts
+
+
+def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16, beta=0.25, rank=1, trlcp=0, ebwt=True, higher=False, binary=True,
+               ctx=None):
+    """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
+    [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta: the FASTA files are parsed on the device, the
+    genome index is built there (refs) or loaded (gidx), only `output` is written.  -> counts {C, U, A, H}"""
+    reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
+    if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
+        raise ValueError("LiME_fasta takes one or two reads files and either refs or gidx")
+    norm = ((int(read_len) & 0xFF) + 1 - int(alpha)) & 0xFFFFFFFF
+    own = ctx is None
+    ctx = ctx or Context()
+    tx = None
+    try:
+        mates = [ctx.docs_from_fasta(r) for r in reads]
+        if refs is not None:
+            g = ctx.docs_from_fasta(refs)
+            nd, nt = g.info()
+            pt, po = g.device()
+            h = C.c_void_p()
+            check(ctx.lib.lime_gindex_build_dev(ctx.h, pt, po, nd, nt, 0, int(trlcp), None, C.byref(h)))
+            gi = ctx._gindex_of(h)
+            g.close()
+        else:
+            gi = ctx.load_genome_index(gidx)
+        tx = Taxonomy(lineage, rank, higher, gi.info()["n_docs"])
+        v, counts, _ = ctx.classify_sample(mates, gi, tx, alpha, norm, float(np.float32(beta)), ebwt, binary, 0 if refs is not None else trlcp)
+        for d in mates:
+            d.close()
+        gi.close()
+    finally:
+        if own:
+            ctx.close()
+        if tx is not None:
+            tx.close()
     write_classification(output, v)
     return counts
 

@@ -1,5 +1,5 @@
 // lime_ctx.h -- what the host-side translation units of the library share (lime_api.cpp, lime_alloc.cpp, lime_pass.cpp, lime_stream.cpp,
-// lime_choose.cpp, lime_build.cpp, lime_merge.cpp, lime_comm.cpp): the context and the lists object, error reporting, the device-block helpers and the
+// lime_choose.cpp, lime_build.cpp, lime_merge.cpp, lime_docs.cpp, lime_comm.cpp): the context and the lists object, error reporting, the device-block helpers and the
 // declarations of the functions one file defines and another calls.  Internal: include/lime_hip.h is the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -173,6 +173,7 @@ struct __attribute__((visibility("hidden"))) lime_ctx {              // (hidden:
     double mrg_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // the last lime_merge_index_dev (lime_get_merge_info)
     std::vector<lime_lists *> lists;        // clusterChoose results left in HBM that are still alive (lime_lists_free / lime_shutdown)
     std::vector<lime_gindex *> gidx;        // genome indexes left in HBM that are still alive (lime_gindex_free / lime_shutdown)
+    std::vector<lime_docs *> docs;          // document collections left in HBM that are still alive (lime_docs_free / lime_shutdown)
 };
 
 // one collection's clusterChoose result in HBM: [row_off u64[n_reads + 1]][row_max u8[n_reads]] in one block, the pairs in another
@@ -207,6 +208,15 @@ struct __attribute__((visibility("hidden"))) lime_gindex {
     uint32_t *da() const { return reinterpret_cast<uint32_t *>(blk.p + off_da()); }
     uint8_t *text() const { return blk.p + off_text(); }
     uint8_t *ebwt() const { return blk.p + off_ebwt(); }
+};
+
+// a document collection in HBM (lime_docs.cpp): the symbols back to back (16-byte aligned, at least one byte) and doc_off[n_docs + 1]
+struct __attribute__((visibility("hidden"))) lime_docs {
+    lime_ctx *ctx = nullptr;
+    uint32_t n_docs = 0;
+    uint64_t n_text = 0;
+    lime_host::DevArr<uint8_t> text;
+    lime_host::DevArr<uint64_t> doc_off;
 };
 
 namespace lime_host __attribute__((visibility("hidden"))) {

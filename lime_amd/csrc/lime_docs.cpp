@@ -1,0 +1,308 @@
+// lime_docs.cpp -- document collections that stay in HBM (lime_docs: made from the raw bytes of a FASTA file by the kernels of
+// lime_fasta_kernel.hip, or copied from parsed arrays), their reverse complements, and a whole sample from documents to verdicts
+// (lime_classify_sample_dev: per collection the merge into the genome index, the scan and clusterChoose, then Classify over the lists).
+// include/lime_hip.h states the contract.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "lime_index.h"
+#include "lime_ctx.h"
+#include "lime_classify.h"
+
+using namespace lime;
+using namespace lime_host;
+
+// ---- the handle ---------------------------------------------------------------------------------------------------------
+static void docs_release(lime_docs *d)
+{
+    if (!d) return;
+    std::vector<lime_docs *> &v = d->ctx->docs;
+    v.erase(std::remove(v.begin(), v.end(), d), v.end());
+    delete d;
+}
+namespace {
+struct DocsGuard {                                       // releases a handle on an error path
+    lime_docs *d = nullptr;
+    ~DocsGuard() { docs_release(d); }
+    lime_docs *take() { lime_docs *r = d; d = nullptr; return r; }
+};
+struct ListsGuard {                                      // the lists of a sample's collections
+    lime_lists *l[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~ListsGuard() { for (lime_lists *x : l) lime_lists_free(x); }
+};
+struct PinnedPair {                                      // two pinned staging buffers and the events that say when a copy out of them is done
+    void *buf[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~PinnedPair() { for (int k = 0; k < 2; ++k) { if (ev[k]) (void)hipEventDestroy(ev[k]); if (buf[k]) (void)hipHostFree(buf[k]); } }
+};
+struct FileGuard { FILE *f = nullptr; ~FileGuard() { if (f) fclose(f); } };
+constexpr size_t STAGE_BYTES = 8u << 20;
+}
+
+// a handle with room for n_text symbols and n_docs + 1 offsets, nothing in them yet
+static int docs_new(lime_ctx *c, const char *who, uint32_t n_docs, uint64_t n_text, DocsGuard &dg)
+{
+    lime_docs *d = new (std::nothrow) lime_docs();
+    if (!d) return fail(LIME_ERR_NOMEM, "%s: out of host memory", who);
+    d->ctx = c; d->n_docs = n_docs; d->n_text = n_text;
+    c->docs.push_back(d);
+    dg.d = d;
+    int rc;
+    if ((rc = d->text.acquire((size_t)n_text + 16)) || (rc = d->doc_off.acquire((size_t)n_docs + 1)))
+        return fail(rc, "%s: no device memory for %llu symbols in %u documents: %s", who, (unsigned long long)n_text, n_docs, lime_last_error());
+    return LIME_OK;
+}
+
+static int check_input_size(const char *who, uint64_t n)
+{
+    if (n > 0xFFFFFFFFull)
+        return fail(LIME_ERR_ARG, "%s: %llu bytes of input; the parser counts in 32 bits (at most 2^32 - 1 bytes, and the builder indexes no more)", who,
+                    (unsigned long long)n);
+    return LIME_OK;
+}
+
+// d_bytes[0 .. n) -> a handle; the parse's scratch (24 bytes per block of LIME_FASTA_BLOCK input bytes + rocPRIM's) goes back before this returns
+static int parse_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out)
+{
+    const uint32_t nb = (uint32_t)((n + LIME_FASTA_BLOCK - 1) / LIME_FASTA_BLOCK);
+    uint32_t totals[2] = {0, 0};                         // kept bytes, header starts
+    DevBuf scratch;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t words = up(((size_t)nb + 1) * 4);
+    uint32_t *last_lf = nullptr, *cum_lf = nullptr, *cnt = nullptr, *off_keep = nullptr, *off_hdr = nullptr, *first_hdr = nullptr;
+    if (nb) {
+        size_t t_max = 0, t_sum = 0;
+        HIP_TRY(idx_scan_max(nullptr, &t_max, nullptr, nullptr, nb, st));
+        HIP_TRY(idx_scan_sum(nullptr, &t_sum, nullptr, nullptr, (size_t)nb + 1, false, st));
+        size_t tmp_bytes = std::max(t_max, t_sum);
+        int rc = scratch.alloc(6 * words + 256 + up(tmp_bytes));
+        if (rc) return fail(rc, "%s: no device memory for the parse of %llu bytes: %s", who, (unsigned long long)n, lime_last_error());
+        uint8_t *at = static_cast<uint8_t *>(scratch.p);
+        auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
+        last_lf = (uint32_t *)take(words); cum_lf = (uint32_t *)take(words);
+        cnt = (uint32_t *)take(2 * words);               // kept bytes, then header starts: each with a 0 behind the last block's
+        off_keep = (uint32_t *)take(words); off_hdr = (uint32_t *)take(words);
+        first_hdr = (uint32_t *)take(256);
+        void *tmp = take(up(tmp_bytes));
+        uint32_t *cnt_keep = cnt, *cnt_hdr = cnt + words / 4;
+        HIP_TRY(hipMemsetAsync(cnt, 0, 2 * words, st));
+        HIP_TRY(hipMemsetAsync(first_hdr, 0xFF, 4, st));
+        fa_launch_lines(d_bytes, n, nb, last_lf, first_hdr, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(idx_scan_max(tmp, &tmp_bytes, last_lf, cum_lf, nb, st));
+        fa_launch_count(d_bytes, n, nb, cum_lf, first_hdr, cnt_keep, cnt_hdr, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(idx_scan_sum(tmp, &tmp_bytes, cnt_keep, off_keep, (size_t)nb + 1, false, st));
+        HIP_TRY(idx_scan_sum(tmp, &tmp_bytes, cnt_hdr, off_hdr, (size_t)nb + 1, false, st));
+        HIP_TRY(hipMemcpyAsync(&totals[0], off_keep + nb, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&totals[1], off_hdr + nb, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));               // (the totals size the handle)
+    }
+    DocsGuard dg;
+    int rc = docs_new(c, who, totals[1], totals[0], dg); if (rc) return rc;
+    if (nb) {
+        fa_launch_write(d_bytes, n, nb, cum_lf, first_hdr, off_keep, off_hdr, dg.d->text.p, dg.d->doc_off.p, st);
+        HIP_TRY(hipGetLastError());
+    } else {
+        HIP_TRY(hipMemsetAsync(dg.d->doc_off.p, 0, 8, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                   // (the scratch goes back when this returns)
+    *out = dg.take();
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_from_bytes_dev(lime_ctx *c, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out)
+{
+    const char *who = "lime_docs_from_bytes_dev";
+    if (!c || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    *out = nullptr;
+    int rc = check_input_size(who, n); if (rc) return rc;
+    if (n && !d_bytes) return fail(LIME_ERR_ARG, "%s: NULL array", who);
+    if ((rc = check_ctx(c, who))) return rc;
+    return parse_dev(c, who, d_bytes, n, (hipStream_t)stream, out);
+}
+
+extern "C" int lime_docs_from_bytes(lime_ctx *c, const uint8_t *bytes, uint64_t n, lime_docs **out)
+{
+    const char *who = "lime_docs_from_bytes";
+    if (!c || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    *out = nullptr;
+    int rc = check_input_size(who, n); if (rc) return rc;
+    if (n && !bytes) return fail(LIME_ERR_ARG, "%s: NULL array", who);
+    if ((rc = check_ctx(c, who))) return rc;
+    DevBuf raw;
+    if ((rc = raw.upload(bytes, (size_t)n))) return rc;
+    return parse_dev(c, who, (const uint8_t *)raw.p, n, nullptr, out);   // (raw goes back when this returns)
+}
+
+extern "C" int lime_docs_from_fasta(lime_ctx *c, const char *path, lime_docs **out)
+{
+    const char *who = "lime_docs_from_fasta";
+    if (!c || !path || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    *out = nullptr;
+    FileGuard fg; fg.f = fopen(path, "rb");
+    if (!fg.f) return fail(LIME_ERR_IO, "%s: cannot open %s", who, path);
+    if (fseeko(fg.f, 0, SEEK_END) != 0) return fail(LIME_ERR_IO, "%s: cannot seek in %s", who, path);
+    const off_t size = ftello(fg.f);
+    if (size < 0 || fseeko(fg.f, 0, SEEK_SET) != 0) return fail(LIME_ERR_IO, "%s: cannot seek in %s", who, path);
+    int rc = check_input_size(who, (uint64_t)size); if (rc) return rc;
+    if ((rc = check_ctx(c, who))) return rc;
+    DevBuf raw;
+    if ((rc = raw.alloc((size_t)size + 16))) return fail(rc, "%s: no device memory for the %lld bytes of %s: %s", who, (long long)size, path, lime_last_error());
+    // the file through two pinned buffers: one is read into while the other one's copy runs
+    PinnedPair pin;
+    const size_t stage = (size_t)std::min<uint64_t>(STAGE_BYTES, (uint64_t)size);
+    uint64_t n = 0;
+    for (int k = 0; (uint64_t)size > n; k ^= 1) {
+        if (!pin.buf[k]) { HIP_TRY(hipHostMalloc(&pin.buf[k], stage)); HIP_TRY(hipEventCreateWithFlags(&pin.ev[k], hipEventDisableTiming)); }
+        else HIP_TRY(hipEventSynchronize(pin.ev[k]));
+        const size_t want = (size_t)std::min<uint64_t>(stage, (uint64_t)size - n);
+        const size_t got = fread(pin.buf[k], 1, want, fg.f);
+        if (got != want) return fail(LIME_ERR_IO, "%s: cannot read %s (%llu of %lld bytes)", who, path, (unsigned long long)(n + got), (long long)size);
+        HIP_TRY(hipMemcpyAsync((uint8_t *)raw.p + n, pin.buf[k], got, hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipEventRecord(pin.ev[k], nullptr));
+        n += got;
+    }
+    return parse_dev(c, who, (const uint8_t *)raw.p, n, nullptr, out);   // synchronises: the copies are done before the buffers go
+}
+
+extern "C" int lime_docs_from_arrays_dev(lime_ctx *c, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
+                                         void *stream, lime_docs **out)
+{
+    const char *who = "lime_docs_from_arrays_dev";
+    if (!c || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    *out = nullptr;
+    if (n_text > 0xFFFFFFFFull || n_text + n_docs > 0xFFFFFFFFull)
+        return fail(LIME_ERR_ARG, "%s: %llu symbols + %u terminators exceed 2^32 - 1 positions", who, (unsigned long long)n_text, n_docs);
+    if (!n_docs && n_text) return fail(LIME_ERR_ARG, "%s: %llu symbols in no document", who, (unsigned long long)n_text);
+    if (!d_doc_off || (n_text && !d_text)) return fail(LIME_ERR_ARG, "%s: NULL array", who);
+    int rc = check_ctx(c, who); if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf err;
+    if ((rc = err.alloc(16))) return rc;
+    HIP_TRY(hipMemsetAsync(err.p, 0, 4, st));
+    fa_launch_check_off(d_doc_off, n_docs, n_text, (uint32_t *)err.p, st);
+    HIP_TRY(hipGetLastError());
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, err.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(LIME_ERR_ARG, "%s: doc_off must start at 0, never decrease and end at n_text (%llu)", who, (unsigned long long)n_text);
+    DocsGuard dg;
+    if ((rc = docs_new(c, who, n_docs, n_text, dg))) return rc;
+    HIP_TRY(hipMemcpyAsync(dg.d->doc_off.p, d_doc_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToDevice, st));
+    if (n_text) HIP_TRY(hipMemcpyAsync(dg.d->text.p, d_text, (size_t)n_text, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = dg.take();
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_revcomp(lime_ctx *c, const lime_docs *in, void *stream, lime_docs **out)
+{
+    const char *who = "lime_docs_revcomp";
+    if (!c || !in || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    *out = nullptr;
+    if (in->ctx != c) return fail(LIME_ERR_ARG, "%s: the documents belong to another context", who);
+    int rc = check_ctx(c, who); if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DocsGuard dg;
+    if ((rc = docs_new(c, who, in->n_docs, in->n_text, dg))) return rc;
+    HIP_TRY(hipMemcpyAsync(dg.d->doc_off.p, in->doc_off.p, ((size_t)in->n_docs + 1) * 8, hipMemcpyDeviceToDevice, st));
+    fa_launch_revcomp(in->text.p, in->doc_off.p, in->n_docs, in->n_text, dg.d->text.p, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = dg.take();
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_info(const lime_docs *d, uint32_t *n_docs, uint64_t *n_text)
+{
+    if (!d) return fail(LIME_ERR_ARG, "lime_docs_info: the documents are NULL");
+    if (n_docs) *n_docs = d->n_docs;
+    if (n_text) *n_text = d->n_text;
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_device(const lime_docs *d, const uint8_t **d_text, const uint64_t **d_doc_off)
+{
+    if (!d) return fail(LIME_ERR_ARG, "lime_docs_device: the documents are NULL");
+    if (d_text) *d_text = d->text.p;
+    if (d_doc_off) *d_doc_off = d->doc_off.p;
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_get(const lime_docs *d, uint8_t *text, uint64_t *doc_off)
+{
+    const char *who = "lime_docs_get";
+    if (!d) return fail(LIME_ERR_ARG, "%s: the documents are NULL", who);
+    int rc = check_ctx(d->ctx, who); if (rc) return rc;
+    if (text && d->n_text && (rc = d2h_pageable(d->ctx, text, d->text.p, (size_t)d->n_text, nullptr))) return rc;
+    if (doc_off && (rc = d2h_pageable(d->ctx, doc_off, d->doc_off.p, ((size_t)d->n_docs + 1) * 8, nullptr))) return rc;
+    return LIME_OK;
+}
+
+extern "C" void lime_docs_free(lime_docs *d)
+{
+    if (!d) return;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(d->ctx->device);
+    docs_release(d);
+    (void)hipSetDevice(cur);
+}
+
+// ---- a sample: documents -> verdicts -----------------------------------------------------------------------------------------
+extern "C" int lime_classify_sample_dev(lime_ctx *c, uint32_t n_mates, const lime_docs *const *mates, const lime_gindex *gi,
+                                        const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
+                                        uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream)
+{
+    const char *who = "lime_classify_sample_dev";
+    uint64_t local[4];
+    if (!counts) counts = local;
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (!c) return fail(LIME_ERR_ARG, "%s: ctx is NULL", who);
+    if (n_mates != 1 && n_mates != 2) return fail(LIME_ERR_ARG, "%s: n_mates is %u; a sample has 1 (single-end) or 2 (paired-end) read sets", who, n_mates);
+    if (!mates || !gi || !tx || !verdicts) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (gi->ctx != c) return fail(LIME_ERR_ARG, "%s: the genome index belongs to another context", who);
+    for (uint32_t m = 0; m < n_mates; ++m) {
+        if (!mates[m]) return fail(LIME_ERR_ARG, "%s: read set %u is NULL", who, m);
+        if (mates[m]->ctx != c) return fail(LIME_ERR_ARG, "%s: read set %u belongs to another context", who, m);
+        if (!mates[m]->n_docs) return fail(LIME_ERR_ARG, "%s: read set %u holds no documents", who, m);
+        if (mates[m]->n_docs != mates[0]->n_docs)
+            return fail(LIME_ERR_ARG, "%s: the read sets hold different numbers of reads (%u in set 0, %u in set %u)", who, mates[0]->n_docs, mates[m]->n_docs, m);
+    }
+    if (!alpha) return fail(LIME_ERR_ARG, "%s: alpha is 0", who);
+    if (!gi->n_docs || tx->n_targ != gi->n_docs)
+        return fail(LIME_ERR_ARG, "%s: the taxonomy holds %u genomes, the index %u", who, tx->n_targ, gi->n_docs);
+    const uint32_t cap = lcp_cap ? lcp_cap : gi->lcp_cap;                   // 0: the index's own
+    if (gi->lcp_cap && cap > gi->lcp_cap)
+        return fail(LIME_ERR_ARG, "%s: lcp_cap %u cannot be served from an index built with lcp_cap %u (1 .. %u can)", who, cap, gi->lcp_cap, gi->lcp_cap);
+    if (cap && cap < alpha) return fail(LIME_ERR_ARG, "%s: lcp values capped at %u cannot show clusters of alpha = %u", who, cap, alpha);
+    int rc = check_ctx(c, who); if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_reads = mates[0]->n_docs, n_refs = gi->n_docs;
+
+    ListsGuard lg;
+    for (uint32_t k = 0; k < 2 * n_mates; ++k) {                            // the script's order: F, F_RC, R, R_RC
+        const lime_docs *src = mates[k >> 1];
+        DocsGuard rev;                                                      // (the reverse complement goes back at the end of the round)
+        if (k & 1u) {
+            if ((rc = lime_docs_revcomp(c, src, stream, &rev.d))) return rc;
+            src = rev.d;
+        }
+        const uint64_t n = src->n_text + src->n_docs + gi->n();
+        DevBuf ebwt, lcp, da;
+        if ((use_ebwt && (rc = ebwt.alloc((size_t)n))) || (rc = lcp.alloc((size_t)n * 4)) || (rc = da.alloc((size_t)n * 4)))
+            return fail(rc, "%s: no device memory for the arrays of %llu positions: %s", who, (unsigned long long)n, lime_last_error());
+        if ((rc = lime_merge_index_dev(c, src->text.p, src->doc_off.p, src->n_docs, src->n_text, gi, cap, (uint8_t *)ebwt.p, (uint32_t *)lcp.p,
+                                       (uint32_t *)da.p, stream)))
+            return rc;
+        if ((rc = lime_fused_choose_lists_dev(c, (const uint32_t *)lcp.p, (const uint32_t *)da.p, (const uint8_t *)ebwt.p, n, n_reads, n_refs, alpha, norm,
+                                              beta, &lg.l[k], stats ? &stats[k] : nullptr, stream)))
+            return rc;
+        HIP_TRY(hipStreamSynchronize(st));                                  // (the arrays go back when the round ends)
+    }
+    return lime_classify_lists_dev(c, 2 * n_mates, lg.l, n_refs, tx, binary, verdicts, counts, stream);
+}

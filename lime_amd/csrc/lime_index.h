@@ -73,6 +73,22 @@ void mrg_launch_ends(const uint32_t *j, uint32_t nr, uint32_t ng, uint32_t *end,
 void mrg_launch_write_reads(const MrgSide &r, const MrgSide &g, const uint32_t *j, uint32_t lcp_cap, uint8_t *ebwt, uint32_t *lcp, uint32_t *da, hipStream_t st);
 void mrg_launch_write_genomes(const MrgSide &r, const MrgSide &g, const uint32_t *c, uint32_t lcp_cap, uint8_t *ebwt, uint32_t *lcp, uint32_t *da, hipStream_t st);
 
+// ---- lime_fasta_kernel.hip: FASTA bytes to documents, reverse complements (lime_docs.cpp) ----
+// The input b[0 .. n), n < 2^32, in n_blocks = ceil(n / LIME_FASTA_BLOCK) blocks; the rule per byte is at the head of the kernel file.
+// last_lf[k] = 1 + the last line-first position of block k (0: none); *first_hdr = min(itself, the first line-first '>')
+void fa_launch_lines(const uint8_t *b, uint64_t n, uint32_t n_blocks, uint32_t *last_lf, uint32_t *first_hdr, hipStream_t st);
+// cum_lf = the running maximum of last_lf.  cnt_keep[k], cnt_hdr[k] = kept bytes and header starts of block k
+void fa_launch_count(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *cum_lf, const uint32_t *first_hdr, uint32_t *cnt_keep, uint32_t *cnt_hdr,
+                     hipStream_t st);
+// off_keep, off_hdr = the exclusive sums of the counts over n_blocks + 1 entries (a 0 appended: the last entry is the total).
+// text (16-byte aligned, off_keep[n_blocks] bytes) and doc_off[off_hdr[n_blocks] + 1] are written, every byte and entry once
+void fa_launch_write(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *cum_lf, const uint32_t *first_hdr, const uint32_t *off_keep,
+                     const uint32_t *off_hdr, uint8_t *text, uint64_t *doc_off, hipStream_t st);
+// *err = 1 unless doc_off[0] == 0, doc_off never decreases and doc_off[n_docs] == n_text
+void fa_launch_check_off(const uint64_t *doc_off, uint32_t n_docs, uint64_t n_text, uint32_t *err, hipStream_t st);
+// out[doc_off[d] + k] = comp[in[doc_off[d + 1] - 1 - k]]; out 16-byte aligned, doc_off checked
+void fa_launch_revcomp(const uint8_t *in, const uint64_t *doc_off, uint32_t n_docs, uint64_t n_text, uint8_t *out, hipStream_t st);
+
 // ---- lime_index_sort.hip: rocPRIM's device primitives.  temp == NULL: only *temp_bytes is set (the size to pass next time) ----
 struct IdxPairs { uint64_t *keys[2]; uint32_t *vals[2]; int cur; };       // double buffers; cur = which holds the data (updated by the sort)
 hipError_t idx_sort_pairs(void *temp, size_t *temp_bytes, IdxPairs *b, size_t m, unsigned begin_bit, unsigned end_bit, hipStream_t st);
