@@ -42,7 +42,7 @@ extern "C" {
 
 #define LIME_MAX_CLUSTER  65536u /* Tools.h:33 sizeMaxBuf */
 #define LIME_TILE         4096u  /* positions per workgroup tile; shard cuts must be multiples */
-#define LIME_FASTA_BLOCK  4096u  /* input bytes one workgroup pass of the device FASTA parser handles (lime_docs_from_*) */
+#define LIME_FASTA_BLOCK  4096u  /* input bytes one workgroup pass of the device FASTA and FASTQ parsers handles (lime_docs_from_*) */
 
 typedef struct lime_ctx lime_ctx;
 
@@ -472,6 +472,22 @@ int lime_get_index_info(lime_ctx *ctx, double out[8]);
  * every other byte unchanged, case kept).  *text (at least one byte) and *doc_off[*n_docs + 1] are library-owned (lime_free).
  * Pure host code.  LIME_ERR_IO when the file cannot be read. */
 int lime_fasta_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs);
+/* FASTQ, the four-line form (wrapped sequences are refused, not guessed at): line 4k is the '@' header, 4k + 1 the sequence, 4k + 2 the
+ * '+' separator, 4k + 3 the quality string.  Records are found by counting lines, never by looking for '@' (a quality string may begin with
+ * '@' or '+').  A line ends at its LF or at the end of the file; bytes after the last LF are a line, nothing after it is none.  The sequence
+ * line's bytes minus CR are the record's symbols as they are (an empty read is a record); the header, the separator's text and the
+ * quality values are not kept.  An empty file: no record, doc_off = {0}.  rc, ownership and LIME_ERR_IO as lime_fasta_read.
+ * LIME_ERR_ARG, with lime_last_error() = "<who>: line <L>: <reason>", L counted from 1, for the lowest offending line, and of two reasons
+ * on one line the first of:
+ *   "record does not start with '@'"               the first byte of a line 4k is not '@' (an empty line included)
+ *   "separator line does not start with '+'"       the first byte of a line 4k + 2 is not '+'
+ *   "quality length differs from sequence length"  line 4k + 3 has another number of bytes that are neither CR nor LF than line 4k + 1
+ *   "truncated record"                             the number of lines is no multiple of 4; L is the last line
+ * Pure host code, a plain line reader: the oracle of the device parser below. */
+int lime_fastq_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs);
+/* *format = 1 (FASTQ) if the file's first byte is '@', else 0 (FASTA: an empty file and text in front of the first header included).
+ * LIME_ERR_IO when the file cannot be read.  Pure host code. */
+int lime_seq_format(const char *path, int *format);
 
 /* ---- reads merged into a prebuilt genome index (eGap's role when the genome database is indexed once) ---------- *
  * lime_gindex: the index of the genome collection alone, left in HBM (ctx-owned, opaque; documents 0 .. n_refs - 1): text, doc_off,
@@ -541,6 +557,18 @@ typedef struct lime_docs lime_docs;
 int  lime_docs_from_fasta(lime_ctx *ctx, const char *path, lime_docs **out);   /* file -> pinned staging -> HBM -> parse; LIME_ERR_IO if unreadable */
 int  lime_docs_from_bytes(lime_ctx *ctx, const uint8_t *bytes, uint64_t n, lime_docs **out);   /* host bytes of a FASTA file */
 int  lime_docs_from_bytes_dev(lime_ctx *ctx, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out);
+/* The same three for four-line FASTQ: exactly lime_fastq_read(path, 0)'s text and doc_off, and its refusals with the same code, line and
+ * reason (the text starts with the name of the call that was made); on a refusal nothing stays allocated and *out is NULL.  The rule per
+ * byte is at the head of lime_fastq_kernel.hip.  The same blocks, limit (2^32 - 1 bytes, refused before any launch), staging and
+ * synchronisation as above: three passes read the input, one writes the kept bytes (the sequence lines); the offending line comes back with
+ * the reads the call waits for anyway.  Device memory next to the handle: the raw bytes (from_fastq / from_fastq_bytes) and 24 bytes per
+ * block (the blocks' counts of LF, of kept bytes and of kept minus quality bytes, and their prefix sums); all of it is given back before
+ * the call returns. */
+int  lime_docs_from_fastq(lime_ctx *ctx, const char *path, lime_docs **out);
+int  lime_docs_from_fastq_bytes(lime_ctx *ctx, const uint8_t *bytes, uint64_t n, lime_docs **out);
+int  lime_docs_from_fastq_bytes_dev(lime_ctx *ctx, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out);
+/* lime_docs_from_fastq or lime_docs_from_fasta, by lime_seq_format(path): the one place a file's format is decided */
+int  lime_docs_from_file(lime_ctx *ctx, const char *path, lime_docs **out);
 /* documents that are parsed already (copied); doc_off is checked on the device by lime_build_index's rules: LIME_ERR_ARG */
 int  lime_docs_from_arrays_dev(lime_ctx *ctx, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
                                void *stream, lime_docs **out);

@@ -140,6 +140,12 @@ SYMBOLS = {
     "lime_docs_from_fasta": (_i, [_vp, C.c_char_p, _pp]),
     "lime_docs_from_bytes": (_i, [_vp, _vp, _u64, _pp]),
     "lime_docs_from_bytes_dev": (_i, [_vp, _vp, _u64, _vp, _pp]),
+    "lime_fastq_read": (_i, [C.c_char_p, _i, _pp, _pp, C.POINTER(_u32)]),
+    "lime_seq_format": (_i, [C.c_char_p, C.POINTER(_i)]),
+    "lime_docs_from_fastq": (_i, [_vp, C.c_char_p, _pp]),
+    "lime_docs_from_fastq_bytes": (_i, [_vp, _vp, _u64, _pp]),
+    "lime_docs_from_fastq_bytes_dev": (_i, [_vp, _vp, _u64, _vp, _pp]),
+    "lime_docs_from_file": (_i, [_vp, C.c_char_p, _pp]),
     "lime_docs_from_arrays_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _pp]),
     "lime_docs_revcomp": (_i, [_vp, _vp, _vp, _pp]),
     "lime_docs_info": (_i, [_vp, C.POINTER(_u32), _pu64]),

@@ -405,6 +405,32 @@ class Context:
         check(self.lib.lime_docs_from_bytes_dev(self.h, _ptr(bytes_t), n, stream, C.byref(h)))
         return self._docs_of(h)
 
+    def docs_from_fastq(self, path):
+        """a four-line FASTQ file, parsed on the device -> Docs (fastq_read(path)'s records; its refusals as LimeError with the line and reason)"""
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_fastq(self.h, os.fsencode(path), C.byref(h)))
+        return self._docs_of(h)
+
+    def docs_from_fastq_bytes(self, data):
+        """the bytes of a FASTQ file (bytes or a uint8 array) -> Docs"""
+        a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_fastq_bytes(self.h, a.ctypes.data if len(a) else None, len(a), C.byref(h)))
+        return self._docs_of(h)
+
+    def docs_from_fastq_bytes_dev(self, bytes_t, n=None, stream=None):
+        """the same from a torch uint8 device tensor (a view at any alignment); n as for docs_from_bytes_dev"""
+        n = int(bytes_t.numel()) if n is None else int(n)
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_fastq_bytes_dev(self.h, _ptr(bytes_t), n, stream, C.byref(h)))
+        return self._docs_of(h)
+
+    def docs_from_file(self, path):
+        """a FASTA or FASTQ file, by seq_format(path) -> Docs"""
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_file(self.h, os.fsencode(path), C.byref(h)))
+        return self._docs_of(h)
+
     def docs_from_arrays_dev(self, text_t, doc_off_t, n_docs, n_text, stream=None):
         """documents that are parsed already: text_t uint8[n_text], doc_off_t int64[n_docs + 1] on the device (copied) -> Docs"""
         h = C.c_void_p()
@@ -651,6 +677,27 @@ def fasta_read(path, rc=False):
     return [raw[int(off[k]):int(off[k + 1])] for k in range(nd.value)]
 
 
+def fastq_read(path, rc=False):
+    """a four-line FASTQ file's reads -> list of bytes (lime_fastq_read: the sequence lines, CR dropped, case kept; rc: reverse complements).
+    A malformed file: LimeError with `line <L>: <reason>`"""
+    lib = _lib.load()
+    pt, po, nd = C.c_void_p(), C.c_void_p(), C.c_uint32(0)
+    check(lib.lime_fastq_read(os.fsencode(path), int(bool(rc)), C.byref(pt), C.byref(po), C.byref(nd)))
+    try:
+        off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(nd.value + 1,)).copy()
+        raw = C.string_at(pt, int(off[-1]))
+    finally:
+        lib.lime_free(pt); lib.lime_free(po)
+    return [raw[int(off[k]):int(off[k + 1])] for k in range(nd.value)]
+
+
+def seq_format(path):
+    """"fastq" if the file's first byte is '@', else "fasta" (lime_seq_format)"""
+    f = C.c_int(0)
+    check(_lib.load().lime_seq_format(os.fsencode(path), C.byref(f)))
+    return "fastq" if f.value == 1 else "fasta"
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -733,7 +780,8 @@ def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, thread
 def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16, beta=0.25, rank=1, trlcp=0, ebwt=True, higher=False, binary=True,
                ctx=None):
     """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
-    [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta: the FASTA files are parsed on the device, the
+    [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta: the files are parsed on the device (each reads file
+    FASTA or four-line FASTQ, by its first byte; refs FASTA), the
     genome index is built there (refs) or loaded (gidx), only `output` is written.  -> counts {C, U, A, H}"""
     reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
     if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
@@ -743,7 +791,7 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     ctx = ctx or Context()
     tx = None
     try:
-        mates = [ctx.docs_from_fasta(r) for r in reads]
+        mates = [ctx.docs_from_file(r) for r in reads]
         if refs is not None:
             g = ctx.docs_from_fasta(refs)
             nd, nt = g.info()

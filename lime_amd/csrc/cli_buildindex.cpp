@@ -4,6 +4,7 @@
 // read) of the collection reads + genomes and prints numReads and numGenomes.  --rc reverse-complements the READS only (the script's
 // `seqtk seq -r`): four runs (reads_1, reads_1 --rc, reads_2, reads_2 --rc) give the four collections of LiME_paired.  --trlcp k stores
 // min(lcp, k) (eGap's option; k >= alpha changes no result downstream).  A thin shell over lime_fasta_read / lime_build_index.
+// The reads file may be four-line FASTQ instead (first byte '@': lime_seq_format, then lime_fastq_read); refs.fasta is FASTA.
 // The genome database indexed once and every read set merged into it (the script's eGSA once, eGap four times):
 //   BuildIndex --refs refs.fasta outBase [--trlcp k]               writes outBase.gidx (lime_gindex_build / _save), prints numGenomes
 //   BuildIndex reads.fasta --gidx file.gidx outBase [--rc] [--trlcp k]   the one-step form's three files and output (lime_merge_index)
@@ -22,15 +23,32 @@ static bool write_file(const std::string &path, const void *data, size_t bytes)
     return (fclose(f) == 0) && ok;
 }
 
+// the positional reads file: FASTA or four-line FASTQ by its first byte
+static int read_reads(const char *path, int rc_reads, uint8_t **text, uint64_t **off, uint32_t *nd)
+{
+    int format = 0;
+    int rc = lime_seq_format(path, &format);
+    if (rc == LIME_OK) rc = format == 1 ? lime_fastq_read(path, rc_reads, text, off, nd) : lime_fasta_read(path, rc_reads, text, off, nd);
+    if (rc == LIME_OK) return 0;
+    std::cerr << "Error reading " << path << "." << std::endl;
+    if (format == 1 && rc == LIME_ERR_ARG) std::cerr << lime_last_error() << std::endl;
+    return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1;
+}
+
 // the two forms around a genome index file: refs.fasta -> outBase.gidx, and reads.fasta + file.gidx -> the three files
 static int two_step(CliClock &clk, bool refs_only, const char *gidx, const char *fasta, const std::string &base, int rc_reads, unsigned trlcp)
 {
     uint8_t *text = nullptr;
     uint64_t *off = nullptr;
     uint32_t nd = 0;
-    const int rc = lime_fasta_read(fasta, refs_only ? 0 : rc_reads, &text, &off, &nd);
-    if (rc != LIME_OK) { std::cerr << "Error reading " << fasta << "." << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
-    clk.mark("FASTA file");
+    if (refs_only) {
+        const int rc = lime_fasta_read(fasta, 0, &text, &off, &nd);
+        if (rc != LIME_OK) { std::cerr << "Error reading " << fasta << "." << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
+    } else {
+        const int rc = read_reads(fasta, rc_reads, &text, &off, &nd);
+        if (rc) return rc;
+    }
+    clk.mark("sequence file");
     lime_ctx *ctx = nullptr;
     if (lime_init(pick_device(), &ctx) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(EXIT_FAILURE); }
     clk.mark("lime_init (HIP runtime)");
@@ -87,7 +105,7 @@ int main(int argc, char **argv)
     if (bad) {
         std::cerr << "Error usage " << argv[0] << " reads.fasta refs.fasta outBase [--rc] [--trlcp k]\n"
                   << "  writes outBase.ebwt, outBase.lcp, outBase.da of the collection reads + genomes; --rc: the reads' reverse complements;\n"
-                  << "  --trlcp k: lcp values truncated at k.\n"
+                  << "  --trlcp k: lcp values truncated at k.  reads.fasta may be four-line FASTQ (first byte '@'); refs.fasta is FASTA.\n"
                   << "or " << argv[0] << " --refs refs.fasta outBase [--trlcp k]\n"
                   << "  writes outBase.gidx, the index of the genomes alone;\n"
                   << "or " << argv[0] << " reads.fasta --gidx file.gidx outBase [--rc] [--trlcp k]\n"
@@ -100,10 +118,11 @@ int main(int argc, char **argv)
     uint64_t *off[2] = {nullptr, nullptr};
     uint32_t nd[2] = {0, 0};
     for (int k = 0; k < 2; ++k) {
-        const int rc = lime_fasta_read(pos[k], k == 0 ? rc_reads : 0, &text[k], &off[k], &nd[k]);
+        if (k == 0) { const int rc = read_reads(pos[0], rc_reads, &text[0], &off[0], &nd[0]); if (rc) return rc; continue; }
+        const int rc = lime_fasta_read(pos[k], 0, &text[k], &off[k], &nd[k]);
         if (rc != LIME_OK) { std::cerr << "Error reading " << pos[k] << "." << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
     }
-    clk.mark("FASTA files");
+    clk.mark("sequence files");
     if ((uint64_t)nd[0] + nd[1] > 0xFFFFFFFFull) { std::cerr << "Error: too many sequences." << std::endl; return 1; }
     const uint32_t n_docs = nd[0] + nd[1];
     const uint64_t n_reads_sym = off[0][nd[0]], n_text = n_reads_sym + off[1][nd[1]];

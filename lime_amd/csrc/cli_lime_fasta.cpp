@@ -1,7 +1,8 @@
-// LiME_fasta -- Preprocessing.sh + LiME_paired.sh for one sample, from FASTA files, as ONE process with nothing on disk in between:
+// LiME_fasta -- Preprocessing.sh + LiME_paired.sh for one sample, from FASTA or FASTQ files, as ONE process with nothing on disk in between:
 //   LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
 //              [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]
-// The files' bytes go to the device as they are and are parsed there (lime_docs_from_fasta); per collection (reads_1, its reverse
+// Each reads file is FASTA or four-line FASTQ, decided by its first byte ('@': FASTQ; lime_docs_from_file), the mates each on their own;
+// --refs is FASTA.  The files' bytes go to the device as they are and are parsed there; per collection (reads_1, its reverse
 // complements, reads_2, its reverse complements: the script's `seqtk seq -r`) the reads are merged into the genome index, scanned and
 // chosen from in HBM, the lists are classified there (lime_classify_sample_dev) and only the verdicts (12 bytes per read) come back to
 // be written as `output`.  --refs parses the genomes with the same device parser and builds their index in the process; --gidx loads
@@ -50,7 +51,8 @@ int main(int argc, char **argv)
         std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output\n"
                   << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]\n"
                   << "  classifies the reads of one sample (one file: single-end, two: paired-end) against the genomes of refs.fasta, or of an\n"
-                  << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  --trlcp k: lcp values\n"
+                  << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  A reads file is FASTA or\n"
+                  << "  four-line FASTQ, by its first byte ('@': FASTQ), each mate on its own; refs.fasta is FASTA.  --trlcp k: lcp values\n"
                   << "  truncated at k.  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
@@ -64,11 +66,11 @@ int main(int argc, char **argv)
     lime_docs *mates[2] = {nullptr, nullptr};
     uint32_t numReads = 0;
     for (uint32_t m = 0; m < n_mates; ++m) {
-        const int rc = lime_docs_from_fasta(ctx, reads[m], &mates[m]);
+        const int rc = lime_docs_from_file(ctx, reads[m], &mates[m]);
         if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
     }
     lime_docs_info(mates[0], &numReads, nullptr);
-    clk.mark("reads (FASTA on the device)");
+    clk.mark("reads (parsed on the device)");
     lime_gindex *gi = nullptr;
     if (refs) {
         lime_docs *g = nullptr;

@@ -1,5 +1,5 @@
-// lime_docs.cpp -- document collections that stay in HBM (lime_docs: made from the raw bytes of a FASTA file by the kernels of
-// lime_fasta_kernel.hip, or copied from parsed arrays), their reverse complements, and a whole sample from documents to verdicts
+// lime_docs.cpp -- document collections that stay in HBM (lime_docs: made from the raw bytes of a FASTA or FASTQ file by the kernels of
+// lime_fasta_kernel.hip / lime_fastq_kernel.hip, or copied from parsed arrays), their reverse complements, and a whole sample from documents to verdicts
 // (lime_classify_sample_dev: per collection the merge into the genome index, the scan and clusterChoose, then Classify over the lists).
 // include/lime_hip.h states the contract.
 #include <hip/hip_runtime.h>
@@ -114,20 +114,74 @@ static int parse_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint6
     return LIME_OK;
 }
 
-extern "C" int lime_docs_from_bytes_dev(lime_ctx *c, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out)
+// the same for four-line FASTQ: 24 bytes per block + rocPRIM's + one error word.  The error word comes back with the copy the write pass
+// is waited for anyway: two synchronisations, like parse_dev
+static int parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out)
 {
-    const char *who = "lime_docs_from_bytes_dev";
+    static const char *const reason[4] = {"record does not start with '@'", "separator line does not start with '+'",
+                                          "quality length differs from sequence length", "truncated record"};
+    const uint32_t nb = (uint32_t)((n + LIME_FASTA_BLOCK - 1) / LIME_FASTA_BLOCK);
+    uint32_t n_keep = 0, n_lines = 0;
+    uint64_t err_word = ~0ull;                           // line * 4 + reason of the lowest offence
+    DevBuf scratch;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t words = up(((size_t)nb + 1) * 4);
+    uint32_t *line0 = nullptr, *off_keep = nullptr, *off_diff = nullptr;
+    uint64_t *err = nullptr;
+    if (nb) {
+        size_t tmp_bytes = 0;
+        HIP_TRY(idx_scan_sum(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)nb + 1, false, st));
+        int rc = scratch.alloc(6 * words + 256 + up(tmp_bytes));
+        if (rc) return fail(rc, "%s: no device memory for the parse of %llu bytes: %s", who, (unsigned long long)n, lime_last_error());
+        uint8_t *at = static_cast<uint8_t *>(scratch.p);
+        auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
+        uint32_t *cnt = (uint32_t *)take(3 * words);     // '\n', kept bytes, kept minus quality bytes: each with a 0 behind the last block's
+        line0 = (uint32_t *)take(words); off_keep = (uint32_t *)take(words); off_diff = (uint32_t *)take(words);
+        err = (uint64_t *)take(256);                     // the error word, then n_lines
+        void *tmp = take(up(tmp_bytes));
+        uint32_t *cnt_lf = cnt, *cnt_keep = cnt + words / 4, *cnt_diff = cnt + 2 * (words / 4), *d_lines = (uint32_t *)(err + 1);
+        HIP_TRY(hipMemsetAsync(cnt, 0, 3 * words, st));
+        HIP_TRY(hipMemsetAsync(err, 0xFF, 8, st));
+        fq_launch_lines(d_bytes, n, nb, cnt_lf, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(idx_scan_sum(tmp, &tmp_bytes, cnt_lf, line0, (size_t)nb + 1, false, st));
+        fq_launch_count(d_bytes, n, nb, line0, cnt_keep, cnt_diff, err, d_lines, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(idx_scan_sum(tmp, &tmp_bytes, cnt_keep, off_keep, (size_t)nb + 1, false, st));
+        HIP_TRY(idx_scan_sum(tmp, &tmp_bytes, cnt_diff, off_diff, (size_t)nb + 1, false, st));
+        HIP_TRY(hipMemcpyAsync(&n_keep, off_keep + nb, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&n_lines, d_lines, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));               // (the totals size the handle)
+    }
+    DocsGuard dg;
+    int rc = docs_new(c, who, n_lines / 4, n_keep, dg); if (rc) return rc;
+    if (nb) {
+        fq_launch_write(d_bytes, n, nb, line0, off_keep, off_diff, n_lines / 4, dg.d->text.p, dg.d->doc_off.p, err, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&err_word, err, 8, hipMemcpyDeviceToHost, st));
+    } else {
+        HIP_TRY(hipMemsetAsync(dg.d->doc_off.p, 0, 8, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                   // (the scratch goes back when this returns)
+    if (err_word != ~0ull) return fail(LIME_ERR_ARG, "%s: line %llu: %s", who, (unsigned long long)(err_word >> 2), reason[err_word & 3u]);
+    *out = dg.take();
+    return LIME_OK;
+}
+
+typedef int (*ParseFn)(lime_ctx *, const char *, const uint8_t *, uint64_t, hipStream_t, lime_docs **);
+
+static int from_bytes_dev(lime_ctx *c, const char *who, ParseFn parse, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out)
+{
     if (!c || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
     *out = nullptr;
     int rc = check_input_size(who, n); if (rc) return rc;
     if (n && !d_bytes) return fail(LIME_ERR_ARG, "%s: NULL array", who);
     if ((rc = check_ctx(c, who))) return rc;
-    return parse_dev(c, who, d_bytes, n, (hipStream_t)stream, out);
+    return parse(c, who, d_bytes, n, (hipStream_t)stream, out);
 }
 
-extern "C" int lime_docs_from_bytes(lime_ctx *c, const uint8_t *bytes, uint64_t n, lime_docs **out)
+static int from_bytes(lime_ctx *c, const char *who, ParseFn parse, const uint8_t *bytes, uint64_t n, lime_docs **out)
 {
-    const char *who = "lime_docs_from_bytes";
     if (!c || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
     *out = nullptr;
     int rc = check_input_size(who, n); if (rc) return rc;
@@ -135,12 +189,11 @@ extern "C" int lime_docs_from_bytes(lime_ctx *c, const uint8_t *bytes, uint64_t 
     if ((rc = check_ctx(c, who))) return rc;
     DevBuf raw;
     if ((rc = raw.upload(bytes, (size_t)n))) return rc;
-    return parse_dev(c, who, (const uint8_t *)raw.p, n, nullptr, out);   // (raw goes back when this returns)
+    return parse(c, who, (const uint8_t *)raw.p, n, nullptr, out);       // (raw goes back when this returns)
 }
 
-extern "C" int lime_docs_from_fasta(lime_ctx *c, const char *path, lime_docs **out)
+static int from_path(lime_ctx *c, const char *who, ParseFn parse, const char *path, lime_docs **out)
 {
-    const char *who = "lime_docs_from_fasta";
     if (!c || !path || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
     *out = nullptr;
     FileGuard fg; fg.f = fopen(path, "rb");
@@ -166,7 +219,35 @@ extern "C" int lime_docs_from_fasta(lime_ctx *c, const char *path, lime_docs **o
         HIP_TRY(hipEventRecord(pin.ev[k], nullptr));
         n += got;
     }
-    return parse_dev(c, who, (const uint8_t *)raw.p, n, nullptr, out);   // synchronises: the copies are done before the buffers go
+    return parse(c, who, (const uint8_t *)raw.p, n, nullptr, out);       // synchronises: the copies are done before the buffers go
+}
+
+extern "C" int lime_docs_from_bytes_dev(lime_ctx *c, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out)
+{
+    return from_bytes_dev(c, "lime_docs_from_bytes_dev", parse_dev, d_bytes, n, stream, out);
+}
+extern "C" int lime_docs_from_bytes(lime_ctx *c, const uint8_t *bytes, uint64_t n, lime_docs **out) { return from_bytes(c, "lime_docs_from_bytes", parse_dev, bytes, n, out); }
+extern "C" int lime_docs_from_fasta(lime_ctx *c, const char *path, lime_docs **out) { return from_path(c, "lime_docs_from_fasta", parse_dev, path, out); }
+
+extern "C" int lime_docs_from_fastq_bytes_dev(lime_ctx *c, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out)
+{
+    return from_bytes_dev(c, "lime_docs_from_fastq_bytes_dev", parse_fastq_dev, d_bytes, n, stream, out);
+}
+extern "C" int lime_docs_from_fastq_bytes(lime_ctx *c, const uint8_t *bytes, uint64_t n, lime_docs **out)
+{
+    return from_bytes(c, "lime_docs_from_fastq_bytes", parse_fastq_dev, bytes, n, out);
+}
+extern "C" int lime_docs_from_fastq(lime_ctx *c, const char *path, lime_docs **out) { return from_path(c, "lime_docs_from_fastq", parse_fastq_dev, path, out); }
+
+// the one place a sequence file's format is decided (lime_seq_format: the first byte)
+extern "C" int lime_docs_from_file(lime_ctx *c, const char *path, lime_docs **out)
+{
+    const char *who = "lime_docs_from_file";
+    if (!c || !path || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    *out = nullptr;
+    int format = 0;
+    if (lime_seq_format(path, &format) != LIME_OK) return fail(LIME_ERR_IO, "%s: cannot open %s", who, path);
+    return format == 1 ? lime_docs_from_fastq(c, path, out) : lime_docs_from_fasta(c, path, out);
 }
 
 extern "C" int lime_docs_from_arrays_dev(lime_ctx *c, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,

@@ -7,6 +7,10 @@
 
 #include "lime_hip.h"
 
+namespace lime_host __attribute__((visibility("hidden"))) {
+int fail(int code, const char *fmt, ...);                 // lime_api.cpp: sets what lime_last_error() returns
+}
+
 namespace {
 struct File {
     FILE *f;
@@ -187,6 +191,13 @@ extern "C" int lime_write_res_bin_pairs(const char *path_bin, const char *path_p
 // '>' lines are headers and start a record; every other line's bytes, CR and LF dropped, are the record's symbols as they are (no case
 // folding; lines in front of the first header belong to no record and are skipped).  rc: every record reversed and complemented
 // (the script's `seqtk seq -r`): A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H in both cases; S, W, N and every other byte stay.
+static void complement_table(uint8_t comp[256])
+{
+    for (int b = 0; b < 256; ++b) comp[b] = (uint8_t)b;
+    const char *from = "ATCGURYKMBVDH", *to = "TAGCAYRMKVBHD";
+    for (int k = 0; from[k]; ++k) { comp[(uint8_t)from[k]] = (uint8_t)to[k]; comp[(uint8_t)(from[k] | 0x20)] = (uint8_t)(to[k] | 0x20); }
+}
+
 extern "C" int lime_fasta_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs)
 {
     if (!path || !text || !doc_off || !n_docs) return LIME_ERR_ARG;
@@ -194,9 +205,7 @@ extern "C" int lime_fasta_read(const char *path, int rc, uint8_t **text, uint64_
     File in(path, "rb");
     if (!in.f) return LIME_ERR_IO;
     uint8_t comp[256];
-    for (int b = 0; b < 256; ++b) comp[b] = (uint8_t)b;
-    const char *from = "ATCGURYKMBVDH", *to = "TAGCAYRMKVBHD";
-    for (int k = 0; from[k]; ++k) { comp[(uint8_t)from[k]] = (uint8_t)to[k]; comp[(uint8_t)(from[k] | 0x20)] = (uint8_t)(to[k] | 0x20); }
+    complement_table(comp);
     std::vector<uint8_t> sym;
     std::vector<uint64_t> off;
     std::vector<char> buf(1 << 20);
@@ -234,5 +243,90 @@ extern "C" int lime_fasta_read(const char *path, int rc, uint8_t **text, uint64_
     if (!sym.empty()) memcpy(t, sym.data(), sym.size());
     memcpy(o, off.data(), off.size() * 8);
     *text = t; *doc_off = o; *n_docs = nd;
+    return LIME_OK;
+}
+
+// ---- FASTQ in ----------------------------------------------------------------------------------
+// Four-line records, read line by line: '@' header, the sequence, '+' separator, the quality string.  The sequence line's bytes, CR
+// dropped, are the record's symbols as they are; the quality string only has to be as long as the sequence.  A line ends at its LF
+// or at the end of the file; what follows the last LF is a line only if it has a byte.  The first offending line is refused
+// (include/lime_hip.h lists the four reasons and their texts).  rc as in lime_fasta_read.
+extern "C" int lime_fastq_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs)
+{
+    const char *who = "lime_fastq_read";
+    if (!path || !text || !doc_off || !n_docs) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    *text = nullptr; *doc_off = nullptr; *n_docs = 0;
+    File in(path, "rb");
+    if (!in.f) return lime_host::fail(LIME_ERR_IO, "%s: cannot open %s", who, path);
+    uint8_t comp[256];
+    complement_table(comp);
+    std::vector<uint8_t> sym, line;
+    std::vector<uint64_t> off;
+    std::vector<char> buf(1 << 20);
+    uint64_t n_lines = 0;                                  // complete lines so far
+    size_t seq_len = 0;
+    // one line without its LF; -> 0, or the code that was reported
+    auto take_line = [&]() -> int {
+        const uint64_t no = ++n_lines;                     // this line's number, from 1
+        size_t len = 0;                                    // its bytes that are not CR
+        for (uint8_t ch : line) len += ch != '\r';
+        switch ((no - 1) & 3u) {
+        case 0:
+            if (line.empty() || line[0] != '@') return lime_host::fail(LIME_ERR_ARG, "%s: line %llu: record does not start with '@'", who, (unsigned long long)no);
+            if (off.size() >= 0xFFFFFFFFull) return lime_host::fail(LIME_ERR_ARG, "%s: more than 2^32 - 1 records", who);
+            off.push_back(sym.size());
+            break;
+        case 1:
+            for (uint8_t ch : line) if (ch != '\r') sym.push_back(ch);
+            seq_len = len;
+            if (rc) {
+                uint8_t *a = sym.data() + off.back(), *b = sym.data() + sym.size();
+                for (uint8_t *x = a, *y = b; x < y; ) { --y; const uint8_t u = comp[*x], v = comp[*y]; *x++ = v; *y = u; }
+            }
+            break;
+        case 2:
+            if (line.empty() || line[0] != '+') return lime_host::fail(LIME_ERR_ARG, "%s: line %llu: separator line does not start with '+'", who, (unsigned long long)no);
+            break;
+        default:
+            if (len != seq_len) return lime_host::fail(LIME_ERR_ARG, "%s: line %llu: quality length differs from sequence length", who, (unsigned long long)no);
+            break;
+        }
+        line.clear();
+        return 0;
+    };
+    size_t got;
+    bool open_line = false;                                // bytes since the last LF?
+    while ((got = fread(buf.data(), 1, buf.size(), in.f)) > 0) {
+        for (size_t i = 0; i < got; ++i) {
+            const uint8_t ch = (uint8_t)buf[i];
+            if (ch != '\n') { line.push_back(ch); open_line = true; continue; }
+            const int e = take_line(); if (e) return e;
+            open_line = false;
+        }
+    }
+    if (ferror(in.f)) return lime_host::fail(LIME_ERR_IO, "%s: cannot read %s", who, path);
+    if (open_line) { const int e = take_line(); if (e) return e; }
+    if (n_lines & 3u) return lime_host::fail(LIME_ERR_ARG, "%s: line %llu: truncated record", who, (unsigned long long)n_lines);
+    off.push_back(sym.size());
+    const uint32_t nd = (uint32_t)(off.size() - 1);
+    uint8_t *t = static_cast<uint8_t *>(malloc(sym.size() ? sym.size() : 1));
+    uint64_t *o = static_cast<uint64_t *>(malloc(off.size() * 8));
+    if (!t || !o) { free(t); free(o); return lime_host::fail(LIME_ERR_NOMEM, "%s: out of host memory", who); }
+    if (!sym.empty()) memcpy(t, sym.data(), sym.size());
+    memcpy(o, off.data(), off.size() * 8);
+    *text = t; *doc_off = o; *n_docs = nd;
+    return LIME_OK;
+}
+
+// the format of a sequence file by its first byte: '@' is FASTQ (1), anything else FASTA (0) -- an empty file and text in front of the
+// first FASTA header included
+extern "C" int lime_seq_format(const char *path, int *format)
+{
+    if (!path || !format) return lime_host::fail(LIME_ERR_ARG, "lime_seq_format: NULL argument");
+    File in(path, "rb");
+    if (!in.f) return lime_host::fail(LIME_ERR_IO, "lime_seq_format: cannot open %s", path);
+    const int ch = fgetc(in.f);
+    if (ch == EOF && ferror(in.f)) return lime_host::fail(LIME_ERR_IO, "lime_seq_format: cannot read %s", path);
+    *format = ch == '@';
     return LIME_OK;
 }

@@ -89,6 +89,19 @@ void fa_launch_check_off(const uint64_t *doc_off, uint32_t n_docs, uint64_t n_te
 // out[doc_off[d] + k] = comp[in[doc_off[d + 1] - 1 - k]]; out 16-byte aligned, doc_off checked
 void fa_launch_revcomp(const uint8_t *in, const uint64_t *doc_off, uint32_t n_docs, uint64_t n_text, uint8_t *out, hipStream_t st);
 
+// ---- lime_fastq_kernel.hip: four-line FASTQ bytes to documents (lime_docs.cpp) ----
+// The same blocks; the rule per byte and the refusals are at the head of the kernel file.  cnt_lf[k] = the '\n' of block k
+void fq_launch_lines(const uint8_t *b, uint64_t n, uint32_t n_blocks, uint32_t *cnt_lf, hipStream_t st);
+// line0 = the exclusive sum of cnt_lf over n_blocks + 1 entries (a 0 appended).  cnt_keep[k], cnt_diff[k] = kept bytes, and kept minus quality
+// bytes modulo 2^32, of block k; *n_lines; *err = min(itself, line * 4 + reason) over the offences of reasons 0, 1 and 3 (lines from 1)
+void fq_launch_count(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, uint32_t *cnt_keep, uint32_t *cnt_diff, uint64_t *err,
+                     uint32_t *n_lines, hipStream_t st);
+// off_keep, off_diff = the exclusive sums of the counts over n_blocks + 1 entries.  text (16-byte aligned, off_keep[n_blocks] bytes) and
+// doc_off[n_docs + 1], n_docs = n_lines / 4, are written, every byte and entry once if the input is valid, never out of bounds if it is
+// not; *err takes reason 2 the same way
+void fq_launch_write(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep, const uint32_t *off_diff,
+                     uint32_t n_docs, uint8_t *text, uint64_t *doc_off, uint64_t *err, hipStream_t st);
+
 // ---- lime_index_sort.hip: rocPRIM's device primitives.  temp == NULL: only *temp_bytes is set (the size to pass next time) ----
 struct IdxPairs { uint64_t *keys[2]; uint32_t *vals[2]; int cur; };       // double buffers; cur = which holds the data (updated by the sort)
 hipError_t idx_sort_pairs(void *temp, size_t *temp_bytes, IdxPairs *b, size_t m, unsigned begin_bit, unsigned end_bit, hipStream_t st);

@@ -12,6 +12,9 @@ Per input:
   (b) lime_fasta_read on the same file with rc 0 and rc 1: ms, GB/s
   (c) wall clock of `LiME_fasta reads_1 reads_2 --gidx` and of every step of the chain on the same files (whole processes, the HIP
       runtime's start included); the two classification files are compared; LiME_fasta's own phases from one more run.  --skip-big-chain leaves (c) out for `reads` (its chain writes 3.6 GB of .ebwt / .lcp / .da files).
+  (d) the same reads written as four-line FASTQ (222 bytes per record), in the same run: (a) without the reverse complement and (b) with
+      lime_docs_from_fastq* / lime_fastq_read, under "fastq"; and `LiME_fasta reads_1.fastq reads_2.fastq --gidx` next to the FASTA pair's run,
+      alternating, the two classification files compared, under "fastq_end_to_end_ms" (measured for both inputs, with or without the chain)
 Prints one JSON line after each input, the last one complete (and writes it to out.json if given)."""
 import ctypes as C
 import json
@@ -71,6 +74,19 @@ def fasta_of_reads(reads):
     return rec.tobytes()
 
 
+def fastq_of_reads(reads):
+    """the same reads as four-line FASTQ: the same 10-byte header line with '@', '+', qualities that cycle through '!' .. 'I' (222 bytes per record)"""
+    n = len(reads)
+    rec = np.empty((n, 10 + READ_LEN + 1 + 2 + READ_LEN + 1), dtype=np.uint8)
+    rec[:, :10 + READ_LEN + 1] = np.frombuffer(fasta_of_reads(reads), np.uint8).reshape(n, -1)
+    rec[:, 0] = ord("@")
+    rec[:, 111] = ord("+")
+    rec[:, 112] = 10
+    rec[:, 113:113 + READ_LEN] = 33 + (np.arange(n)[:, None] * 7 + np.arange(READ_LEN)[None, :]) % 41
+    rec[:, -1] = 10
+    return rec.tobytes()
+
+
 def fasta_of_genomes(genomes):
     out = []
     for k, g in enumerate(genomes):
@@ -91,37 +107,40 @@ def synthetic():
         reads = flat[start[:, None] + np.arange(READ_LEN)[None, :]]
         subst = rng.random(reads.shape) < 0.01
         reads = np.where(subst, sym[rng.integers(0, 4, size=reads.shape)], reads).astype(np.uint8)
-        files.append(fasta_of_reads(reads))
+        files.append(reads)
     return [g.tobytes() for g in genomes], files, MC.taxonomy(n_gen, rng, False)
 
 
-def parsers(ctx, path):
+def parsers(ctx, path, fastq=False):
     lib = _lib.load()
+    from_dev, from_file, host_read = ((ctx.docs_from_fastq_bytes_dev, ctx.docs_from_fastq, lib.lime_fastq_read) if fastq else
+                                      (ctx.docs_from_bytes_dev, ctx.docs_from_fasta, lib.lime_fasta_read))
     data = open(path, "rb").read()
     n = len(data)
     t = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).cuda()
     res = {"input_bytes": n}
-    res["device_parse_from_hbm"] = rate(n, best_of(lambda: ctx.docs_from_bytes_dev(t).close()))
-    res["device_parse_from_file"] = rate(n, best_of(lambda: ctx.docs_from_fasta(path).close()))
-    d = ctx.docs_from_bytes_dev(t)
+    res["device_parse_from_hbm"] = rate(n, best_of(lambda: from_dev(t).close()))
+    res["device_parse_from_file"] = rate(n, best_of(lambda: from_file(path).close()))
+    d = from_dev(t)
     res["n_docs"], res["n_text"] = d.info()
-    res["device_revcomp"] = rate(n, best_of(lambda: d.revcomp().close()))
+    if not fastq:
+        res["device_revcomp"] = rate(n, best_of(lambda: d.revcomp().close()))
     dev = {False: d.get(), True: d.revcomp().get()}
     d.close()
 
     def host(rc):
         pt, po, nd = C.c_void_p(), C.c_void_p(), C.c_uint32(0)
-        assert lib.lime_fasta_read(os.fsencode(path), int(rc), C.byref(pt), C.byref(po), C.byref(nd)) == 0
+        assert host_read(os.fsencode(path), int(rc), C.byref(pt), C.byref(po), C.byref(nd)) == 0
         off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(nd.value + 1,)).copy()
         text = np.frombuffer(C.string_at(pt, int(off[-1])), np.uint8)
         lib.lime_free(pt); lib.lime_free(po)
         return text, off
 
     for rc in (False, True):
-        key = "lime_fasta_read_rc%d" % rc
+        key = ("lime_fastq_read_rc%d" if fastq else "lime_fasta_read_rc%d") % rc
         pt, po, nd = C.c_void_p(), C.c_void_p(), C.c_uint32(0)
         def call():
-            assert lib.lime_fasta_read(os.fsencode(path), int(rc), C.byref(pt), C.byref(po), C.byref(nd)) == 0
+            assert host_read(os.fsencode(path), int(rc), C.byref(pt), C.byref(po), C.byref(nd)) == 0
             lib.lime_free(pt); lib.lime_free(po)
         res[key] = rate(n, best_of(call))
         text, off = host(rc)
@@ -166,15 +185,35 @@ def chains(d, n_reads, n_refs):
     return best
 
 
-def one_input(ctx, genomes, read_files, lineage, chain):
+def fastq_end_to_end(d):
+    """LiME_fasta --gidx on the FASTQ pair next to the FASTA pair, best of 3 whole runs each after a warm-up, alternating"""
+    gidx, tax = os.path.join(d, "g.gidx"), os.path.join(d, "LineageFile.csv")
+    best = {}
+    for k in range(4):
+        for key, ext in (("LiME_fasta on FASTA", "fasta"), ("LiME_fasta on FASTQ", "fastq")):
+            ms = timed([os.path.join(BIN, "LiME_fasta"), os.path.join(d, "reads_1." + ext), os.path.join(d, "reads_2." + ext), "--gidx", gidx, "--lineage", tax,
+                        "--readlen", str(READ_LEN), "--out", os.path.join(d, "e2e_" + ext + ".txt")], d)
+            if k:
+                best[key] = min(best.get(key, ms), ms)
+    p = subprocess.run([os.path.join(BIN, "LiME_fasta"), os.path.join(d, "reads_1.fastq"), os.path.join(d, "reads_2.fastq"), "--gidx", gidx, "--lineage", tax,
+                        "--readlen", str(READ_LEN), "--out", os.path.join(d, "e2e_fastq.txt")], env=dict(os.environ, LIME_CLI_TIMING="1"), capture_output=True, cwd=d)
+    best["LiME_fasta_on_FASTQ_phases"] = {m.group(1).strip(): float(m.group(2)) for m in re.finditer(r"\[cli\] (.+?)\s+([\d.]+) ms \(at", p.stderr.decode())}
+    best["classification_equal"] = open(os.path.join(d, "e2e_fasta.txt"), "rb").read() == open(os.path.join(d, "e2e_fastq.txt"), "rb").read()
+    return best
+
+
+def one_input(ctx, genomes, reads, lineage, chain):
     with tempfile.TemporaryDirectory() as d:
-        for name, data in zip(("reads_1.fasta", "reads_2.fasta"), read_files):
-            open(os.path.join(d, name), "wb").write(data)
+        for name, rows in zip(("reads_1", "reads_2"), reads):
+            open(os.path.join(d, name + ".fasta"), "wb").write(fasta_of_reads(rows))
+            open(os.path.join(d, name + ".fastq"), "wb").write(fastq_of_reads(rows))
         open(os.path.join(d, "refs.fasta"), "wb").write(fasta_of_genomes(genomes))
         open(os.path.join(d, "LineageFile.csv"), "wb").write(lineage)
         res = parsers(ctx, os.path.join(d, "reads_1.fasta"))
+        res["fastq"] = parsers(ctx, os.path.join(d, "reads_1.fastq"), fastq=True)
+        res["index_ms"] = timed([os.path.join(BIN, "BuildIndex"), "--refs", os.path.join(d, "refs.fasta"), os.path.join(d, "g")], d)
+        res["fastq_end_to_end_ms"] = fastq_end_to_end(d)
         if chain:
-            res["index_ms"] = timed([os.path.join(BIN, "BuildIndex"), "--refs", os.path.join(d, "refs.fasta"), os.path.join(d, "g")], d)
             res["end_to_end_ms"] = chains(d, res["n_docs"], len(genomes))
         else:
             res["end_to_end_ms"] = "not measured"
@@ -197,7 +236,7 @@ def main():
             with open(args[0], "w") as f:
                 f.write(line + "\n")
 
-    res["example"] = one_input(ctx, genomes, [fasta_of_reads(as_rows(sets["F1"])), fasta_of_reads(as_rows(sets["F2"]))], bytes(z["lineage"]), True)
+    res["example"] = one_input(ctx, genomes, [as_rows(sets["F1"]), as_rows(sets["F2"])], bytes(z["lineage"]), True)
     emit()                                       # (the large input's chain takes minutes: what is measured so far is on record)
     res["reads"] = one_input(ctx, *synthetic(), "--skip-big-chain" not in sys.argv)
     ctx.close()
