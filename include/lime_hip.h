@@ -596,6 +596,78 @@ int lime_classify_sample_dev(lime_ctx *ctx, uint32_t n_mates, const lime_docs *c
                              const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
                              uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream);
 
+/* ---- a reads file in batches of records, and a sample of any size classified batch by batch ------------------------ *
+ * A read's verdict depends on that read and the genomes and on no other read, so a sample cut into batches of reads, each merged into
+ * the same genome index, gives the verdicts of the whole sample.
+ *
+ * The cut (lime_seqcut_kernel.hip).  d_bytes[0 .. n), n <= 2^32 - 1, at any alignment, is a window of a reads file that begins at a record
+ * start or is the file's first window; format is lime_seq_format's (0 FASTA, 1 FASTQ); max_reads >= 1; eof != 0: the window ends at the
+ * file's end.  Out come *cut, *n_records = m and *n_markers: d_bytes[0 .. cut) holds exactly the next m whole records, d_bytes[cut .. n)
+ * belongs to the next window.
+ *   FASTQ  a marker is an LF, T their number.  eof and T / 4 < max_reads: cut = n and m = the records the parser will find or refuse
+ *          (n_lines / 4; a last line without LF is a line).  Otherwise m = min(max_reads, T / 4) and cut = 1 + the position of LF number
+ *          4m (counted from 1); m = 0: cut = 0.
+ *   FASTA  a marker is a line-first '>' (byte i is '>' and i = 0 or byte i - 1 is LF), H their number.
+ *          m = min(max_reads, eof ? H : max(H, 1) - 1).  cut = n where eof and m = H; otherwise cut = the position of marker number m
+ *          counted from 0 (H = 0: cut = 0).  Bytes in front of the first marker of the file's first window stay in front of record 0,
+ *          where the parser skips them.
+ * One pass counts the markers per block of LIME_FASTA_BLOCK bytes, one prefix sum numbers them, one pass finds the wanted one; 24 bytes
+ * come back.  Device memory: 8 bytes per block + the prefix sum's, given back before the call returns.  Synchronises `stream`. */
+int lime_seq_cut_dev(lime_ctx *ctx, const uint8_t *d_bytes, uint64_t n, int format, uint32_t max_reads, int eof, void *stream,
+                     uint64_t *cut, uint64_t *n_records, uint64_t *n_markers);
+
+/* lime_seq_reader (ctx-owned, opaque): a FASTA or four-line FASTQ file, or such a file's bytes in host memory the caller keeps alive,
+ * handed out in batches of records without ever being parsed whole.  window_bytes: the raw device window's size; 0 = 64 MiB, at most the
+ * source's size; any value >= 1 is legal.
+ * next: *docs = the next max_reads (>= 1) records as an ordinary lime_docs (the caller's, lime_docs_free); every batch but the last holds
+ * exactly max_reads.  *docs = NULL with LIME_OK: the end of the file.  *first_record (may be NULL): the number of the batch's first record.
+ * The window is refilled through two pinned buffers, cut (lime_seq_cut_dev) and parsed up to the cut with the passes of
+ * lime_docs_from_bytes_dev / lime_docs_from_fastq_bytes_dev; the bytes behind the cut stay and move to the window's front only when it is
+ * refilled.  A window that holds fewer than max_reads whole records and is not at the file's end is refilled; where it is full it is
+ * doubled, up to 2^32 - 1 bytes, beyond which the call is LIME_ERR_ARG with a text that says so.
+ * The batches' texts and offsets, concatenated, are byte for byte lime_fastq_read's / lime_fasta_read's of the whole file, for every
+ * max_reads and every window_bytes.  A malformed FASTQ ends the call that meets it with the whole-file call's code, reason and line
+ * number in the FILE; the batches before it have been handed out, *docs = NULL, nothing of that call stays allocated, and later calls
+ * repeat the refusal.  More than 2^32 - 1 records in all: LIME_ERR_ARG.  LIME_ERR_IO where the file cannot be read.
+ * Device memory: the window (+ a second one while it moves its tail or doubles), the cut's and the parse's scratch for one batch.
+ * info: any pointer may be NULL; *n_lines counts FASTQ lines (4 per record handed out), 0 for FASTA.
+ * A reader is released by lime_seq_reader_close, or by lime_shutdown of its ctx (not both).  The calls work on the default stream. */
+typedef struct lime_seq_reader lime_seq_reader;
+int  lime_seq_reader_open(lime_ctx *ctx, const char *path, uint64_t window_bytes, lime_seq_reader **out);
+int  lime_seq_reader_open_bytes(lime_ctx *ctx, const uint8_t *bytes, uint64_t n, int format, uint64_t window_bytes, lime_seq_reader **out);
+int  lime_seq_reader_next(lime_seq_reader *r, uint32_t max_reads, lime_docs **docs, uint64_t *first_record);
+int  lime_seq_reader_info(const lime_seq_reader *r, int *format, uint64_t *n_records, uint64_t *n_lines, uint64_t *n_bytes,
+                          uint64_t *window_bytes);
+void lime_seq_reader_close(lime_seq_reader *r);
+
+/* lime_classify_sample_dev batch by batch: per batch, batch_reads (>= 1) records from each of the n_mates readers, one unchanged
+ * lime_classify_sample_dev call on them, then sink(user, first_read, verdicts, n, stats) with the batch's verdicts and its 2 * n_mates
+ * scan counters (sink may be NULL), then the batch is freed.  counts (may be NULL) = {C, U, A, H} summed over the batches; *n_reads,
+ * *n_batches (may be NULL) what was classified.  stats are PER-BATCH figures: a cluster with reads of three batches counts three times,
+ * and max_len is that of the batch's part of a cluster; they are not the whole sample's numbers.  A cluster longer than
+ * LIME_MAX_CLUSTER in the whole sample may be shorter in every batch: batching can succeed where the whole run is LIME_ERR_MAXLEN,
+ * never the reverse.
+ * LIME_ERR_ARG before any read: lime_classify_sample_dev's argument refusals, a NULL reader or one of another context, batch_reads = 0.
+ * A mate that ends before the other: LIME_ERR_ARG, "the read sets hold different numbers of reads" with both record counts (the longer
+ * file is read to its end for it); no read at all: LIME_ERR_ARG.  A reader's refusal ends the call with it.  A non-zero return of the
+ * sink ends the call with that value.  On any error nothing of this call stays allocated (the readers stay open, where they stopped).
+ * Peak device memory, independent of the sample's size: lime_classify_sample_dev's for n_mates read sets of batch_reads reads (see
+ * there: with P = a batch's read positions + the index's, 9 P for a collection's arrays + 17 per read position + 8 per genome position
+ * of merge scratch + the reverse complement + the batch's lists) + the batch's documents + the readers' windows. */
+typedef int (*lime_verdict_sink)(void *user, uint64_t first_read, const lime_verdict_t *verdicts, uint32_t n, const lime_stats_t *stats);
+int lime_classify_sample_stream(lime_ctx *ctx, uint32_t n_mates, lime_seq_reader *const *readers, const lime_gindex *gi,
+                                const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
+                                uint32_t lcp_cap, uint32_t batch_reads, lime_verdict_sink sink, void *user, uint64_t counts[4],
+                                uint64_t *n_reads, uint64_t *n_batches, void *stream);
+
+/* The classification file in parts: open writes the header under a temporary name, append the lines of verdicts[0 .. n) with the read
+ * ids first_read + i, close(commit != 0) renames the file to `path`, close(0) removes it.  Appending the parts of a verdict array gives
+ * lime_write_classification's file byte for byte.  Pure host code; errors in lime_classify_error(). */
+typedef struct lime_classification_writer lime_classification_writer;
+int lime_classification_writer_open(const char *path, lime_classification_writer **out);
+int lime_classification_writer_append(lime_classification_writer *w, uint64_t first_read, const lime_verdict_t *verdicts, uint32_t n);
+int lime_classification_writer_close(lime_classification_writer *w, int commit);
+
 #ifdef __cplusplus
 }
 #endif

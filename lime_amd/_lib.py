@@ -153,7 +153,19 @@ SYMBOLS = {
     "lime_docs_get": (_i, [_vp, _vp, _vp]),
     "lime_docs_free": (None, [_vp]),
     "lime_classify_sample_dev": (_i, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, C.c_float, _i, _i, _u32, _vp, _vp, _vp, _vp]),
+    "lime_seq_cut_dev": (_i, [_vp, _vp, _u64, _i, _u32, _i, _vp, _pu64, _pu64, _pu64]),
+    "lime_seq_reader_open": (_i, [_vp, C.c_char_p, _u64, _pp]),
+    "lime_seq_reader_open_bytes": (_i, [_vp, _vp, _u64, _i, _u64, _pp]),
+    "lime_seq_reader_next": (_i, [_vp, _u32, _pp, _pu64]),
+    "lime_seq_reader_info": (_i, [_vp, C.POINTER(_i), _pu64, _pu64, _pu64, _pu64]),
+    "lime_seq_reader_close": (None, [_vp]),
+    "lime_classify_sample_stream": (_i, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, C.c_float, _i, _i, _u32, _u32, _vp, _vp, _vp, _pu64, _pu64, _vp]),
+    "lime_classification_writer_open": (_i, [C.c_char_p, _pp]),
+    "lime_classification_writer_append": (_i, [_vp, _u64, _vp, _u32]),
+    "lime_classification_writer_close": (_i, [_vp, _i]),
 }
+# lime_verdict_sink: int (*)(void *user, uint64_t first_read, const lime_verdict_t *verdicts, uint32_t n, const lime_stats_t *stats)
+VERDICT_SINK = C.CFUNCTYPE(_i, _vp, _u64, _vp, _u32, C.POINTER(Stats))
 
 _LIB = None
 

@@ -450,6 +450,115 @@ class Context:
                                                 int(bool(binary)), int(lcp_cap), v.ctypes.data, counts, st, stream))
         return v[:n_reads], list(counts), [st[i] for i in range(2 * k)]
 
+    # ---- a reads file in batches of records, a sample of any size batch by batch (include/lime_hip.h: lime_seq_reader) ----
+    def seq_cut_dev(self, bytes_t, fmt, max_reads, eof, n=None, stream=None):
+        """where a window of a reads file (a torch uint8 device tensor, a view at any alignment) is cut so that whole records stand in front
+        (lime_seq_cut_dev); fmt "fasta" / "fastq" or 0 / 1 -> (cut, n_records, n_markers)"""
+        n = int(bytes_t.numel()) if n is None else int(n)
+        cut, m, t = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.lime_seq_cut_dev(self.h, _ptr(bytes_t), n, _format_of(fmt), int(max_reads), int(bool(eof)), stream,
+                                        C.byref(cut), C.byref(m), C.byref(t)))
+        return int(cut.value), int(m.value), int(t.value)
+
+    def _reader_of(self, h, keep=None):
+        import weakref
+        r = SeqReader(self, h, keep)
+        self._lists = [x for x in self._lists if x() is not None] + [weakref.ref(r)]
+        return r
+
+    def seq_reader(self, path, window_bytes=0):
+        """a FASTA or FASTQ file (by seq_format(path)) handed out in batches of records -> SeqReader"""
+        h = C.c_void_p()
+        check(self.lib.lime_seq_reader_open(self.h, os.fsencode(path), int(window_bytes), C.byref(h)))
+        return self._reader_of(h)
+
+    def seq_reader_bytes(self, data, fmt, window_bytes=0):
+        """the same over the bytes of such a file (bytes or a uint8 array, kept alive by the reader)"""
+        a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        h = C.c_void_p()
+        check(self.lib.lime_seq_reader_open_bytes(self.h, a.ctypes.data if len(a) else None, len(a), _format_of(fmt), int(window_bytes), C.byref(h)))
+        return self._reader_of(h, a)
+
+    def classify_sample_stream(self, readers, gi, taxonomy, alpha, norm, beta, batch_reads, ebwt=True, binary=True, lcp_cap=0, sink=None, stream=None):
+        """classify_sample batch by batch over 1 or 2 SeqReaders (lime_classify_sample_stream).  sink(first_read, verdicts, stats) is called
+        per batch with a VERDICT array that is only valid during the call and the batch's Stats; a non-zero return ends the call (LimeError
+        with that code).  Without a sink -> (verdicts of all reads, counts {C, U, A, H}, [per-batch list of Stats]); with one ->
+        (n_reads, counts, n_batches)"""
+        k = len(readers)
+        hs = (C.c_void_p * max(k, 1))(*[r.h for r in readers])
+        parts, per_batch, raised = [], [], []
+
+        def cb(_user, first_read, pv, n, pst):
+            try:
+                v = np.ctypeslib.as_array(C.cast(pv, C.POINTER(C.c_uint8)), shape=(n * VERDICT.itemsize,)).view(VERDICT)
+                st = [Stats.from_buffer_copy(pst[i]) for i in range(2 * k)]
+                if sink is None:
+                    parts.append(v.copy()); per_batch.append(st)
+                    return 0
+                return int(sink(int(first_read), v, st) or 0)
+            except BaseException as e:               # (an exception cannot cross the C frames: it is raised again below)
+                raised.append(e)
+                return _lib.ERR_ARG
+        fn = _lib.VERDICT_SINK(cb)
+        counts = (C.c_uint64 * 4)()
+        n_reads, n_batches = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.lime_classify_sample_stream(self.h, k, hs, gi.h, taxonomy.h, int(alpha), int(norm) & 0xFFFFFFFF, float(beta), int(bool(ebwt)),
+                                                  int(bool(binary)), int(lcp_cap), int(batch_reads), C.cast(fn, C.c_void_p), None, counts, C.byref(n_reads), C.byref(n_batches),
+                                                  stream)
+        if raised:
+            raise raised[0]
+        if rc > 0:
+            raise LimeError(rc, "the sink ended the call")
+        check(rc)
+        if sink is None:
+            return (np.concatenate(parts) if parts else np.zeros(0, dtype=VERDICT)), list(counts), per_batch
+        return int(n_reads.value), list(counts), int(n_batches.value)
+
+
+def _format_of(fmt):
+    if fmt in ("fasta", "fastq"):
+        return int(fmt == "fastq")
+    return int(fmt)
+
+
+class SeqReader:
+    """a reads file handed out in batches of records (lime_seq_reader), owned by its Context; iterating gives Docs of `batch` records"""
+
+    def __init__(self, ctx, h, keep=None, batch=65536):
+        self.ctx, self.h, self._keep, self.batch = ctx, h, keep, batch
+
+    def next(self, max_reads):
+        """the next max_reads records -> (Docs, number of its first record), or None at the end of the file"""
+        d, first = C.c_void_p(), C.c_uint64(0)
+        check(self.ctx.lib.lime_seq_reader_next(self.h, int(max_reads), C.byref(d), C.byref(first)))
+        if not d:
+            return None
+        return self.ctx._docs_of(d), int(first.value)
+
+    def __iter__(self):
+        while True:
+            b = self.next(self.batch)
+            if b is None:
+                return
+            yield b[0]
+
+    def info(self):
+        f, nr, nl, nb, w = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(self.ctx.lib.lime_seq_reader_info(self.h, C.byref(f), C.byref(nr), C.byref(nl), C.byref(nb), C.byref(w)))
+        return {"format": "fastq" if f.value == 1 else "fasta", "records": int(nr.value), "lines": int(nl.value), "bytes": int(nb.value),
+                "window_bytes": int(w.value)}
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lime_seq_reader_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class Docs:
     """a document collection resident in HBM (lime_docs), owned by its Context"""
@@ -583,6 +692,39 @@ def write_classification(path, verdicts):
     """the classification file (lime_classify's bytes) from VERDICT records"""
     v = np.ascontiguousarray(verdicts, dtype=VERDICT)
     check_cls(_lib.load().lime_write_classification(str(path).encode(), v.ctypes.data if len(v) else None, len(v)))
+
+
+class ClassificationWriter:
+    """the classification file in parts (lime_classification_writer): written under a temporary name, renamed by close(commit=True).
+    As a context manager it commits on a clean exit and removes the file on an exception"""
+
+    def __init__(self, path):
+        self.lib = _lib.load()
+        h = C.c_void_p()
+        check_cls(self.lib.lime_classification_writer_open(os.fsencode(path), C.byref(h)))
+        self.h = h
+
+    def append(self, first_read, verdicts):
+        v = np.ascontiguousarray(verdicts, dtype=VERDICT)
+        check_cls(self.lib.lime_classification_writer_append(self.h, int(first_read), v.ctypes.data if len(v) else None, len(v)))
+
+    def close(self, commit=True):
+        if self.h:
+            h, self.h = self.h, None
+            check_cls(self.lib.lime_classification_writer_close(h, int(bool(commit))))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.close(commit=exc_type is None)
+        return False
+
+    def __del__(self):
+        try:
+            self.close(commit=False)
+        except Exception:
+            pass
 
 
 def classify_mem(lists, norms, betas, n_targ, taxonomy, binary=True):
@@ -778,11 +920,12 @@ def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, thread
 
 
 def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16, beta=0.25, rank=1, trlcp=0, ebwt=True, higher=False, binary=True,
-               ctx=None):
+               ctx=None, batch_reads=0, window_bytes=0):
     """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
     [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta: the files are parsed on the device (each reads file
     FASTA or four-line FASTQ, by its first byte; refs FASTA), the
-    genome index is built there (refs) or loaded (gidx), only `output` is written.  -> counts {C, U, A, H}"""
+    genome index is built there (refs) or loaded (gidx), only `output` is written.  batch_reads > 0: `--batch-reads N [--window-bytes W]`,
+    the sample read and classified N reads at a time, `output` appended to batch by batch and renamed at the end.  -> counts {C, U, A, H}"""
     reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
     if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
         raise ValueError("LiME_fasta takes one or two reads files and either refs or gidx")
@@ -791,7 +934,10 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     ctx = ctx or Context()
     tx = None
     try:
-        mates = [ctx.docs_from_file(r) for r in reads]
+        if batch_reads:
+            mates = [ctx.seq_reader(r, window_bytes) for r in reads]
+        else:
+            mates = [ctx.docs_from_file(r) for r in reads]
         if refs is not None:
             g = ctx.docs_from_fasta(refs)
             nd, nt = g.info()
@@ -803,7 +949,12 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
         else:
             gi = ctx.load_genome_index(gidx)
         tx = Taxonomy(lineage, rank, higher, gi.info()["n_docs"])
-        v, counts, _ = ctx.classify_sample(mates, gi, tx, alpha, norm, float(np.float32(beta)), ebwt, binary, 0 if refs is not None else trlcp)
+        if batch_reads:
+            with ClassificationWriter(output) as w:
+                _, counts, _ = ctx.classify_sample_stream(mates, gi, tx, alpha, norm, float(np.float32(beta)), batch_reads, ebwt, binary,
+                                                          0 if refs is not None else trlcp, sink=lambda first, v, st: w.append(first, v))
+        else:
+            v, counts, _ = ctx.classify_sample(mates, gi, tx, alpha, norm, float(np.float32(beta)), ebwt, binary, 0 if refs is not None else trlcp)
         for d in mates:
             d.close()
         gi.close()
@@ -812,7 +963,8 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
             ctx.close()
         if tx is not None:
             tx.close()
-    write_classification(output, v)
+    if not batch_reads:
+        write_classification(output, v)
     return counts
 
 

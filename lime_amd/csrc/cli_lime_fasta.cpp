@@ -1,12 +1,17 @@
 // LiME_fasta -- Preprocessing.sh + LiME_paired.sh for one sample, from FASTA or FASTQ files, as ONE process with nothing on disk in between:
 //   LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
-//              [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]
+//              [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]]
 // Each reads file is FASTA or four-line FASTQ, decided by its first byte ('@': FASTQ; lime_docs_from_file), the mates each on their own;
 // --refs is FASTA.  The files' bytes go to the device as they are and are parsed there; per collection (reads_1, its reverse
 // complements, reads_2, its reverse complements: the script's `seqtk seq -r`) the reads are merged into the genome index, scanned and
 // chosen from in HBM, the lists are classified there (lime_classify_sample_dev) and only the verdicts (12 bytes per read) come back to
 // be written as `output`.  --refs parses the genomes with the same device parser and builds their index in the process; --gidx loads
 // one that BuildIndex --refs wrote.  --trlcp k: lcp values truncated at k (eGap's option; with --gidx at most the index's).
+// --batch-reads N: a sample of any size.  The reads files are read N records at a time (lime_seq_reader, through a raw device window of
+// W bytes, default 64 MiB), each batch is classified on its own against the same genome index (lime_classify_sample_stream) and its
+// lines are appended to `output`, which is written under a temporary name and renamed at the end: a failure half-way leaves no output
+// file.  The verdicts are those of the whole sample; the cluster count and the maximum length printed per collection are PER-BATCH
+// figures (the count summed over the batches, the largest of the batches' maxima): a cluster with reads of three batches counts three times.
 // The defaults are the script's constants (LiME_paired.sh:21-23); norm = readLen + 1 - alpha (ClusterBWT_DA.cpp:555).  The reference's
 // compile-time switches are environment variables, as for the other drop-ins: LIME_EBWT (default 1), LIME_BIN (default 1), LIME_HIGHER (0).
 #include <string.h>
@@ -23,13 +28,35 @@ static int env_flag(const char *name, int dflt)
     return s ? atoi(s) != 0 : dflt;
 }
 
+namespace {
+struct BatchSink {                             // --batch-reads: the writer and the collections' counters over the batches
+    lime_classification_writer *w = nullptr;
+    uint32_t n_coll = 0;
+    uint64_t n_clusters[4] = {0, 0, 0, 0}, max_len[4] = {0, 0, 0, 0};
+    bool write_failed = false;                 // the call ended with the writer's error: its text is in lime_classify_error
+};
+int batch_sink(void *user, uint64_t first_read, const lime_verdict_t *verdicts, uint32_t n, const lime_stats_t *stats)
+{
+    BatchSink *s = static_cast<BatchSink *>(user);
+    for (uint32_t k = 0; k < s->n_coll; ++k) {
+        s->n_clusters[k] += stats[k].n_clusters;
+        if (stats[k].max_len > s->max_len[k]) s->max_len[k] = stats[k].max_len;
+    }
+    const int rc = lime_classification_writer_append(s->w, first_read, verdicts, n);
+    s->write_failed = rc != LIME_OK;
+    return rc;
+}
+}
+
 int main(int argc, char **argv)
 {
     CliClock clk;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<const char *> reads;
     const char *refs = nullptr, *gidx = nullptr, *lineage = nullptr, *output = nullptr;
-    unsigned alpha = 16, rank = 1, trlcp = 0;
+    unsigned alpha = 16, rank = 1, trlcp = 0, batch_reads = 0;
+    unsigned long long window_bytes = 0;
+    bool batched = false, have_window = false;
     float beta = 0.25f;
     unsigned char readLen = 0;                 // dataTypeSim, parsed with %hhu like ClusterBWT_DA (:519-521)
     bool bad = false, have_len = false;
@@ -44,16 +71,22 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--beta")) { if (more && sscanf(argv[i + 1], "%f", &beta) == 1) ++i; else bad = true; }
         else if (!strcmp(argv[i], "--rank")) { if (more && sscanf(argv[i + 1], "%u", &rank) == 1) ++i; else bad = true; }
         else if (!strcmp(argv[i], "--trlcp")) { if (more && sscanf(argv[i + 1], "%u", &trlcp) == 1) ++i; else bad = true; }
+        else if (!strcmp(argv[i], "--batch-reads")) { if (more && sscanf(argv[i + 1], "%u", &batch_reads) == 1 && batch_reads) { ++i; batched = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--window-bytes")) { if (more && sscanf(argv[i + 1], "%llu", &window_bytes) == 1 && window_bytes) { ++i; have_window = true; } else bad = true; }
         else reads.push_back(argv[i]);
     }
+    if (have_window && !batched) bad = true;
     if (reads.empty() || reads.size() > 2 || !refs == !gidx || !lineage || !output || !have_len) bad = true;
     if (bad) {
         std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output\n"
-                  << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]\n"
+                  << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]]\n"
                   << "  classifies the reads of one sample (one file: single-end, two: paired-end) against the genomes of refs.fasta, or of an\n"
                   << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  A reads file is FASTA or\n"
                   << "  four-line FASTQ, by its first byte ('@': FASTQ), each mate on its own; refs.fasta is FASTA.  --trlcp k: lcp values\n"
-                  << "  truncated at k.  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
+                  << "  truncated at k.  --batch-reads N: a sample of any size, read and classified N reads at a time (through a window of W\n"
+                  << "  bytes per file); the verdicts are the whole sample's, the clusters and maximum length printed per collection are\n"
+                  << "  per-batch figures (summed / the largest over the batches: a cluster with reads of three batches counts three times).\n"
+                  << "  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
     const int EBWT = env_flag("LIME_EBWT", 1), BIN = env_flag("LIME_BIN", 1), HIGHER = env_flag("LIME_HIGHER", 0);
@@ -64,13 +97,18 @@ int main(int argc, char **argv)
     if (lime_init(pick_device(), &ctx) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(EXIT_FAILURE); }
     clk.mark("lime_init (HIP runtime)");
     lime_docs *mates[2] = {nullptr, nullptr};
-    uint32_t numReads = 0;
-    for (uint32_t m = 0; m < n_mates; ++m) {
+    lime_seq_reader *readers[2] = {nullptr, nullptr};
+    uint64_t numReads = 0;
+    for (uint32_t m = 0; m < n_mates && batched; ++m) {
+        const int rc = lime_seq_reader_open(ctx, reads[m], window_bytes, &readers[m]);
+        if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
+    }
+    for (uint32_t m = 0; m < n_mates && !batched; ++m) {
         const int rc = lime_docs_from_file(ctx, reads[m], &mates[m]);
         if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
     }
-    lime_docs_info(mates[0], &numReads, nullptr);
-    clk.mark("reads (parsed on the device)");
+    if (!batched) { uint32_t nd = 0; lime_docs_info(mates[0], &nd, nullptr); numReads = nd; }
+    clk.mark(batched ? "readers" : "reads (parsed on the device)");
     lime_gindex *gi = nullptr;
     if (refs) {
         lime_docs *g = nullptr;
@@ -88,24 +126,48 @@ int main(int argc, char **argv)
     uint32_t numTarg = 0;
     lime_gindex_info(gi, &numTarg, nullptr, nullptr, nullptr);
     clk.mark("genome index");
-    std::cout << "numReads: " << numReads << "\nnumGenomes: " << numTarg << std::endl;
+    if (batched) std::cout << "numGenomes: " << numTarg << std::endl;        // (numReads is known after the last batch)
+    else std::cout << "numReads: " << numReads << "\nnumGenomes: " << numTarg << std::endl;
 
     lime_taxonomy *tx = nullptr;
     std::cout << "Reading " << lineage << std::endl;
     if (lime_taxonomy_load(lineage, (int)rank, HIGHER, numTarg, &tx) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
-    std::vector<lime_verdict_t> verdicts(numReads ? numReads : 1);
     uint64_t counts[4] = {0, 0, 0, 0};
-    lime_stats_t stats[4];
-    std::cerr << "Start comparing..." << std::endl;
-    if (lime_classify_sample_dev(ctx, n_mates, mates, gi, tx, alpha, norm, beta, EBWT, BIN, refs ? 0 : trlcp, verdicts.data(), counts, stats, nullptr) != LIME_OK) {
-        std::cerr << "Error: " << lime_last_error() << std::endl; exit(1);
+    if (batched) {
+        BatchSink sink;
+        sink.n_coll = 2 * n_mates;
+        if (lime_classification_writer_open(output, &sink.w) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
+        std::cerr << "Start comparing..." << std::endl;
+        uint64_t n_batches = 0;
+        const int rc = lime_classify_sample_stream(ctx, n_mates, readers, gi, tx, alpha, norm, beta, EBWT, BIN, refs ? 0 : trlcp, batch_reads, batch_sink, &sink,
+                                                   counts, &numReads, &n_batches, nullptr);
+        if (rc != LIME_OK) {
+            std::cerr << "Error: " << (sink.write_failed ? lime_classify_error() : lime_last_error()) << std::endl;
+            lime_classification_writer_close(sink.w, 0);
+            lime_shutdown(ctx);
+            return 1;
+        }
+        std::cout << "numReads: " << numReads << " (" << n_batches << " batches of at most " << batch_reads << ")" << std::endl;
+        for (uint32_t k = 0; k < 2 * n_mates; ++k)
+            std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << sink.n_clusters[k] << " clusters summed over the batches, maximum length "
+                      << sink.max_len[k] << " in a batch." << std::endl;
+        clk.mark("batches: reads, collections, classification");
+        if (lime_classification_writer_close(sink.w, 1) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
+        clk.mark("output file");
+    } else {
+        std::vector<lime_verdict_t> verdicts(numReads ? numReads : 1);
+        lime_stats_t stats[4];
+        std::cerr << "Start comparing..." << std::endl;
+        if (lime_classify_sample_dev(ctx, n_mates, mates, gi, tx, alpha, norm, beta, EBWT, BIN, refs ? 0 : trlcp, verdicts.data(), counts, stats, nullptr) != LIME_OK) {
+            std::cerr << "Error: " << lime_last_error() << std::endl; exit(1);
+        }
+        for (uint32_t k = 0; k < 2 * n_mates; ++k)
+            std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << stats[k].n_clusters << " clusters, maximum length " << stats[k].max_len
+                      << "." << std::endl;
+        clk.mark("collections, classification");
+        if (lime_write_classification(output, verdicts.data(), (uint32_t)numReads) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
+        clk.mark("output file");
     }
-    for (uint32_t k = 0; k < 2 * n_mates; ++k)
-        std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << stats[k].n_clusters << " clusters, maximum length " << stats[k].max_len
-                  << "." << std::endl;
-    clk.mark("collections, classification");
-    if (lime_write_classification(output, verdicts.data(), numReads) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
-    clk.mark("output file");
     lime_shutdown(ctx);
     lime_taxonomy_free(tx);
     std::cout << "Classification process at level " << rank << " completed.\nNumber of successfully classified reads: "

@@ -165,6 +165,7 @@ extern "C" void lime_shutdown(lime_ctx *c)
     if (c->ev_xoff) (void)hipEventDestroy(c->ev_xoff);
     for (lime_lists *L : c->lists) delete L;
     for (lime_gindex *g : c->gidx) delete g;
+    for (lime_seq_reader *r : c->readers) delete r;
     for (lime_docs *d : c->docs) delete d;
     delete c;                                            // (the device buffers go with their owners: DevArr / DevWords, lime_ctx.h)
 }

@@ -17,6 +17,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
 #include <fstream>
 #include <iostream>
@@ -340,6 +341,50 @@ extern "C" int lime_write_classification(const char *path, const lime_verdict_t 
     out.close();
     if (out.fail()) { g_cls_err = std::string("Error writing ") + path; return LIME_ERR_IO; }
     return LIME_OK;
+}
+
+// ---- the classification file in parts ----
+struct lime_classification_writer {
+    std::ofstream out;
+    std::string path, tmp;
+};
+
+extern "C" int lime_classification_writer_open(const char *path, lime_classification_writer **out)
+{
+    if (!path || !out) { g_cls_err = "lime_classification_writer_open: NULL argument"; return LIME_ERR_ARG; }
+    *out = nullptr;
+    lime_classification_writer *w = new (std::nothrow) lime_classification_writer();
+    if (!w) { g_cls_err = "lime_classification_writer_open: out of host memory"; return LIME_ERR_NOMEM; }
+    w->path = path;
+    w->tmp = w->path + ".tmp" + std::to_string((long)getpid());
+    w->out.open(w->tmp);
+    if (!w->out.is_open()) { g_cls_err = "ERROR: File Output not Open"; delete w; return LIME_ERR_IO; }
+    w->out << "C/U/A/H,IdSeqRead,TaxID,maxSim\n";
+    *out = w;
+    return LIME_OK;
+}
+
+extern "C" int lime_classification_writer_append(lime_classification_writer *w, uint64_t first_read, const lime_verdict_t *verdicts, uint32_t n)
+{
+    if (!w || (n && !verdicts)) { g_cls_err = "lime_classification_writer_append: NULL argument"; return LIME_ERR_ARG; }
+    uint64_t counts[4] = {0, 0, 0, 0};
+    for (uint32_t r = 0; r < n; ++r) write_verdict(w->out, first_read + r, verdicts[r], counts);
+    if (w->out.fail()) { g_cls_err = std::string("Error writing ") + w->tmp; return LIME_ERR_IO; }
+    return LIME_OK;
+}
+
+extern "C" int lime_classification_writer_close(lime_classification_writer *w, int commit)
+{
+    if (!w) return LIME_OK;
+    w->out.close();
+    int rc = LIME_OK;
+    if (commit && (w->out.fail() || rename(w->tmp.c_str(), w->path.c_str()) != 0)) {
+        g_cls_err = std::string("Error writing ") + w->path;
+        rc = LIME_ERR_IO;
+    }
+    if (!commit || rc) (void)remove(w->tmp.c_str());
+    delete w;
+    return rc;
 }
 
 extern "C" int lime_classify_mem(uint32_t n_files, const uint8_t *const *row_max, const uint64_t *const *row_off,

@@ -1,5 +1,5 @@
 // lime_ctx.h -- what the host-side translation units of the library share (lime_api.cpp, lime_alloc.cpp, lime_pass.cpp, lime_stream.cpp,
-// lime_choose.cpp, lime_build.cpp, lime_merge.cpp, lime_docs.cpp, lime_comm.cpp): the context and the lists object, error reporting, the device-block helpers and the
+// lime_choose.cpp, lime_build.cpp, lime_merge.cpp, lime_docs.cpp, lime_reader.cpp, lime_comm.cpp): the context and the lists object, error reporting, the device-block helpers and the
 // declarations of the functions one file defines and another calls.  Internal: include/lime_hip.h is the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -174,6 +174,7 @@ struct __attribute__((visibility("hidden"))) lime_ctx {              // (hidden:
     std::vector<lime_lists *> lists;        // clusterChoose results left in HBM that are still alive (lime_lists_free / lime_shutdown)
     std::vector<lime_gindex *> gidx;        // genome indexes left in HBM that are still alive (lime_gindex_free / lime_shutdown)
     std::vector<lime_docs *> docs;          // document collections left in HBM that are still alive (lime_docs_free / lime_shutdown)
+    std::vector<lime_seq_reader *> readers; // open readers of reads files (lime_seq_reader_close / lime_shutdown)
 };
 
 // one collection's clusterChoose result in HBM: [row_off u64[n_reads + 1]][row_max u8[n_reads]] in one block, the pairs in another
@@ -219,6 +220,22 @@ struct __attribute__((visibility("hidden"))) lime_docs {
     lime_host::DevArr<uint64_t> doc_off;
 };
 
+// a reads file handed out in batches of records (lime_reader.cpp): the raw bytes win[start .. fill) of the file, which begin at a record
+// start (or are the file's first bytes), in a device window that is refilled through two pinned buffers and doubled where a batch does not fit
+struct __attribute__((visibility("hidden"))) lime_seq_reader {
+    lime_ctx *ctx = nullptr;
+    int format = 0;                         // 0 FASTA, 1 FASTQ
+    FILE *f = nullptr;                      // the source: a file ...
+    const uint8_t *host = nullptr;          // ... or the caller's bytes
+    uint64_t src_size = 0, src_pos = 0;     // the source's bytes, and how many of them have gone to the window
+    lime_host::DevArr<uint8_t> win;         // win.cap = the window size (+ 16 allocated)
+    uint64_t start = 0, fill = 0;
+    void *pin[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; size_t pin_bytes = 0; int pin_k = 0;
+    uint64_t n_records = 0, n_lines = 0, n_bytes = 0;      // handed out so far
+    int failed = 0; std::string failure;    // a refusal is final: later calls repeat it
+    ~lime_seq_reader();
+};
+
 namespace lime_host __attribute__((visibility("hidden"))) {
 inline int check_ctx(lime_ctx *c, const char *who)
 {
@@ -262,6 +279,9 @@ int score_dev_impl(lime_ctx *c, const uint32_t *d_da, const uint8_t *d_ebwt, uin
 // d_sa (may be NULL) receives the suffix array (u32[N]); `who` names the public call in error messages
 int build_index_impl(lime_ctx *c, const char *who, const uint8_t *d_text, const uint64_t *d_doc_off, uint32_t n_docs, uint64_t n_text,
                      uint8_t term, uint32_t lcp_cap, uint8_t *d_ebwt, uint32_t *d_lcp, uint32_t *d_da, uint32_t *d_sa, hipStream_t st);
+// lime_docs.cpp: the device parsers behind lime_docs_from_* on d_bytes[0 .. n), n < 2^32; line_base: the lines in front of d_bytes[0]
+int docs_parse_fasta_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out);
+int docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, uint64_t line_base, hipStream_t st, lime_docs **out);
 // lime_stream.cpp
 int score_in_chunks(lime_ctx *c, const uint32_t *da, const uint8_t *ebwt, uint64_t n,
                     const lime_cluster_t *clusters, uint64_t n_clusters, uint32_t n_reads, uint32_t n_refs,

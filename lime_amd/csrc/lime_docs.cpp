@@ -65,7 +65,7 @@ static int check_input_size(const char *who, uint64_t n)
 }
 
 // d_bytes[0 .. n) -> a handle; the parse's scratch (24 bytes per block of LIME_FASTA_BLOCK input bytes + rocPRIM's) goes back before this returns
-static int parse_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out)
+int lime_host::docs_parse_fasta_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out)
 {
     const uint32_t nb = (uint32_t)((n + LIME_FASTA_BLOCK - 1) / LIME_FASTA_BLOCK);
     uint32_t totals[2] = {0, 0};                         // kept bytes, header starts
@@ -115,8 +115,9 @@ static int parse_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint6
 }
 
 // the same for four-line FASTQ: 24 bytes per block + rocPRIM's + one error word.  The error word comes back with the copy the write pass
-// is waited for anyway: two synchronisations, like parse_dev
-static int parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out)
+// is waited for anyway: two synchronisations, like parse_dev.  line_base: the lines in front of d_bytes[0] (a batch of lime_seq_reader), added to
+// the line a refusal names
+int lime_host::docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, uint64_t line_base, hipStream_t st, lime_docs **out)
 {
     static const char *const reason[4] = {"record does not start with '@'", "separator line does not start with '+'",
                                           "quality length differs from sequence length", "truncated record"};
@@ -163,9 +164,18 @@ static int parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes,
         HIP_TRY(hipMemsetAsync(dg.d->doc_off.p, 0, 8, st));
     }
     HIP_TRY(hipStreamSynchronize(st));                   // (the scratch goes back when this returns)
-    if (err_word != ~0ull) return fail(LIME_ERR_ARG, "%s: line %llu: %s", who, (unsigned long long)(err_word >> 2), reason[err_word & 3u]);
+    if (err_word != ~0ull) return fail(LIME_ERR_ARG, "%s: line %llu: %s", who, (unsigned long long)((err_word >> 2) + line_base), reason[err_word & 3u]);
     *out = dg.take();
     return LIME_OK;
+}
+
+static int parse_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out)
+{
+    return docs_parse_fasta_dev(c, who, d_bytes, n, st, out);
+}
+static int parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out)
+{
+    return docs_parse_fastq_dev(c, who, d_bytes, n, 0, st, out);
 }
 
 typedef int (*ParseFn)(lime_ctx *, const char *, const uint8_t *, uint64_t, hipStream_t, lime_docs **);

@@ -102,6 +102,15 @@ void fq_launch_count(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint
 void fq_launch_write(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep, const uint32_t *off_diff,
                      uint32_t n_docs, uint8_t *text, uint64_t *doc_off, uint64_t *err, hipStream_t st);
 
+// ---- lime_seqcut_kernel.hip: where a window of a reads file is cut into whole records (lime_reader.cpp) ----
+// The same blocks; the markers and the rule are at the head of the kernel file.  cnt[k] = the line-first '>' of block k (FASTQ counts
+// its markers with fq_launch_lines)
+void sc_launch_headers(const uint8_t *b, uint64_t n, uint32_t n_blocks, uint32_t *cnt, hipStream_t st);
+// off = the exclusive sum of the counts over n_blocks + 1 entries (a 0 appended).  out[0 .. 3) = the cut, the records in front of it, the
+// window's markers: written by exactly one lane.  format: 0 FASTA, 1 FASTQ; n > 0
+void sc_launch_select(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *off, int format, uint32_t max_reads, int eof, uint64_t *out,
+                      hipStream_t st);
+
 // ---- lime_index_sort.hip: rocPRIM's device primitives.  temp == NULL: only *temp_bytes is set (the size to pass next time) ----
 struct IdxPairs { uint64_t *keys[2]; uint32_t *vals[2]; int cur; };       // double buffers; cur = which holds the data (updated by the sort)
 hipError_t idx_sort_pairs(void *temp, size_t *temp_bytes, IdxPairs *b, size_t m, unsigned begin_bit, unsigned end_bit, hipStream_t st);
