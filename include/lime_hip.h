@@ -414,6 +414,24 @@ int lime_fused_choose_lists(lime_ctx *ctx, const uint32_t *lcp, const uint32_t *
 int lime_lists_get(const lime_lists *lists, uint8_t *row_max, uint64_t *row_off, lime_pair_t **pairs, uint64_t *n_pairs);
 int lime_lists_info(const lime_lists *lists, uint32_t *n_reads, uint64_t *n_pairs, uint32_t *norm, float *beta);
 void lime_lists_free(lime_lists *lists);
+/* The lists of column shards of one table made into the whole table's list.  A table column depends on its genome and the reads and on no
+ * other genome, so P >= 1 parts -- lists over the same n_reads and norm, part p holding genomes id_base[p] ..
+ * id_base[p] + n_refs_part[p] - 1 of the whole table, each made with a beta every non-zero row passes (a negative one) -- hold all its
+ * non-zero cells.  What does not split is clusterChoose's test, `float(max) / norm > beta` with max over the WHOLE row: it is applied here,
+ * once, on the maximum over the parts, and a passing row lists all its parts' pairs (id_ref + id_base[p], sim unchanged; ascending idRef
+ * is kept).  *out is an ordinary lime_lists with the parts' norm and this beta; the parts stay the caller's.  A negative beta keeps every
+ * non-zero row, so acc = concat(acc, part) step by step, then one call with the single part acc and the real beta, equals the one-step
+ * call.  On the device: one pass over the rows, one 64-bit prefix sum, 8 bytes to the host (the total sizes the pairs' block), one pass
+ * that copies the pairs; no row comes to the host.  Device memory next to *out: 32 bytes per part + 8 per read + the prefix sum's,
+ * given back before the call returns.
+ * LIME_ERR_ARG, with text in lime_last_error() and before any launch: n_parts = 0, a NULL part or one of another context, parts of
+ * different n_reads or norm, id_base[p] < id_base[p - 1] + n_refs_part[p - 1] (not ascending, or id ranges that overlap), id_base[p] +
+ * n_refs_part[p] > 2^32 - 1.  On any error nothing stays allocated.  Synchronises `stream`. */
+int lime_lists_concat_dev(lime_ctx *ctx, uint32_t n_parts, const lime_lists *const *parts, const uint32_t *id_base,
+                          const uint32_t *n_refs_part, float beta, lime_lists **out, void *stream);
+/* the last lime_lists_concat_dev of the ctx: with lime_set_timing on, HIP-event ms of out[0] the pass over the rows (k_lc_rows), out[1] the
+ * prefix sum, out[2] the pass that copies the pairs (k_lc_copy); out[3] the pairs it wrote */
+int lime_get_concat_info(lime_ctx *ctx, double out[4]);
 
 /* The lineage file (';'-separated, a header line; Classify.cpp:32-85) at taxRank `rank` (0 = genome .. 6), with the higher ranks'
  * columns when higher != 0 (the HIGHER=1 build; needs rank >= 1).  Host only; the device copy is made by the first device
@@ -516,6 +534,13 @@ int lime_gindex_info(const lime_gindex *gi, uint32_t *n_docs, uint64_t *n_text, 
 /* the header and size checks of lime_gindex_load without a device (pure host code) */
 int lime_gindex_probe(const char *path, uint32_t *n_docs, uint64_t *n_text, uint32_t *lcp_cap, uint8_t *term);
 void lime_gindex_free(lime_gindex *gi);
+/* A genome collection cut into index shards (pure host code): greedy in order, a shard takes consecutive genomes while its positions
+ * (symbols + one terminator per genome) stay <= max_positions.  doc_off[n_docs + 1] as lime_gindex_build takes it; first_doc[0 ..
+ * *n_shards] receive the cuts (shard s = genomes first_doc[s] .. first_doc[s + 1] - 1; first_doc[*n_shards] = n_docs), `cap` is the
+ * number of entries first_doc holds.  No genome: *n_shards = 0.  LIME_ERR_ARG: a genome with more than max_positions positions (named
+ * in lime_last_error(); a genome is never cut), max_positions = 0, more than cap - 1 shards. */
+int lime_gindex_shard_plan(const uint64_t *doc_off, uint32_t n_docs, uint64_t max_positions, uint32_t *first_doc, uint32_t cap,
+                           uint32_t *n_shards);
 
 /* ebwt / lcp / da of the collection reads + genomes, bit for bit what lime_build_index[_dev] gives for it with the index's term and
  * the same lcp_cap, without sorting the genomes again: the reads are sorted alone (lime_build_index_dev's scratch, 52 bytes per READ
@@ -595,6 +620,22 @@ void lime_docs_free(lime_docs *docs);
 int lime_classify_sample_dev(lime_ctx *ctx, uint32_t n_mates, const lime_docs *const *mates, const lime_gindex *gi,
                              const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
                              uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream);
+/* The same against a genome database cut into n_shards >= 1 indexes of one ctx (lime_gindex_shard_plan; shard s holds the genomes that
+ * follow shard s - 1's, the taxonomy's order is their concatenation), all resident.  n_shards == 1 makes exactly the calls above.
+ * Otherwise, per collection: the reverse complement once; per shard lime_merge_index_dev and lime_fused_choose_lists_dev with beta -1
+ * (every non-zero row), the arrays given back before the next shard; lime_lists_concat_dev with the real beta; the shards' lists freed.
+ * Then lime_classify_lists_dev with n_targ = the shards' genomes in all.  The verdicts are those of one index over all the genomes.
+ * stats (may be NULL): n_shards * 2 * n_mates entries, shard-major (stats[s * 2 * n_mates + k]); they are PER-SHARD figures: a cluster
+ * with genomes of three shards counts three times.  A cluster longer than LIME_MAX_CLUSTER over all genomes may be shorter in every
+ * shard: sharding can succeed where the one index is LIME_ERR_MAXLEN, never the reverse.
+ * Peak device memory next to the read sets: lime_classify_sample_dev's for the largest shard, plus the other shards (14 bytes per
+ * genome position), plus one collection's unfiltered lists of all shards (8 bytes per non-zero cell + 9 per read and shard).
+ * Refusals before any launch, next to the ones above: n_shards = 0, a NULL shard or one of another context, shards built with different
+ * term or lcp_cap, a taxonomy whose n_targ is not the shards' genomes in all. */
+int lime_classify_sample_shards_dev(lime_ctx *ctx, uint32_t n_mates, const lime_docs *const *mates, uint32_t n_shards,
+                                    const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta,
+                                    int use_ebwt, int binary, uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4],
+                                    lime_stats_t *stats, void *stream);
 
 /* ---- a reads file in batches of records, and a sample of any size classified batch by batch ------------------------ *
  * A read's verdict depends on that read and the genomes and on no other read, so a sample cut into batches of reads, each merged into
@@ -659,6 +700,11 @@ int lime_classify_sample_stream(lime_ctx *ctx, uint32_t n_mates, lime_seq_reader
                                 const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
                                 uint32_t lcp_cap, uint32_t batch_reads, lime_verdict_sink sink, void *user, uint64_t counts[4],
                                 uint64_t *n_reads, uint64_t *n_batches, void *stream);
+/* The same with lime_classify_sample_shards_dev per batch; the sink's stats are the batch's n_shards * 2 * n_mates entries, shard-major. */
+int lime_classify_sample_stream_shards(lime_ctx *ctx, uint32_t n_mates, lime_seq_reader *const *readers, uint32_t n_shards,
+                                       const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta,
+                                       int use_ebwt, int binary, uint32_t lcp_cap, uint32_t batch_reads, lime_verdict_sink sink, void *user,
+                                       uint64_t counts[4], uint64_t *n_reads, uint64_t *n_batches, void *stream);
 
 /* The classification file in parts: open writes the header under a temporary name, append the lines of verdicts[0 .. n) with the read
  * ids first_read + i, close(commit != 0) renames the file to `path`, close(0) removes it.  Appending the parts of a verdict array gives

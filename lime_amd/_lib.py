@@ -116,6 +116,7 @@ SYMBOLS = {
     "lime_lists_get": (_i, [_vp, _vp, _vp, _pp, _pu64]),
     "lime_lists_info": (_i, [_vp, C.POINTER(_u32), _pu64, C.POINTER(_u32), C.POINTER(C.c_float)]),
     "lime_lists_free": (None, [_vp]),
+    "lime_lists_concat_dev": (_i, [_vp, _u32, _vp, _vp, _vp, C.c_float, _pp, _vp]),
     "lime_taxonomy_load": (_i, [C.c_char_p, _i, _i, _u32, _pp]),
     "lime_taxonomy_free": (None, [_vp]),
     "lime_classify_lists_dev": (_i, [_vp, _u32, _vp, _u32, _vp, _i, _vp, _vp, _vp]),
@@ -133,6 +134,8 @@ SYMBOLS = {
     "lime_gindex_info": (_i, [_vp, C.POINTER(_u32), _pu64, C.POINTER(_u32), C.POINTER(C.c_uint8)]),
     "lime_gindex_probe": (_i, [C.c_char_p, C.POINTER(_u32), _pu64, C.POINTER(_u32), C.POINTER(C.c_uint8)]),
     "lime_gindex_free": (None, [_vp]),
+    "lime_get_concat_info": (_i, [_vp, C.POINTER(C.c_double)]),
+    "lime_gindex_shard_plan": (_i, [_vp, _u32, _u64, _vp, _u32, C.POINTER(_u32)]),
     "lime_merge_size": (_u64, [_vp, _vp, _u32]),
     "lime_merge_index_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
     "lime_merge_index": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
@@ -153,6 +156,7 @@ SYMBOLS = {
     "lime_docs_get": (_i, [_vp, _vp, _vp]),
     "lime_docs_free": (None, [_vp]),
     "lime_classify_sample_dev": (_i, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, C.c_float, _i, _i, _u32, _vp, _vp, _vp, _vp]),
+    "lime_classify_sample_shards_dev": (_i, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, C.c_float, _i, _i, _u32, _vp, _vp, _vp, _vp]),
     "lime_seq_cut_dev": (_i, [_vp, _vp, _u64, _i, _u32, _i, _vp, _pu64, _pu64, _pu64]),
     "lime_seq_reader_open": (_i, [_vp, C.c_char_p, _u64, _pp]),
     "lime_seq_reader_open_bytes": (_i, [_vp, _vp, _u64, _i, _u64, _pp]),
@@ -160,6 +164,7 @@ SYMBOLS = {
     "lime_seq_reader_info": (_i, [_vp, C.POINTER(_i), _pu64, _pu64, _pu64, _pu64]),
     "lime_seq_reader_close": (None, [_vp]),
     "lime_classify_sample_stream": (_i, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, C.c_float, _i, _i, _u32, _u32, _vp, _vp, _vp, _pu64, _pu64, _vp]),
+    "lime_classify_sample_stream_shards": (_i, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, C.c_float, _i, _i, _u32, _u32, _vp, _vp, _vp, _pu64, _pu64, _vp]),
     "lime_classification_writer_open": (_i, [C.c_char_p, _pp]),
     "lime_classification_writer_append": (_i, [_vp, _u64, _vp, _u32]),
     "lime_classification_writer_close": (_i, [_vp, _i]),

@@ -202,6 +202,26 @@ class Context:
                                                n, n_reads, n_refs, alpha, norm, beta, C.byref(h), C.byref(s)))
         return self._lists_of(h), s
 
+    def lists_concat(self, parts, id_base, n_refs_part, beta, stream=None):
+        """the Lists of column shards of one table (each made with a negative beta: every non-zero row) made into the whole table's Lists:
+        part p holds the genomes id_base[p] .. id_base[p] + n_refs_part[p] - 1, clusterChoose's test is taken on the maximum over the parts
+        (lime_lists_concat_dev).  The parts stay the caller's -> Lists"""
+        k = len(parts)
+        hs = (C.c_void_p * max(k, 1))(*[None if li is None else li.h for li in parts])
+        base = np.ascontiguousarray(id_base, dtype=np.uint32)
+        cnt = np.ascontiguousarray(n_refs_part, dtype=np.uint32)
+        if len(base) != k or len(cnt) != k:
+            raise ValueError("lists_concat: one id_base and one n_refs_part per part")
+        h = C.c_void_p()
+        check(self.lib.lime_lists_concat_dev(self.h, k, hs, base.ctypes.data if k else None, cnt.ctypes.data if k else None, float(beta), C.byref(h), stream))
+        return self._lists_of(h)
+
+    def concat_info(self):
+        """the last lists_concat of this context (lime_get_concat_info); the ms need set_timing(True)"""
+        v = (C.c_double * 4)()
+        check(self.lib.lime_get_concat_info(self.h, v))
+        return {"rows_ms": v[0], "scan_ms": v[1], "copy_ms": v[2], "pairs": int(v[3])}
+
     def classify_lists_dev(self, lists, n_targ, taxonomy, binary=True, stream=None):
         """Classify over 2 or 4 Lists of this ctx -> (verdicts: numpy VERDICT[n_reads], counts {C, U, A, H} as a list)"""
         hs = (C.c_void_p * len(lists))(*[li.h for li in lists])
@@ -450,6 +470,20 @@ class Context:
                                                 int(bool(binary)), int(lcp_cap), v.ctypes.data, counts, st, stream))
         return v[:n_reads], list(counts), [st[i] for i in range(2 * k)]
 
+    def classify_sample_shards(self, mates, shards, taxonomy, alpha, norm, beta, ebwt=True, binary=True, lcp_cap=0, stream=None):
+        """classify_sample against a genome database cut into GenomeIndex shards, in genome order (lime_classify_sample_shards_dev)
+        -> (verdicts, counts, stats: one Stats per shard and collection, shard-major: stats[s * 2 * len(mates) + k])"""
+        k, ns = len(mates), len(shards)
+        hs = (C.c_void_p * max(k, 1))(*[m.h for m in mates])
+        gs = (C.c_void_p * max(ns, 1))(*[None if g is None else g.h for g in shards])
+        n_reads = mates[0].info()[0] if k and mates[0].h else 0
+        v = np.zeros(max(n_reads, 1), dtype=VERDICT)
+        counts = (C.c_uint64 * 4)()
+        st = (Stats * (4 * max(ns, 1)))()
+        check(self.lib.lime_classify_sample_shards_dev(self.h, k, hs, ns, gs, taxonomy.h, int(alpha), int(norm) & 0xFFFFFFFF, float(beta), int(bool(ebwt)),
+                                                       int(bool(binary)), int(lcp_cap), v.ctypes.data, counts, st, stream))
+        return v[:n_reads], list(counts), [st[i] for i in range(ns * 2 * k)]
+
     # ---- a reads file in batches of records, a sample of any size batch by batch (include/lime_hip.h: lime_seq_reader) ----
     def seq_cut_dev(self, bytes_t, fmt, max_reads, eof, n=None, stream=None):
         """where a window of a reads file (a torch uint8 device tensor, a view at any alignment) is cut so that whole records stand in front
@@ -480,18 +514,22 @@ class Context:
         return self._reader_of(h, a)
 
     def classify_sample_stream(self, readers, gi, taxonomy, alpha, norm, beta, batch_reads, ebwt=True, binary=True, lcp_cap=0, sink=None, stream=None):
-        """classify_sample batch by batch over 1 or 2 SeqReaders (lime_classify_sample_stream).  sink(first_read, verdicts, stats) is called
+        """classify_sample batch by batch over 1 or 2 SeqReaders (lime_classify_sample_stream).  gi: a GenomeIndex, or a list of them: the
+        shards of one genome database in genome order (lime_classify_sample_stream_shards; the Stats are then per shard and collection,
+        shard-major).  sink(first_read, verdicts, stats) is called
         per batch with a VERDICT array that is only valid during the call and the batch's Stats; a non-zero return ends the call (LimeError
         with that code).  Without a sink -> (verdicts of all reads, counts {C, U, A, H}, [per-batch list of Stats]); with one ->
         (n_reads, counts, n_batches)"""
         k = len(readers)
         hs = (C.c_void_p * max(k, 1))(*[r.h for r in readers])
         parts, per_batch, raised = [], [], []
+        shards = list(gi) if isinstance(gi, (list, tuple)) else None
+        n_stats = 2 * k * (len(shards) if shards is not None else 1)
 
         def cb(_user, first_read, pv, n, pst):
             try:
                 v = np.ctypeslib.as_array(C.cast(pv, C.POINTER(C.c_uint8)), shape=(n * VERDICT.itemsize,)).view(VERDICT)
-                st = [Stats.from_buffer_copy(pst[i]) for i in range(2 * k)]
+                st = [Stats.from_buffer_copy(pst[i]) for i in range(n_stats)]
                 if sink is None:
                     parts.append(v.copy()); per_batch.append(st)
                     return 0
@@ -502,9 +540,15 @@ class Context:
         fn = _lib.VERDICT_SINK(cb)
         counts = (C.c_uint64 * 4)()
         n_reads, n_batches = C.c_uint64(0), C.c_uint64(0)
-        rc = self.lib.lime_classify_sample_stream(self.h, k, hs, gi.h, taxonomy.h, int(alpha), int(norm) & 0xFFFFFFFF, float(beta), int(bool(ebwt)),
-                                                  int(bool(binary)), int(lcp_cap), int(batch_reads), C.cast(fn, C.c_void_p), None, counts, C.byref(n_reads), C.byref(n_batches),
-                                                  stream)
+        if shards is not None:
+            gs = (C.c_void_p * max(len(shards), 1))(*[None if g is None else g.h for g in shards])
+            rc = self.lib.lime_classify_sample_stream_shards(self.h, k, hs, len(shards), gs, taxonomy.h, int(alpha), int(norm) & 0xFFFFFFFF, float(beta),
+                                                             int(bool(ebwt)), int(bool(binary)), int(lcp_cap), int(batch_reads), C.cast(fn, C.c_void_p), None, counts,
+                                                             C.byref(n_reads), C.byref(n_batches), stream)
+        else:
+            rc = self.lib.lime_classify_sample_stream(self.h, k, hs, gi.h, taxonomy.h, int(alpha), int(norm) & 0xFFFFFFFF, float(beta), int(bool(ebwt)),
+                                                      int(bool(binary)), int(lcp_cap), int(batch_reads), C.cast(fn, C.c_void_p), None, counts, C.byref(n_reads), C.byref(n_batches),
+                                                      stream)
         if raised:
             raise raised[0]
         if rc > 0:
@@ -799,6 +843,18 @@ def gindex_probe(path):
     return {"n_docs": int(nd.value), "n_text": int(nt.value), "lcp_cap": int(cap.value), "term": int(term.value)}
 
 
+def gindex_shard_plan(doc_off, max_positions):
+    """a genome collection cut into index shards (lime_gindex_shard_plan; no device): doc_off[n_docs + 1] the genomes' starts in their
+    text -> the cuts [first genome of shard 0, of shard 1, ..., n_docs]: consecutive genomes while a shard's positions (symbols + one
+    terminator per genome) stay <= max_positions.  LimeError for a genome above the budget"""
+    off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    n_docs = len(off) - 1
+    first = np.zeros(n_docs + 2, dtype=np.uint32)
+    ns = C.c_uint32(0)
+    check(_lib.load().lime_gindex_shard_plan(off.ctypes.data, n_docs, int(max_positions), first.ctypes.data, len(first), C.byref(ns)))
+    return [int(x) for x in first[:ns.value + 1]]
+
+
 def index_size(doc_off):
     off = np.ascontiguousarray(doc_off, dtype=np.uint64)
     return int(_lib.load().lime_index_size(off.ctypes.data, len(off) - 1))
@@ -924,7 +980,8 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
     [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta: the files are parsed on the device (each reads file
     FASTA or four-line FASTQ, by its first byte; refs FASTA), the
-    genome index is built there (refs) or loaded (gidx), only `output` is written.  batch_reads > 0: `--batch-reads N [--window-bytes W]`,
+    genome index is built there (refs) or loaded (gidx: a file, or a list of files, the index shards of one database in genome order:
+    repeated `--gidx`), only `output` is written.  batch_reads > 0: `--batch-reads N [--window-bytes W]`,
     the sample read and classified N reads at a time, `output` appended to batch by batch and renamed at the end.  -> counts {C, U, A, H}"""
     reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
     if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
@@ -946,18 +1003,28 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
             check(ctx.lib.lime_gindex_build_dev(ctx.h, pt, po, nd, nt, 0, int(trlcp), None, C.byref(h)))
             gi = ctx._gindex_of(h)
             g.close()
+        elif isinstance(gidx, (list, tuple)):                       # the shards of one genome database, in genome order
+            for g in gidx:
+                p = gindex_probe(g)
+                if (p["lcp_cap"], p["term"]) != (gindex_probe(gidx[0])["lcp_cap"], gindex_probe(gidx[0])["term"]):
+                    raise ValueError(f"LiME_fasta: {g} and {gidx[0]} were built with different lcp_cap or terminators")
+            gi = [ctx.load_genome_index(g) for g in gidx]
         else:
             gi = ctx.load_genome_index(gidx)
-        tx = Taxonomy(lineage, rank, higher, gi.info()["n_docs"])
+        shards = gi if isinstance(gi, list) else [gi]
+        tx = Taxonomy(lineage, rank, higher, sum(g.info()["n_docs"] for g in shards))
         if batch_reads:
             with ClassificationWriter(output) as w:
                 _, counts, _ = ctx.classify_sample_stream(mates, gi, tx, alpha, norm, float(np.float32(beta)), batch_reads, ebwt, binary,
                                                           0 if refs is not None else trlcp, sink=lambda first, v, st: w.append(first, v))
+        elif isinstance(gi, list):
+            v, counts, _ = ctx.classify_sample_shards(mates, gi, tx, alpha, norm, float(np.float32(beta)), ebwt, binary, trlcp)
         else:
             v, counts, _ = ctx.classify_sample(mates, gi, tx, alpha, norm, float(np.float32(beta)), ebwt, binary, 0 if refs is not None else trlcp)
         for d in mates:
             d.close()
-        gi.close()
+        for g in shards:
+            g.close()
     finally:
         if own:
             ctx.close()

@@ -8,7 +8,13 @@
 // The genome database indexed once and every read set merged into it (the script's eGSA once, eGap four times):
 //   BuildIndex --refs refs.fasta outBase [--trlcp k]               writes outBase.gidx (lime_gindex_build / _save), prints numGenomes
 //   BuildIndex reads.fasta --gidx file.gidx outBase [--rc] [--trlcp k]   the one-step form's three files and output (lime_merge_index)
+// A genome database of any size, cut into index shards (lime_gindex_shard_plan: consecutive genomes while a shard's positions, symbols +
+// one terminator per genome, stay <= P; a genome is never cut):
+//   BuildIndex --refs refs.fasta outBase --shard-positions P [--trlcp k]   writes outBase.000.gidx, outBase.001.gidx, ... and prints each
+// name with its genomes and positions.  The file is read on the host and the shards are built and saved one at a time, so device memory
+// holds one shard and refs.fasta may hold more than 2^32 - 1 positions.  LiME_fasta takes the shards with one --gidx each, in this order.
 #include <string.h>
+#include <algorithm>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -36,7 +42,8 @@ static int read_reads(const char *path, int rc_reads, uint8_t **text, uint64_t *
 }
 
 // the two forms around a genome index file: refs.fasta -> outBase.gidx, and reads.fasta + file.gidx -> the three files
-static int two_step(CliClock &clk, bool refs_only, const char *gidx, const char *fasta, const std::string &base, int rc_reads, unsigned trlcp)
+static int two_step(CliClock &clk, bool refs_only, const char *gidx, const char *fasta, const std::string &base, int rc_reads, unsigned trlcp,
+                    unsigned long long shard_positions)
 {
     uint8_t *text = nullptr;
     uint64_t *off = nullptr;
@@ -53,6 +60,31 @@ static int two_step(CliClock &clk, bool refs_only, const char *gidx, const char 
     if (lime_init(pick_device(), &ctx) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(EXIT_FAILURE); }
     clk.mark("lime_init (HIP runtime)");
     lime_gindex *gi = nullptr;
+    if (refs_only && shard_positions) {
+        std::vector<uint32_t> first((size_t)nd + 2);
+        uint32_t n_shards = 0;
+        if (lime_gindex_shard_plan(off, nd, shard_positions, first.data(), (uint32_t)std::min<uint64_t>((uint64_t)nd + 2, 0xFFFFFFFFull), &n_shards) != LIME_OK) {
+            std::cerr << "Error: " << lime_last_error() << std::endl; return 1;
+        }
+        std::cout << "numGenomes: " << nd << "\nsymbols: " << off[nd] + nd << "\nshards: " << n_shards << std::endl;
+        for (uint32_t s = 0; s < n_shards; ++s) {                       // one shard at a time on the device
+            const uint32_t d0 = first[s], cnt = first[s + 1] - d0;
+            std::vector<uint64_t> soff((size_t)cnt + 1);
+            for (uint32_t k = 0; k <= cnt; ++k) soff[k] = off[d0 + k] - off[d0];
+            char num[16];
+            snprintf(num, sizeof num, ".%03u", s);
+            const std::string name = base + num + ".gidx";
+            if (lime_gindex_build(ctx, text + off[d0], soff.data(), cnt, 0, trlcp, &gi) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
+            if (lime_gindex_save(gi, name.c_str()) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; return -LIME_ERR_IO; }
+            lime_gindex_free(gi);
+            gi = nullptr;
+            std::cout << name << ": " << cnt << " genomes, " << soff[cnt] + cnt << " positions" << std::endl;
+        }
+        clk.mark("index shards");
+        lime_shutdown(ctx);
+        lime_free(text); lime_free(off);
+        return 0;
+    }
     if (refs_only) {
         if (lime_gindex_build(ctx, text, off, nd, 0, trlcp, &gi) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
         clk.mark("index");
@@ -92,15 +124,18 @@ int main(int argc, char **argv)
     std::vector<const char *> pos;
     int rc_reads = 0;
     unsigned trlcp = 0;
-    bool bad = false, refs_only = false;
+    unsigned long long shard_positions = 0;
+    bool bad = false, refs_only = false, sharded = false;
     const char *gidx = nullptr;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--rc")) rc_reads = 1;
         else if (!strcmp(argv[i], "--refs")) refs_only = true;
         else if (!strcmp(argv[i], "--gidx")) { if (i + 1 < argc) gidx = argv[++i]; else bad = true; }
         else if (!strcmp(argv[i], "--trlcp")) { if (i + 1 < argc && sscanf(argv[i + 1], "%u", &trlcp) == 1) ++i; else bad = true; }
+        else if (!strcmp(argv[i], "--shard-positions")) { if (i + 1 < argc && sscanf(argv[i + 1], "%llu", &shard_positions) == 1 && shard_positions) { ++i; sharded = true; } else bad = true; }
         else pos.push_back(argv[i]);
     }
+    if (sharded && !refs_only) bad = true;
     if ((refs_only && (gidx || rc_reads)) || pos.size() != ((refs_only || gidx) ? 2u : 3u)) bad = true;
     if (bad) {
         std::cerr << "Error usage " << argv[0] << " reads.fasta refs.fasta outBase [--rc] [--trlcp k]\n"
@@ -108,11 +143,14 @@ int main(int argc, char **argv)
                   << "  --trlcp k: lcp values truncated at k.  reads.fasta may be four-line FASTQ (first byte '@'); refs.fasta is FASTA.\n"
                   << "or " << argv[0] << " --refs refs.fasta outBase [--trlcp k]\n"
                   << "  writes outBase.gidx, the index of the genomes alone;\n"
+                  << "or " << argv[0] << " --refs refs.fasta outBase --shard-positions P [--trlcp k]\n"
+                  << "  writes outBase.000.gidx, outBase.001.gidx, ...: consecutive genomes while a shard's positions (symbols + one terminator\n"
+                  << "  per genome) stay <= P, built one at a time (LiME_fasta takes them with one --gidx each, in this order);\n"
                   << "or " << argv[0] << " reads.fasta --gidx file.gidx outBase [--rc] [--trlcp k]\n"
                   << "  writes the three files from the reads and a genome index (--trlcp: at most the index's)." << std::endl;
         exit(1);
     }
-    if (refs_only || gidx) return two_step(clk, refs_only, gidx, pos[0], pos[1], rc_reads, trlcp);
+    if (refs_only || gidx) return two_step(clk, refs_only, gidx, pos[0], pos[1], rc_reads, trlcp, shard_positions);
     const std::string base = pos[2];
     uint8_t *text[2] = {nullptr, nullptr};
     uint64_t *off[2] = {nullptr, nullptr};

@@ -12,6 +12,12 @@
 // lines are appended to `output`, which is written under a temporary name and renamed at the end: a failure half-way leaves no output
 // file.  The verdicts are those of the whole sample; the cluster count and the maximum length printed per collection are PER-BATCH
 // figures (the count summed over the batches, the largest of the batches' maxima): a cluster with reads of three batches counts three times.
+// --gidx a.gidx --gidx b.gidx ...: a genome database cut into index shards (BuildIndex --refs --shard-positions), in genome order: the
+// lineage file's order is the concatenation.  All files are probed (lime_gindex_probe) before a device is opened: shards built with
+// different --trlcp or terminators, and a lineage file of another genome count, are refused with a text.  All shards are loaded; per
+// collection every shard is merged and scanned on its own and the shards' lists are made into the whole row's on the device
+// (lime_classify_sample_shards_dev / lime_classify_sample_stream_shards).  The verdicts are those of one index; the clusters and the
+// maximum length printed per collection are PER-SHARD figures in the same way (summed / the largest over the shards).
 // The defaults are the script's constants (LiME_paired.sh:21-23); norm = readLen + 1 - alpha (ClusterBWT_DA.cpp:555).  The reference's
 // compile-time switches are environment variables, as for the other drop-ins: LIME_EBWT (default 1), LIME_BIN (default 1), LIME_HIGHER (0).
 #include <string.h>
@@ -32,16 +38,19 @@ namespace {
 struct BatchSink {                             // --batch-reads: the writer and the collections' counters over the batches
     lime_classification_writer *w = nullptr;
     uint32_t n_coll = 0;
+    uint32_t n_shards = 1;
     uint64_t n_clusters[4] = {0, 0, 0, 0}, max_len[4] = {0, 0, 0, 0};
     bool write_failed = false;                 // the call ended with the writer's error: its text is in lime_classify_error
 };
 int batch_sink(void *user, uint64_t first_read, const lime_verdict_t *verdicts, uint32_t n, const lime_stats_t *stats)
 {
     BatchSink *s = static_cast<BatchSink *>(user);
-    for (uint32_t k = 0; k < s->n_coll; ++k) {
-        s->n_clusters[k] += stats[k].n_clusters;
-        if (stats[k].max_len > s->max_len[k]) s->max_len[k] = stats[k].max_len;
-    }
+    for (uint32_t sh = 0; sh < s->n_shards; ++sh)
+        for (uint32_t k = 0; k < s->n_coll; ++k) {
+            const lime_stats_t &x = stats[(size_t)sh * s->n_coll + k];
+            s->n_clusters[k] += x.n_clusters;
+            if (x.max_len > s->max_len[k]) s->max_len[k] = x.max_len;
+        }
     const int rc = lime_classification_writer_append(s->w, first_read, verdicts, n);
     s->write_failed = rc != LIME_OK;
     return rc;
@@ -53,7 +62,8 @@ int main(int argc, char **argv)
     CliClock clk;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<const char *> reads;
-    const char *refs = nullptr, *gidx = nullptr, *lineage = nullptr, *output = nullptr;
+    std::vector<const char *> gidx;
+    const char *refs = nullptr, *lineage = nullptr, *output = nullptr;
     unsigned alpha = 16, rank = 1, trlcp = 0, batch_reads = 0;
     unsigned long long window_bytes = 0;
     bool batched = false, have_window = false;
@@ -63,7 +73,7 @@ int main(int argc, char **argv)
     for (int i = 1; i < argc; ++i) {
         const bool more = i + 1 < argc;
         if (!strcmp(argv[i], "--refs")) { if (more) refs = argv[++i]; else bad = true; }
-        else if (!strcmp(argv[i], "--gidx")) { if (more) gidx = argv[++i]; else bad = true; }
+        else if (!strcmp(argv[i], "--gidx")) { if (more) gidx.push_back(argv[++i]); else bad = true; }
         else if (!strcmp(argv[i], "--lineage")) { if (more) lineage = argv[++i]; else bad = true; }
         else if (!strcmp(argv[i], "--out")) { if (more) output = argv[++i]; else bad = true; }
         else if (!strcmp(argv[i], "--readlen")) { if (more && sscanf(argv[i + 1], "%hhu", &readLen) == 1) { ++i; have_len = true; } else bad = true; }
@@ -76,9 +86,9 @@ int main(int argc, char **argv)
         else reads.push_back(argv[i]);
     }
     if (have_window && !batched) bad = true;
-    if (reads.empty() || reads.size() > 2 || !refs == !gidx || !lineage || !output || !have_len) bad = true;
+    if (reads.empty() || reads.size() > 2 || !refs == gidx.empty() || !lineage || !output || !have_len) bad = true;
     if (bad) {
-        std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output\n"
+        std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx [--gidx next.gidx ...]) --lineage LineageFile --readlen L --out output\n"
                   << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]]\n"
                   << "  classifies the reads of one sample (one file: single-end, two: paired-end) against the genomes of refs.fasta, or of an\n"
                   << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  A reads file is FASTA or\n"
@@ -86,12 +96,38 @@ int main(int argc, char **argv)
                   << "  truncated at k.  --batch-reads N: a sample of any size, read and classified N reads at a time (through a window of W\n"
                   << "  bytes per file); the verdicts are the whole sample's, the clusters and maximum length printed per collection are\n"
                   << "  per-batch figures (summed / the largest over the batches: a cluster with reads of three batches counts three times).\n"
+                  << "  --gidx given several times: the index shards of one genome database (BuildIndex --refs --shard-positions), in genome\n"
+                  << "  order (the lineage file's order); the verdicts are those of one index, the clusters and maximum length printed per\n"
+                  << "  collection are per-shard figures in the same way (summed / the largest over the shards).\n"
                   << "  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
     const int EBWT = env_flag("LIME_EBWT", 1), BIN = env_flag("LIME_BIN", 1), HIGHER = env_flag("LIME_HIGHER", 0);
     const uint32_t norm = (uint32_t)(readLen + 1 - alpha);        // ClusterBWT_DA.cpp:555
     const uint32_t n_mates = (uint32_t)reads.size();
+    const uint32_t n_shards = refs ? 1u : (uint32_t)gidx.size();
+    if (n_shards > 1) {                        // the shards must agree and the lineage must hold their genomes: known before a device is opened
+        uint64_t total = 0;
+        uint32_t cap0 = 0; uint8_t term0 = 0;
+        for (uint32_t s = 0; s < n_shards; ++s) {
+            uint32_t nd = 0, cap = 0; uint8_t term = 0;
+            if (lime_gindex_probe(gidx[s], &nd, nullptr, &cap, &term) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
+            if (s == 0) { cap0 = cap; term0 = term; }
+            else if (cap != cap0 || term != term0) {
+                std::cerr << "Error: " << gidx[s] << " was built with --trlcp " << cap << " and terminator " << (unsigned)term << ", " << gidx[0] << " with --trlcp "
+                          << cap0 << " and terminator " << (unsigned)term0 << ": the shards of one database are built alike." << std::endl;
+                exit(1);
+            }
+            total += nd;
+        }
+        if (total > 0xFFFFFFFFull) { std::cerr << "Error: the index shards hold " << total << " genomes; ids are 32 bits." << std::endl; exit(1); }
+        lime_taxonomy *probe = nullptr;
+        if (lime_taxonomy_load(lineage, (int)rank, env_flag("LIME_HIGHER", 0), (uint32_t)total, &probe) != LIME_OK) {
+            std::cerr << "Error: " << lineage << " does not describe the " << total << " genomes of the " << n_shards << " index shards: " << lime_classify_error() << std::endl;
+            exit(1);
+        }
+        lime_taxonomy_free(probe);
+    }
 
     lime_ctx *ctx = nullptr;
     if (lime_init(pick_device(), &ctx) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(EXIT_FAILURE); }
@@ -110,6 +146,7 @@ int main(int argc, char **argv)
     if (!batched) { uint32_t nd = 0; lime_docs_info(mates[0], &nd, nullptr); numReads = nd; }
     clk.mark(batched ? "readers" : "reads (parsed on the device)");
     lime_gindex *gi = nullptr;
+    std::vector<lime_gindex *> shards;
     if (refs) {
         lime_docs *g = nullptr;
         const int rc = lime_docs_from_fasta(ctx, refs, &g);
@@ -120,11 +157,16 @@ int main(int argc, char **argv)
         lime_docs_device(g, &d_text, &d_off);
         if (lime_gindex_build_dev(ctx, d_text, d_off, nd, nt, 0, trlcp, nullptr, &gi) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
         lime_docs_free(g);
-    } else if (lime_gindex_load(ctx, gidx, &gi) != LIME_OK) {
-        std::cerr << "Error: " << lime_last_error() << std::endl; exit(1);
+    } else {
+        for (uint32_t s = 0; s < n_shards; ++s) {
+            if (lime_gindex_load(ctx, gidx[s], &gi) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
+            shards.push_back(gi);
+        }
+        gi = shards[0];
     }
+    if (shards.empty()) shards.push_back(gi);
     uint32_t numTarg = 0;
-    lime_gindex_info(gi, &numTarg, nullptr, nullptr, nullptr);
+    for (lime_gindex *x : shards) { uint32_t nd = 0; lime_gindex_info(x, &nd, nullptr, nullptr, nullptr); numTarg += nd; }
     clk.mark("genome index");
     if (batched) std::cout << "numGenomes: " << numTarg << std::endl;        // (numReads is known after the last batch)
     else std::cout << "numReads: " << numReads << "\nnumGenomes: " << numTarg << std::endl;
@@ -135,12 +177,14 @@ int main(int argc, char **argv)
     uint64_t counts[4] = {0, 0, 0, 0};
     if (batched) {
         BatchSink sink;
-        sink.n_coll = 2 * n_mates;
+        sink.n_coll = 2 * n_mates; sink.n_shards = n_shards;
         if (lime_classification_writer_open(output, &sink.w) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
         std::cerr << "Start comparing..." << std::endl;
         uint64_t n_batches = 0;
-        const int rc = lime_classify_sample_stream(ctx, n_mates, readers, gi, tx, alpha, norm, beta, EBWT, BIN, refs ? 0 : trlcp, batch_reads, batch_sink, &sink,
-                                                   counts, &numReads, &n_batches, nullptr);
+        const int rc = n_shards == 1 ? lime_classify_sample_stream(ctx, n_mates, readers, gi, tx, alpha, norm, beta, EBWT, BIN, refs ? 0 : trlcp, batch_reads, batch_sink,
+                                                                   &sink, counts, &numReads, &n_batches, nullptr)
+                                     : lime_classify_sample_stream_shards(ctx, n_mates, readers, n_shards, shards.data(), tx, alpha, norm, beta, EBWT, BIN, trlcp,
+                                                                          batch_reads, batch_sink, &sink, counts, &numReads, &n_batches, nullptr);
         if (rc != LIME_OK) {
             std::cerr << "Error: " << (sink.write_failed ? lime_classify_error() : lime_last_error()) << std::endl;
             lime_classification_writer_close(sink.w, 0);
@@ -149,21 +193,29 @@ int main(int argc, char **argv)
         }
         std::cout << "numReads: " << numReads << " (" << n_batches << " batches of at most " << batch_reads << ")" << std::endl;
         for (uint32_t k = 0; k < 2 * n_mates; ++k)
-            std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << sink.n_clusters[k] << " clusters summed over the batches, maximum length "
-                      << sink.max_len[k] << " in a batch." << std::endl;
+            std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << sink.n_clusters[k] << " clusters summed over the batches"
+                      << (n_shards > 1 ? " and shards" : "") << ", maximum length " << sink.max_len[k] << " in a batch" << (n_shards > 1 ? " and shard" : "") << "." << std::endl;
         clk.mark("batches: reads, collections, classification");
         if (lime_classification_writer_close(sink.w, 1) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
         clk.mark("output file");
     } else {
         std::vector<lime_verdict_t> verdicts(numReads ? numReads : 1);
-        lime_stats_t stats[4];
+        std::vector<lime_stats_t> stats((size_t)n_shards * 4);
         std::cerr << "Start comparing..." << std::endl;
-        if (lime_classify_sample_dev(ctx, n_mates, mates, gi, tx, alpha, norm, beta, EBWT, BIN, refs ? 0 : trlcp, verdicts.data(), counts, stats, nullptr) != LIME_OK) {
-            std::cerr << "Error: " << lime_last_error() << std::endl; exit(1);
+        const int rc = n_shards == 1 ? lime_classify_sample_dev(ctx, n_mates, mates, gi, tx, alpha, norm, beta, EBWT, BIN, refs ? 0 : trlcp, verdicts.data(), counts,
+                                                                stats.data(), nullptr)
+                                     : lime_classify_sample_shards_dev(ctx, n_mates, mates, n_shards, shards.data(), tx, alpha, norm, beta, EBWT, BIN, trlcp, verdicts.data(),
+                                                                       counts, stats.data(), nullptr);
+        if (rc != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
+        for (uint32_t k = 0; k < 2 * n_mates; ++k) {
+            uint64_t nc = 0, ml = 0;
+            for (uint32_t s = 0; s < n_shards; ++s) { const lime_stats_t &x = stats[(size_t)s * 2 * n_mates + k]; nc += x.n_clusters; if (x.max_len > ml) ml = x.max_len; }
+            if (n_shards == 1)
+                std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << nc << " clusters, maximum length " << ml << "." << std::endl;
+            else
+                std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << nc << " clusters summed over the shards, maximum length " << ml
+                          << " in a shard." << std::endl;
         }
-        for (uint32_t k = 0; k < 2 * n_mates; ++k)
-            std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << stats[k].n_clusters << " clusters, maximum length " << stats[k].max_len
-                      << "." << std::endl;
         clk.mark("collections, classification");
         if (lime_write_classification(output, verdicts.data(), (uint32_t)numReads) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
         clk.mark("output file");

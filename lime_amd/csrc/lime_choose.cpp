@@ -1,15 +1,17 @@
 // lime_choose.cpp -- clusterChoose and what follows it: the ctx's choose scratch, the lists objects left in HBM (lime_lists), the fused
-// scan + choose with and without the table, Classify on the device and the taxonomy's device copy, and the calls that score a host
+// scan + choose with and without the table, the lists of genome shards made into one (lime_lists_concat_dev), Classify on the device and the taxonomy's device copy, and the calls that score a host
 // cluster list and choose in one go (lime_score_choose, on several GPUs lime_score_choose_multi).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdlib.h>
 #include <string.h>
 #include <mutex>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "lime_index.h"
 #include "lime_classify.h"
 #include "lime_ctx.h"
 
@@ -302,6 +304,112 @@ extern "C" void lime_lists_free(lime_lists *L)
     (void)hipSetDevice(L->ctx->device);
     lists_release(L);
     (void)hipSetDevice(cur);
+}
+
+// ---- lists of column shards of one table made into the whole table's list (lime_listcat_kernel.hip) ------------------------------
+// A table column depends on its genome and the reads alone, so the lists of genome shards, each made with a
+// test every non-zero row passes, hold the whole table's non-zero cells; clusterChoose's test is applied here once, on the maximum over
+// the parts.  Passes: k_lc_rows (maxima and lengths), one 64-bit prefix sum, the total (8 bytes) to the host, k_lc_copy.
+extern "C" int lime_lists_concat_dev(lime_ctx *c, uint32_t n_parts, const lime_lists *const *parts, const uint32_t *id_base,
+                                     const uint32_t *n_refs_part, float beta, lime_lists **out, void *stream)
+{
+    const char *who = "lime_lists_concat_dev";
+    if (!c) return fail(LIME_ERR_ARG, "%s: ctx is NULL", who);
+    if (!out) return fail(LIME_ERR_ARG, "%s: NULL output", who);
+    *out = nullptr;
+    if (!n_parts) return fail(LIME_ERR_ARG, "%s: n_parts is 0", who);
+    if (!parts || !id_base || !n_refs_part) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        if (!parts[p]) return fail(LIME_ERR_ARG, "%s: part %u is NULL", who, p);
+        if (parts[p]->ctx != c) return fail(LIME_ERR_ARG, "%s: part %u belongs to another context", who, p);
+        if (parts[p]->n_reads != parts[0]->n_reads)
+            return fail(LIME_ERR_ARG, "%s: the parts hold different numbers of reads (%u in part 0, %u in part %u)", who, parts[0]->n_reads, parts[p]->n_reads, p);
+        if (parts[p]->norm != parts[0]->norm)
+            return fail(LIME_ERR_ARG, "%s: the parts were made with different norms (%u in part 0, %u in part %u)", who, parts[0]->norm, parts[p]->norm, p);
+        if (p && (uint64_t)id_base[p] < (uint64_t)id_base[p - 1] + n_refs_part[p - 1])
+            return fail(LIME_ERR_ARG, "%s: id_base must ascend: part %u starts at genome %u, part %u ends at %llu", who, p, id_base[p], p - 1,
+                        (unsigned long long)id_base[p - 1] + n_refs_part[p - 1]);
+        if ((uint64_t)id_base[p] + n_refs_part[p] > 0xFFFFFFFFull)
+            return fail(LIME_ERR_ARG, "%s: part %u: genome ids from %u on for %u genomes pass 2^32 - 1", who, p, id_base[p], n_refs_part[p]);
+    }
+    int rc = check_ctx(c, who); if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n_reads = parts[0]->n_reads;
+    const size_t off_bytes = ((size_t)n_reads + 1) * 8;
+
+    ListsGuard g;
+    lime_lists *L = new (std::nothrow) lime_lists();
+    if (!L) return fail(LIME_ERR_NOMEM, "%s: out of host memory", who);
+    L->ctx = c; L->n_reads = n_reads; L->norm = parts[0]->norm; L->beta = beta;
+    c->lists.push_back(L);
+    g.L = L;
+    if ((rc = L->rows.acquire(off_bytes + n_reads + 16))) return rc;
+
+    // scratch: the parts' table, the pass table, the rows' lengths, rocPRIM's
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t tab_bytes = up((size_t)n_parts * sizeof(LcPart));
+    size_t tmp_bytes = 0;
+    HIP_TRY(idx_scan_sum64(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)n_reads + 1, st));
+    DevBuf scratch;
+    if ((rc = scratch.alloc(tab_bytes + 256 + up(off_bytes) + up(tmp_bytes))))
+        return fail(rc, "%s: no device memory for %u parts of %u reads: %s", who, n_parts, n_reads, lime_last_error());
+    uint8_t *at = static_cast<uint8_t *>(scratch.p);
+    LcPart *d_parts = reinterpret_cast<LcPart *>(at);
+    uint8_t *d_pass = at + tab_bytes;
+    uint64_t *d_len = reinterpret_cast<uint64_t *>(at + tab_bytes + 256);
+    void *tmp = at + tab_bytes + 256 + up(off_bytes);
+    std::vector<uint8_t> h(tab_bytes + 256, 0);
+    LcPart *hp = reinterpret_cast<LcPart *>(h.data());
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        hp[p].row_off = parts[p]->row_off(); hp[p].row_max = parts[p]->row_max();
+        hp[p].pairs = parts[p]->n_pairs ? parts[p]->pairs.p : nullptr;
+        hp[p].id_base = id_base[p]; hp[p].pad = 0;
+    }
+    bool pass[256];
+    choose_pass_table(L->norm, beta, pass);                     // the reference's test, in the reference's types (ClusterBWT_DA.cpp:404-406)
+    for (int v = 0; v < 256; ++v) h[tab_bytes + v] = pass[v] ? 1 : 0;
+    HIP_TRY(hipMemcpy(scratch.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(L->rows.p);
+    struct Events {                                             // timing on: the rows' pass, the prefix sum, the copy
+        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    if (c->timing) for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
+    c->lc_info[0] = c->lc_info[1] = c->lc_info[2] = c->lc_info[3] = 0.0;
+    if (c->timing) HIP_TRY(hipEventRecord(ev.e[0], st));
+    launch_lc_rows(d_parts, n_parts, n_reads, d_pass, L->rows.p + off_bytes, d_len, st);
+    HIP_TRY(hipGetLastError());
+    if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], st));
+    HIP_TRY(idx_scan_sum64(tmp, &tmp_bytes, d_len, d_off, (size_t)n_reads + 1, st));
+    if (c->timing) HIP_TRY(hipEventRecord(ev.e[2], st));
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_off + n_reads, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                          // (the total sizes the pairs' block)
+    L->n_pairs = total;
+    if (total) {
+        if ((rc = L->pairs.acquire((size_t)total))) return fail(rc, "%s: no device memory for %llu pairs: %s", who, (unsigned long long)total, lime_last_error());
+        if (c->timing) HIP_TRY(hipEventRecord(ev.e[3], st));
+        launch_lc_copy(d_parts, n_parts, n_reads, d_off, L->pairs.p, st);
+        HIP_TRY(hipGetLastError());
+        if (c->timing) HIP_TRY(hipEventRecord(ev.e[4], st));
+        HIP_TRY(hipStreamSynchronize(st));                      // (the scratch goes back when this returns)
+    }
+    if (c->timing) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) c->lc_info[0] = ms;
+        if (hipEventElapsedTime(&ms, ev.e[1], ev.e[2]) == hipSuccess) c->lc_info[1] = ms;
+        if (total && hipEventElapsedTime(&ms, ev.e[3], ev.e[4]) == hipSuccess) c->lc_info[2] = ms;
+    }
+    c->lc_info[3] = (double)total;
+    *out = g.take();
+    return LIME_OK;
+}
+
+extern "C" int lime_get_concat_info(lime_ctx *c, double out[4])
+{
+    if (!c || !out) return fail(LIME_ERR_ARG, "lime_get_concat_info: NULL argument");
+    for (int k = 0; k < 4; ++k) out[k] = c->lc_info[k];
+    return LIME_OK;
 }
 
 // ---- Classify on the device over lists in HBM (lime_classify_kernel.hip) -------------------------------------------------

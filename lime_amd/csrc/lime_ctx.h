@@ -171,6 +171,7 @@ struct __attribute__((visibility("hidden"))) lime_ctx {              // (hidden:
     double cls_ms = 0.0;                    // the last lime_classify_lists_dev kernel (timing on)
     double idx_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // the last lime_build_index_dev (lime_get_index_info)
     double mrg_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // the last lime_merge_index_dev (lime_get_merge_info)
+    double lc_info[4] = {0, 0, 0, 0};                       // the last lime_lists_concat_dev (lime_get_concat_info)
     std::vector<lime_lists *> lists;        // clusterChoose results left in HBM that are still alive (lime_lists_free / lime_shutdown)
     std::vector<lime_gindex *> gidx;        // genome indexes left in HBM that are still alive (lime_gindex_free / lime_shutdown)
     std::vector<lime_docs *> docs;          // document collections left in HBM that are still alive (lime_docs_free / lime_shutdown)
@@ -282,6 +283,10 @@ int build_index_impl(lime_ctx *c, const char *who, const uint8_t *d_text, const 
 // lime_docs.cpp: the device parsers behind lime_docs_from_* on d_bytes[0 .. n), n < 2^32; line_base: the lines in front of d_bytes[0]
 int docs_parse_fasta_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out);
 int docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, uint64_t line_base, hipStream_t st, lime_docs **out);
+// lime_docs.cpp: the genome side's refusals of the sample calls, with one index or with shards (the read sets' own come between the two)
+int sample_check_shards(const char *who, lime_ctx *c, uint32_t n_shards, const lime_gindex *const *shards);
+int sample_check_rules(const char *who, uint32_t n_shards, const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha,
+                       uint32_t lcp_cap, uint32_t *n_refs, uint32_t *cap);
 // lime_stream.cpp
 int score_in_chunks(lime_ctx *c, const uint32_t *da, const uint8_t *ebwt, uint64_t n,
                     const lime_cluster_t *clusters, uint64_t n_clusters, uint32_t n_reads, uint32_t n_refs,

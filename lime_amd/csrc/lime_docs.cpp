@@ -345,18 +345,63 @@ extern "C" void lime_docs_free(lime_docs *d)
 }
 
 // ---- a sample: documents -> verdicts -----------------------------------------------------------------------------------------
-extern "C" int lime_classify_sample_dev(lime_ctx *c, uint32_t n_mates, const lime_docs *const *mates, const lime_gindex *gi,
-                                        const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
-                                        uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream)
+// The refusals about the genome side that lime_classify_sample[_shards]_dev and lime_classify_sample_stream[_shards] share, in two steps
+// (the read sets' own come between them): the shards are there and of this context; then alpha, shards that agree on term and lcp_cap, a
+// taxonomy of the shards' genomes in all, a cap the indexes can serve.  One shard: the texts of the calls that take one index.
+int lime_host::sample_check_shards(const char *who, lime_ctx *c, uint32_t n_shards, const lime_gindex *const *shards)
 {
-    const char *who = "lime_classify_sample_dev";
+    if (!n_shards) return fail(LIME_ERR_ARG, "%s: n_shards is 0", who);
+    for (uint32_t s = 0; s < n_shards; ++s) {
+        if (!shards[s]) return fail(LIME_ERR_ARG, "%s: index shard %u is NULL", who, s);
+        if (shards[s]->ctx != c)
+            return n_shards == 1 ? fail(LIME_ERR_ARG, "%s: the genome index belongs to another context", who)
+                                 : fail(LIME_ERR_ARG, "%s: index shard %u belongs to another context", who, s);
+    }
+    return LIME_OK;
+}
+int lime_host::sample_check_rules(const char *who, uint32_t n_shards, const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha,
+                                  uint32_t lcp_cap, uint32_t *n_refs, uint32_t *cap_out)
+{
+    if (!alpha) return fail(LIME_ERR_ARG, "%s: alpha is 0", who);
+    uint64_t total = 0;
+    for (uint32_t s = 0; s < n_shards; ++s) {
+        if (shards[s]->term != shards[0]->term || shards[s]->lcp_cap != shards[0]->lcp_cap)
+            return fail(LIME_ERR_ARG, "%s: index shard %u was built with term %u and lcp_cap %u, shard 0 with term %u and lcp_cap %u", who, s,
+                        (unsigned)shards[s]->term, shards[s]->lcp_cap, (unsigned)shards[0]->term, shards[0]->lcp_cap);
+        total += shards[s]->n_docs;
+    }
+    if (total > 0xFFFFFFFFull) return fail(LIME_ERR_ARG, "%s: the shards hold %llu genomes; ids are 32 bits", who, (unsigned long long)total);
+    if (!total || tx->n_targ != total)
+        return n_shards == 1 ? fail(LIME_ERR_ARG, "%s: the taxonomy holds %u genomes, the index %u", who, tx->n_targ, (uint32_t)total)
+                             : fail(LIME_ERR_ARG, "%s: the taxonomy holds %u genomes, the %u index shards %u", who, tx->n_targ, n_shards, (uint32_t)total);
+    const uint32_t gi_cap = shards[0]->lcp_cap, cap = lcp_cap ? lcp_cap : gi_cap;     // 0: the index's own
+    if (gi_cap && cap > gi_cap)
+        return fail(LIME_ERR_ARG, "%s: lcp_cap %u cannot be served from an index built with lcp_cap %u (1 .. %u can)", who, cap, gi_cap, gi_cap);
+    if (cap && cap < alpha) return fail(LIME_ERR_ARG, "%s: lcp values capped at %u cannot show clusters of alpha = %u", who, cap, alpha);
+    *n_refs = (uint32_t)total; *cap_out = cap;
+    return LIME_OK;
+}
+
+namespace {
+struct PartsGuard {                                      // one collection's unfiltered lists, one per index shard
+    std::vector<lime_lists *> l;
+    ~PartsGuard() { release(); }
+    void release() { for (lime_lists *&x : l) { lime_lists_free(x); x = nullptr; } }
+};
+}
+
+// lime_classify_sample_dev (one shard: the calls it always made) and lime_classify_sample_shards_dev
+static int classify_sample_impl(const char *who, lime_ctx *c, uint32_t n_mates, const lime_docs *const *mates, uint32_t n_shards,
+                                const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt,
+                                int binary, uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream)
+{
     uint64_t local[4];
     if (!counts) counts = local;
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
     if (!c) return fail(LIME_ERR_ARG, "%s: ctx is NULL", who);
     if (n_mates != 1 && n_mates != 2) return fail(LIME_ERR_ARG, "%s: n_mates is %u; a sample has 1 (single-end) or 2 (paired-end) read sets", who, n_mates);
-    if (!mates || !gi || !tx || !verdicts) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
-    if (gi->ctx != c) return fail(LIME_ERR_ARG, "%s: the genome index belongs to another context", who);
+    if (!mates || !shards || (n_shards == 1 && !shards[0]) || !tx || !verdicts) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    int rc = sample_check_shards(who, c, n_shards, shards); if (rc) return rc;
     for (uint32_t m = 0; m < n_mates; ++m) {
         if (!mates[m]) return fail(LIME_ERR_ARG, "%s: read set %u is NULL", who, m);
         if (mates[m]->ctx != c) return fail(LIME_ERR_ARG, "%s: read set %u belongs to another context", who, m);
@@ -364,36 +409,91 @@ extern "C" int lime_classify_sample_dev(lime_ctx *c, uint32_t n_mates, const lim
         if (mates[m]->n_docs != mates[0]->n_docs)
             return fail(LIME_ERR_ARG, "%s: the read sets hold different numbers of reads (%u in set 0, %u in set %u)", who, mates[0]->n_docs, mates[m]->n_docs, m);
     }
-    if (!alpha) return fail(LIME_ERR_ARG, "%s: alpha is 0", who);
-    if (!gi->n_docs || tx->n_targ != gi->n_docs)
-        return fail(LIME_ERR_ARG, "%s: the taxonomy holds %u genomes, the index %u", who, tx->n_targ, gi->n_docs);
-    const uint32_t cap = lcp_cap ? lcp_cap : gi->lcp_cap;                   // 0: the index's own
-    if (gi->lcp_cap && cap > gi->lcp_cap)
-        return fail(LIME_ERR_ARG, "%s: lcp_cap %u cannot be served from an index built with lcp_cap %u (1 .. %u can)", who, cap, gi->lcp_cap, gi->lcp_cap);
-    if (cap && cap < alpha) return fail(LIME_ERR_ARG, "%s: lcp values capped at %u cannot show clusters of alpha = %u", who, cap, alpha);
-    int rc = check_ctx(c, who); if (rc) return rc;
+    uint32_t n_refs = 0, cap = 0;
+    if ((rc = sample_check_rules(who, n_shards, shards, tx, alpha, lcp_cap, &n_refs, &cap))) return rc;
+    if ((rc = check_ctx(c, who))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t n_reads = mates[0]->n_docs, n_refs = gi->n_docs;
+    const uint32_t n_reads = mates[0]->n_docs, n_coll = 2 * n_mates;
+    std::vector<uint32_t> id_base(n_shards), n_part(n_shards);
+    for (uint32_t s = 0, at = 0; s < n_shards; ++s) { id_base[s] = at; n_part[s] = shards[s]->n_docs; at += shards[s]->n_docs; }
 
     ListsGuard lg;
-    for (uint32_t k = 0; k < 2 * n_mates; ++k) {                            // the script's order: F, F_RC, R, R_RC
+    for (uint32_t k = 0; k < n_coll; ++k) {                                 // the script's order: F, F_RC, R, R_RC
         const lime_docs *src = mates[k >> 1];
         DocsGuard rev;                                                      // (the reverse complement goes back at the end of the round)
         if (k & 1u) {
             if ((rc = lime_docs_revcomp(c, src, stream, &rev.d))) return rc;
             src = rev.d;
         }
-        const uint64_t n = src->n_text + src->n_docs + gi->n();
-        DevBuf ebwt, lcp, da;
-        if ((use_ebwt && (rc = ebwt.alloc((size_t)n))) || (rc = lcp.alloc((size_t)n * 4)) || (rc = da.alloc((size_t)n * 4)))
-            return fail(rc, "%s: no device memory for the arrays of %llu positions: %s", who, (unsigned long long)n, lime_last_error());
-        if ((rc = lime_merge_index_dev(c, src->text.p, src->doc_off.p, src->n_docs, src->n_text, gi, cap, (uint8_t *)ebwt.p, (uint32_t *)lcp.p,
-                                       (uint32_t *)da.p, stream)))
-            return rc;
-        if ((rc = lime_fused_choose_lists_dev(c, (const uint32_t *)lcp.p, (const uint32_t *)da.p, (const uint8_t *)ebwt.p, n, n_reads, n_refs, alpha, norm,
-                                              beta, &lg.l[k], stats ? &stats[k] : nullptr, stream)))
-            return rc;
-        HIP_TRY(hipStreamSynchronize(st));                                  // (the arrays go back when the round ends)
+        PartsGuard parts;
+        parts.l.assign(n_shards, nullptr);
+        for (uint32_t s = 0; s < n_shards; ++s) {
+            const lime_gindex *gi = shards[s];
+            const uint64_t n = src->n_text + src->n_docs + gi->n();
+            DevBuf ebwt, lcp, da;
+            if ((use_ebwt && (rc = ebwt.alloc((size_t)n))) || (rc = lcp.alloc((size_t)n * 4)) || (rc = da.alloc((size_t)n * 4)))
+                return fail(rc, "%s: no device memory for the arrays of %llu positions: %s", who, (unsigned long long)n, lime_last_error());
+            if ((rc = lime_merge_index_dev(c, src->text.p, src->doc_off.p, src->n_docs, src->n_text, gi, cap, (uint8_t *)ebwt.p, (uint32_t *)lcp.p,
+                                           (uint32_t *)da.p, stream)))
+                return rc;
+            // one shard: the list itself.  More: every non-zero row (beta -1: pass[0] holds and such rows are empty); the test follows on the whole row
+            lime_lists **dst = n_shards == 1 ? &lg.l[k] : &parts.l[s];
+            if ((rc = lime_fused_choose_lists_dev(c, (const uint32_t *)lcp.p, (const uint32_t *)da.p, (const uint8_t *)ebwt.p, n, n_reads, gi->n_docs, alpha,
+                                                  norm, n_shards == 1 ? beta : -1.0f, dst, stats ? &stats[(size_t)s * n_coll + k] : nullptr, stream)))
+                return rc;
+            HIP_TRY(hipStreamSynchronize(st));                              // (the arrays go back when the round ends)
+        }
+        if (n_shards > 1) {
+            if ((rc = lime_lists_concat_dev(c, n_shards, parts.l.data(), id_base.data(), n_part.data(), beta, &lg.l[k], stream))) return rc;
+        }
     }
-    return lime_classify_lists_dev(c, 2 * n_mates, lg.l, n_refs, tx, binary, verdicts, counts, stream);
+    return lime_classify_lists_dev(c, n_coll, lg.l, n_refs, tx, binary, verdicts, counts, stream);
+}
+
+extern "C" int lime_classify_sample_dev(lime_ctx *c, uint32_t n_mates, const lime_docs *const *mates, const lime_gindex *gi,
+                                        const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
+                                        uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream)
+{
+    return classify_sample_impl("lime_classify_sample_dev", c, n_mates, mates, 1, &gi, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap, verdicts, counts,
+                                stats, stream);
+}
+
+extern "C" int lime_classify_sample_shards_dev(lime_ctx *c, uint32_t n_mates, const lime_docs *const *mates, uint32_t n_shards,
+                                               const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta,
+                                               int use_ebwt, int binary, uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4],
+                                               lime_stats_t *stats, void *stream)
+{
+    return classify_sample_impl("lime_classify_sample_shards_dev", c, n_mates, mates, n_shards, shards, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap,
+                                verdicts, counts, stats, stream);
+}
+
+// ---- the genomes cut into index shards (pure host code) ------------------------------------------------------------------------
+extern "C" int lime_gindex_shard_plan(const uint64_t *doc_off, uint32_t n_docs, uint64_t max_positions, uint32_t *first_doc, uint32_t cap,
+                                      uint32_t *n_shards)
+{
+    const char *who = "lime_gindex_shard_plan";
+    if (n_shards) *n_shards = 0;
+    if (!doc_off || !first_doc || !n_shards) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (!max_positions) return fail(LIME_ERR_ARG, "%s: max_positions is 0", who);
+    if (!cap) return fail(LIME_ERR_ARG, "%s: first_doc holds no entry", who);
+    uint32_t ns = 0;
+    uint64_t used = 0;
+    first_doc[0] = 0;
+    for (uint32_t d = 0; d < n_docs; ++d) {
+        if (doc_off[d + 1] < doc_off[d]) return fail(LIME_ERR_ARG, "%s: doc_off decreases at genome %u", who, d);
+        const uint64_t pos = doc_off[d + 1] - doc_off[d] + 1;              // its symbols and its terminator
+        if (pos > max_positions)
+            return fail(LIME_ERR_ARG, "%s: genome %u holds %llu positions, more than the %llu a shard may hold (a genome is not cut)", who, d,
+                        (unsigned long long)pos, (unsigned long long)max_positions);
+        if (d == 0 || used + pos > max_positions) {                         // this genome opens a shard
+            if ((uint64_t)ns + 2 > cap)
+                return fail(LIME_ERR_ARG, "%s: more than %u shards: first_doc holds %u entries (n_shards + 1 are written)", who, cap - 1, cap);
+            first_doc[ns++] = d;
+            used = 0;
+        }
+        used += pos;
+    }
+    first_doc[ns] = n_docs;
+    *n_shards = ns;
+    return LIME_OK;
 }

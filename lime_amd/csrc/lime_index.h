@@ -115,6 +115,7 @@ void sc_launch_select(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uin
 struct IdxPairs { uint64_t *keys[2]; uint32_t *vals[2]; int cur; };       // double buffers; cur = which holds the data (updated by the sort)
 hipError_t idx_sort_pairs(void *temp, size_t *temp_bytes, IdxPairs *b, size_t m, unsigned begin_bit, unsigned end_bit, hipStream_t st);
 hipError_t idx_scan_sum(void *temp, size_t *temp_bytes, const uint32_t *in, uint32_t *out, size_t m, bool inclusive, hipStream_t st);
+hipError_t idx_scan_sum64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, size_t m, hipStream_t st);      // exclusive
 hipError_t idx_scan_max(void *temp, size_t *temp_bytes, const uint32_t *in, uint32_t *out, size_t m, hipStream_t st);
 
 } // namespace lime

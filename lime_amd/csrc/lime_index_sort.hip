@@ -23,6 +23,12 @@ hipError_t idx_scan_sum(void *temp, size_t *temp_bytes, const uint32_t *in, uint
                      : rocprim::exclusive_scan(temp, *temp_bytes, in, out, 0u, m, rocprim::plus<uint32_t>(), st);
 }
 
+// the exclusive sum of 64-bit words (the rows' offsets of lime_lists_concat_dev: a list may hold more than 2^32 pairs)
+hipError_t idx_scan_sum64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, size_t m, hipStream_t st)
+{
+    return rocprim::exclusive_scan(temp, *temp_bytes, in, out, (uint64_t)0, m, rocprim::plus<uint64_t>(), st);
+}
+
 hipError_t idx_scan_max(void *temp, size_t *temp_bytes, const uint32_t *in, uint32_t *out, size_t m, hipStream_t st)
 {
     return rocprim::inclusive_scan(temp, *temp_bytes, in, out, m, rocprim::maximum<uint32_t>(), st);

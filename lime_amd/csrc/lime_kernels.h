@@ -181,4 +181,12 @@ struct ClsArgs {
 };
 void launch_classify(const ClsArgs &a, hipStream_t st);
 
+// lists of column shards of one table made into the whole table's list (lime_listcat_kernel.hip; lime_choose.cpp lime_lists_concat_dev).
+// One part: its rows, its pairs (NULL where it has none) and the whole table's column its genome 0 is.  The table of parts is device memory.
+struct LcPart { const uint64_t *row_off; const uint8_t *row_max; const lime_pair_t *pairs; uint32_t id_base, pad; };
+// row_max[n_reads] = the maximum over the parts; len[n_reads + 1] = the parts' row lengths summed where pass[row_max] (256 bytes), else 0, and a 0 behind them
+void launch_lc_rows(const LcPart *parts, uint32_t n_parts, uint32_t n_reads, const uint8_t *pass, uint8_t *row_max, uint64_t *len, hipStream_t st);
+// row_off = the exclusive sum of len; out[row_off[r] .. row_off[r + 1]) = the parts' rows r one after the other, id_ref + id_base
+void launch_lc_copy(const LcPart *parts, uint32_t n_parts, uint32_t n_reads, const uint64_t *row_off, lime_pair_t *out, hipStream_t st);
+
 } // namespace lime

@@ -297,38 +297,34 @@ static int drain(lime_seq_reader *r, uint32_t batch_reads)
     }
 }
 
-extern "C" int lime_classify_sample_stream(lime_ctx *c, uint32_t n_mates, lime_seq_reader *const *readers, const lime_gindex *gi,
-                                           const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
-                                           uint32_t lcp_cap, uint32_t batch_reads, lime_verdict_sink sink, void *user, uint64_t counts[4],
-                                           uint64_t *n_reads, uint64_t *n_batches, void *stream)
+// lime_classify_sample_stream (one shard) and lime_classify_sample_stream_shards
+static int sample_stream_impl(const char *who, lime_ctx *c, uint32_t n_mates, lime_seq_reader *const *readers, uint32_t n_shards,
+                              const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt,
+                              int binary, uint32_t lcp_cap, uint32_t batch_reads, lime_verdict_sink sink, void *user, uint64_t counts[4],
+                              uint64_t *n_reads, uint64_t *n_batches, void *stream)
 {
-    const char *who = "lime_classify_sample_stream";
     uint64_t local[4];
     if (!counts) counts = local;
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
     if (n_reads) *n_reads = 0;
     if (n_batches) *n_batches = 0;
-    // lime_classify_sample_dev's refusals, in its order, before any read
+    // the sample call's refusals, in its order, before any read
     if (!c) return fail(LIME_ERR_ARG, "%s: ctx is NULL", who);
     if (n_mates != 1 && n_mates != 2) return fail(LIME_ERR_ARG, "%s: n_mates is %u; a sample has 1 (single-end) or 2 (paired-end) read sets", who, n_mates);
-    if (!readers || !gi || !tx) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
-    if (gi->ctx != c) return fail(LIME_ERR_ARG, "%s: the genome index belongs to another context", who);
+    if (!readers || !shards || (n_shards == 1 && !shards[0]) || !tx) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    int rc = sample_check_shards(who, c, n_shards, shards); if (rc) return rc;
     for (uint32_t m = 0; m < n_mates; ++m) {
         if (!readers[m]) return fail(LIME_ERR_ARG, "%s: reader %u is NULL", who, m);
         if (readers[m]->ctx != c) return fail(LIME_ERR_ARG, "%s: reader %u belongs to another context", who, m);
     }
     if (n_mates == 2 && readers[0] == readers[1]) return fail(LIME_ERR_ARG, "%s: the two read sets are one reader", who);
-    if (!alpha) return fail(LIME_ERR_ARG, "%s: alpha is 0", who);
-    const uint32_t n_refs = gi->n_docs, gi_cap = gi->lcp_cap;
-    if (!n_refs || tx->n_targ != n_refs) return fail(LIME_ERR_ARG, "%s: the taxonomy holds %u genomes, the index %u", who, tx->n_targ, n_refs);
-    const uint32_t cap = lcp_cap ? lcp_cap : gi_cap;
-    if (gi_cap && cap > gi_cap)
-        return fail(LIME_ERR_ARG, "%s: lcp_cap %u cannot be served from an index built with lcp_cap %u (1 .. %u can)", who, cap, gi_cap, gi_cap);
-    if (cap && cap < alpha) return fail(LIME_ERR_ARG, "%s: lcp values capped at %u cannot show clusters of alpha = %u", who, cap, alpha);
+    uint32_t n_refs = 0, cap = 0;
+    if ((rc = sample_check_rules(who, n_shards, shards, tx, alpha, lcp_cap, &n_refs, &cap))) return rc;
     if (!batch_reads) return fail(LIME_ERR_ARG, "%s: batch_reads is 0", who);
-    int rc = check_ctx(c, who); if (rc) return rc;
+    if ((rc = check_ctx(c, who))) return rc;
 
     std::vector<lime_verdict_t> verdicts;
+    std::vector<lime_stats_t> stats((size_t)n_shards * 4);
     uint64_t total = 0, batches = 0;
     for (;;) {
         DocsPair batch;
@@ -346,16 +342,37 @@ extern "C" int lime_classify_sample_stream(lime_ctx *c, uint32_t n_mates, lime_s
         if (!got[0]) break;
         if (verdicts.size() < got[0]) verdicts.resize(got[0]);
         uint64_t part[4];
-        lime_stats_t stats[4];
-        if ((rc = lime_classify_sample_dev(c, n_mates, batch.d, gi, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap, verdicts.data(), part, stats, stream)))
-            return rc;
+        rc = n_shards == 1 ? lime_classify_sample_dev(c, n_mates, batch.d, shards[0], tx, alpha, norm, beta, use_ebwt, binary, lcp_cap, verdicts.data(), part,
+                                                      stats.data(), stream)
+                           : lime_classify_sample_shards_dev(c, n_mates, batch.d, n_shards, shards, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap,
+                                                             verdicts.data(), part, stats.data(), stream);
+        if (rc) return rc;
         batch.release();
         for (int k = 0; k < 4; ++k) counts[k] += part[k];
-        if (sink && (rc = sink(user, total, verdicts.data(), got[0], stats))) return rc;
+        if (sink && (rc = sink(user, total, verdicts.data(), got[0], stats.data()))) return rc;
         total += got[0]; ++batches;
         if (n_reads) *n_reads = total;
         if (n_batches) *n_batches = batches;
     }
     if (!total) return fail(LIME_ERR_ARG, "%s: the read sets hold no reads", who);
     return LIME_OK;
+}
+
+extern "C" int lime_classify_sample_stream(lime_ctx *c, uint32_t n_mates, lime_seq_reader *const *readers, const lime_gindex *gi,
+                                           const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
+                                           uint32_t lcp_cap, uint32_t batch_reads, lime_verdict_sink sink, void *user, uint64_t counts[4],
+                                           uint64_t *n_reads, uint64_t *n_batches, void *stream)
+{
+    return sample_stream_impl("lime_classify_sample_stream", c, n_mates, readers, 1, &gi, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap, batch_reads,
+                              sink, user, counts, n_reads, n_batches, stream);
+}
+
+extern "C" int lime_classify_sample_stream_shards(lime_ctx *c, uint32_t n_mates, lime_seq_reader *const *readers, uint32_t n_shards,
+                                                  const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha, uint32_t norm,
+                                                  float beta, int use_ebwt, int binary, uint32_t lcp_cap, uint32_t batch_reads,
+                                                  lime_verdict_sink sink, void *user, uint64_t counts[4], uint64_t *n_reads, uint64_t *n_batches,
+                                                  void *stream)
+{
+    return sample_stream_impl("lime_classify_sample_stream_shards", c, n_mates, readers, n_shards, shards, tx, alpha, norm, beta, use_ebwt, binary,
+                              lcp_cap, batch_reads, sink, user, counts, n_reads, n_batches, stream);
 }
