@@ -214,6 +214,13 @@ int lime_fused_dev(lime_ctx *ctx, const uint32_t *d_lcp, const uint32_t *d_da,
  * [b0, b0 + nb) gathers the slices d_recs[binbase[b0] .. binbase[b0 + nb]) of every rank into one buffer and calls
  * lime_apply_records_dev, which builds bytes [b0 << bin_shift, ...) of the table in d_block (every byte written; add
  * the long clusters' records of ALL ranks).  lime_comm_exchange_records does the transport with RCCL.
+ * The t field of a 32-bit record: the contract is t == 1 (a score of t leaves the pass as t records), and a word whose t
+ * field is 0 is "no record": it is skipped wherever it stands between h_srcoff's bounds, so a caller may pad with such
+ * words.  What a 32-bit record with t >= 2 adds is unspecified (the kernels differ), and d_rx is not validated: that
+ * would cost a read of every record.  The 64-bit records carry any t of 1 .. 255 (added modulo 256).
+ * lime_apply_records_dev refuses with LIME_ERR_ARG, before anything is launched: n_src == 0, nb > 3072, bin_shift
+ * outside 16 .. 25, block_bytes not a multiple of 16 or beyond nb << bin_shift, d_block not 16-byte aligned, cell_lo not
+ * a multiple of 1 << bin_shift, and source offsets that descend.
  * Reference counterpart: the cluster-range split over threads adding into one table, ClusterBWT_DA.cpp:630-670. */
 typedef struct {
     uint32_t n_bins, bin_shift;

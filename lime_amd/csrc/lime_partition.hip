@@ -582,7 +582,13 @@ __global__ __launch_bounds__(PART_WG) void k_part2(const uint32_t *recs, const u
     }
     __syncthreads();
     part_scan(cnt, gcur, f2, wsum);                                  // gcur[sub] = where region sub starts inside the bin
+    // words of the bin that are no record (t == 0: a caller of lime_apply_records_dev may pad with them) move nowhere: the regions' ranges fill the
+    // bin's first n_valid places, and the rest of it -- which the bin's last region reaches up to, its range ends where the next bin starts -- is
+    // written as "no record" here (the array is scratch: what it held is anything)
+    const uint32_t n_valid = gcur[f2 - 1u] + cnt[f2 - 1u];
+    __syncthreads();
     for (uint32_t i = tid; i < f2; i += PART_WG) { regbase[(size_t)bin * f2 + i] = lo + gcur[i]; cnt[i] = 0u; }
+    for (uint64_t i = lo + n_valid + tid; i < hi; i += PART_WG) out[i] = 0u;
     __syncthreads();
     // ---- sweep 2: tile by tile into the regions' ranges (the next tile's records are loaded meanwhile)
     auto load_tile = [&](uint64_t t0, uint32_t (&v)[PART_PER]) {
@@ -596,7 +602,6 @@ __global__ __launch_bounds__(PART_WG) void k_part2(const uint32_t *recs, const u
     uint32_t nxt[PART_PER];
     if (lo < hi) load_tile(lo, nxt);
     for (uint64_t t0 = lo; t0 < hi; t0 += PART_TILE) {
-        const uint32_t tn = hi - t0 < PART_TILE ? (uint32_t)(hi - t0) : PART_TILE;
         uint32_t val[PART_PER], dr[PART_PER];
 #pragma unroll
         for (uint32_t j = 0; j < PART_PER; ++j) {
@@ -616,7 +621,8 @@ __global__ __launch_bounds__(PART_WG) void k_part2(const uint32_t *recs, const u
                 stage[toff[d] + r] = make_uint2(gcur[d] + r, val[j]);
             }
         __syncthreads();
-        for (uint32_t i = tid; i < tn; i += PART_WG) { const uint2 sv = stage[i]; out[lo + sv.x] = sv.y; }
+        const uint32_t nv = toff[f2 - 1u] + cnt[f2 - 1u];               // the tile's records: tn less its no-record words, which were not staged
+        for (uint32_t i = tid; i < nv; i += PART_WG) { const uint2 sv = stage[i]; out[lo + sv.x] = sv.y; }
         __syncthreads();
         for (uint32_t i = tid; i < f2; i += PART_WG) { gcur[i] += cnt[i]; cnt[i] = 0u; }
         __syncthreads();

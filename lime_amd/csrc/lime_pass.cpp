@@ -484,6 +484,8 @@ extern "C" int lime_apply_records_dev(lime_ctx *c, uint32_t n_src, const uint32_
     if (bin_shift < REGION_SHIFT || bin_shift > BIN_SHIFT_MAX || (block_bytes & 15u) || misaligned(d_block, 16) ||
         block_bytes > ((uint64_t)nb << bin_shift) || (cell_lo & (((uint64_t)1 << bin_shift) - 1u)))
         return fail(LIME_ERR_ARG, "lime_apply_records_dev: bad block geometry");
+    // (k_tile_bases counts the bins' tiles in LDS arrays of BIN_MAX words, and tbase holds BIN_MAX + 2)
+    if (nb > BIN_MAX) return fail(LIME_ERR_ARG, "lime_apply_records_dev: nb %u beyond the %u bins a block may have", nb, BIN_MAX);
     if (!nb || !block_bytes) return LIME_OK;
     // where every bin starts in the regrouped array: the sources' counts added up
     std::vector<uint64_t> dstbase((size_t)nb + 1, 0);
