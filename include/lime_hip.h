@@ -439,6 +439,18 @@ int lime_lists_concat_dev(lime_ctx *ctx, uint32_t n_parts, const lime_lists *con
 /* the last lime_lists_concat_dev of the ctx: with lime_set_timing on, HIP-event ms of out[0] the pass over the rows (k_lc_rows), out[1] the
  * prefix sum, out[2] the pass that copies the pairs (k_lc_copy); out[3] the pairs it wrote */
 int lime_get_concat_info(lime_ctx *ctx, double out[4]);
+/* The same with clusterChoose's test taken PER READ: read r passes where `float(max) / d_norms[r] > beta` (the reference's expression in the
+ * reference's types, from a 256 x 256 table the host builds for the norms 1 .. 255; a norm of 0 passes nothing; nothing is divided on the
+ * device).  d_norms: u8[n_reads] in device memory, e.g. lime_docs_norms_dev's.  The parts are as above -- made with a negative beta, their
+ * own norm plays no part but is equal among them; parts that hold per-read norms themselves are taken too, and theirs are ignored -- and
+ * one part with id_base 0 is the plain per-read filter of a list.  Same passes as above (k_rn_rows in place of k_lc_rows; the prefix sum and
+ * k_lc_copy unchanged), same argument checks and texts, same lime_get_concat_info; d_norms == NULL with n_reads > 0: LIME_ERR_ARG.  A negative
+ * beta keeps every non-zero row, as above.  *out owns a copy of the norms: lime_lists_info reports norm 0 for it, lime_lists_get_norms copies
+ * them out (LIME_ERR_ARG for a list made with one norm), lime_classify_lists_dev takes it, alone or next to lists with one norm, and
+ * lime_lists_concat_dev refuses it as a part (LIME_ERR_ARG). */
+int lime_lists_concat_norms_dev(lime_ctx *ctx, uint32_t n_parts, const lime_lists *const *parts, const uint32_t *id_base,
+                                const uint32_t *n_refs_part, const uint8_t *d_norms, float beta, lime_lists **out, void *stream);
+int lime_lists_get_norms(const lime_lists *lists, uint8_t *norms);   /* host copy into the caller's n_reads bytes */
 
 /* The lineage file (';'-separated, a header line; Classify.cpp:32-85) at taxRank `rank` (0 = genome .. 6), with the higher ranks'
  * columns when higher != 0 (the HIGHER=1 build; needs rank >= 1).  Host only; the device copy is made by the first device
@@ -454,12 +466,21 @@ void lime_taxonomy_free(lime_taxonomy *tx);
  * LIME_ERR_ARG (lime_last_error) for n_lists other than 2 / 4, lists with different n_reads, a taxonomy of another n_targ and an
  * idRef >= n_targ.  Synchronises `stream`.  One taxonomy may serve contexts on several threads and devices (its device copy is made
  * on first use, per device, under a lock; calls that use it on different devices take turns). */
+/* Lists with a norm per read (lime_lists_concat_norms_dev) are taken alone or next to lists with one norm, which behave as if every read
+ * had that norm: read r's values in list i are those of lime_cls value tables for norms_i[r], built by the host for the norms 1 .. 255 at the
+ * list's beta (float[256][2][256], 512 KB of device memory per distinct beta for the call's duration) and read by a second instantiation
+ * of the same decision, k_classify_norms.  A call without such a list runs k_classify, exactly as before. */
 int lime_classify_lists_dev(lime_ctx *ctx, uint32_t n_lists, const lime_lists *const *lists, uint32_t n_targ,
                             const lime_taxonomy *tx, int binary, lime_verdict_t *verdicts, uint64_t counts[4], void *stream);
 /* The same decision on the host over lists held in memory (lime_lists_get's copies): the CPU reference of the device path. */
 int lime_classify_mem(uint32_t n_files, const uint8_t *const *row_max, const uint64_t *const *row_off, const lime_pair_t *const *pairs,
                       const uint32_t *norms, const float *betas, int binary, uint32_t n_reads, uint32_t n_targ,
                       const lime_taxonomy *tx, lime_verdict_t *verdicts, uint64_t counts[4]);
+/* lime_classify_mem with a norm per read: read_norms[i] (u8[n_reads]) gives list i's norm for every read; an entry may be NULL, and then
+ * norms[i] is used for all reads as in lime_classify_mem.  A read norm of 0 gives the read no record in that list.  The same decide(). */
+int lime_classify_mem_norms(uint32_t n_files, const uint8_t *const *row_max, const uint64_t *const *row_off, const lime_pair_t *const *pairs,
+                            const uint32_t *norms, const uint8_t *const *read_norms, const float *betas, int binary, uint32_t n_reads,
+                            uint32_t n_targ, const lime_taxonomy *tx, lime_verdict_t *verdicts, uint64_t counts[4]);
 /* The classification file of lime_classify (header, "C,read,taxon,sim" lines, same float formatting) from verdicts. */
 int lime_write_classification(const char *path, const lime_verdict_t *verdicts, uint32_t n_reads);
 
@@ -610,6 +631,12 @@ int  lime_docs_info(const lime_docs *docs, uint32_t *n_docs, uint64_t *n_text);
 int  lime_docs_device(const lime_docs *docs, const uint8_t **d_text, const uint64_t **d_doc_off);
 int  lime_docs_get(const lime_docs *docs, uint8_t *text, uint64_t *doc_off);   /* host copies into the caller's n_text bytes / n_docs + 1 words */
 void lime_docs_free(lime_docs *docs);
+/* A norm per read from the documents' own lengths: d_norms[r] (u8[n_docs], device memory) = len + 1 - alpha where len = doc_off[r + 1] -
+ * doc_off[r] >= alpha -- the reference's norm = readLen + 1 - alpha (ClusterBWT_DA.cpp:555) with the read's own length -- and 1 for a shorter
+ * read, which is in no alpha-cluster and whose rows are empty.  One pass over doc_off (k_rn_norms), 8 bytes come back.  LIME_ERR_ARG for
+ * alpha == 0, and for a read of more than 255 symbols (the longest --readlen names, and the cells are bytes): the text gives the lowest such
+ * read's index, counted from 0, and its length; d_norms is then unspecified.  Synchronises `stream`. */
+int  lime_docs_norms_dev(lime_ctx *ctx, const lime_docs *docs, uint32_t alpha, uint8_t *d_norms, void *stream);
 
 /* Preprocessing.sh + LiME_paired.sh for one sample whose reads and genome index are in HBM: n_mates = 1 (single-end) or 2 (paired-end)
  * read sets of equally many reads; the collections are worked on in the script's order F, F_RC, R, R_RC.  Each one: the reverse complement
@@ -624,6 +651,14 @@ void lime_docs_free(lime_docs *docs);
  * LIME_ERR_ARG, with text in lime_last_error() and before any launch: n_mates other than 1 or 2, read sets with different document
  * counts, a read set without documents, alpha == 0, a taxonomy of another n_targ than the index's genomes, a cap the index cannot
  * serve or below alpha.  On any error nothing stays allocated.  Synchronises `stream`. */
+/* norm = LIME_NORM_PER_READ (this call, lime_classify_sample_shards_dev and the two stream calls; every other call that takes a norm refuses
+ * it with LIME_ERR_ARG): every read is normalised by its own length, for files whose reads differ in length (trimmed FASTQ).  Per mate
+ * lime_docs_norms_dev gives the norms (F and RC of a mate share them); every collection's lists are made with beta -1 and
+ * lime_lists_concat_norms_dev applies the real beta per read, for one shard or many; the stream calls take each batch's norms from the
+ * batch's documents.  With reads of one length L the verdicts are those of norm = L + 1 - alpha.  A read shorter than alpha has empty rows.
+ * A read of more than 255 symbols ends the call with LIME_ERR_ARG before any collection is made; the text names the read set (0 or 1) and
+ * the read's index in the whole sample; nothing stays allocated (and the stream calls' caller is left without an output file). */
+#define LIME_NORM_PER_READ 0xFFFFFFFFu
 int lime_classify_sample_dev(lime_ctx *ctx, uint32_t n_mates, const lime_docs *const *mates, const lime_gindex *gi,
                              const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
                              uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream);

@@ -117,10 +117,13 @@ SYMBOLS = {
     "lime_lists_info": (_i, [_vp, C.POINTER(_u32), _pu64, C.POINTER(_u32), C.POINTER(C.c_float)]),
     "lime_lists_free": (None, [_vp]),
     "lime_lists_concat_dev": (_i, [_vp, _u32, _vp, _vp, _vp, C.c_float, _pp, _vp]),
+    "lime_lists_concat_norms_dev": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, C.c_float, _pp, _vp]),
+    "lime_lists_get_norms": (_i, [_vp, _vp]),
     "lime_taxonomy_load": (_i, [C.c_char_p, _i, _i, _u32, _pp]),
     "lime_taxonomy_free": (None, [_vp]),
     "lime_classify_lists_dev": (_i, [_vp, _u32, _vp, _u32, _vp, _i, _vp, _vp, _vp]),
     "lime_classify_mem": (_i, [_u32, _vp, _vp, _vp, _vp, _vp, _i, _u32, _u32, _vp, _vp, _vp]),
+    "lime_classify_mem_norms": (_i, [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _i, _u32, _u32, _vp, _vp, _vp]),
     "lime_write_classification": (_i, [C.c_char_p, _vp, _u32]),
     "lime_index_size": (_u64, [_vp, _u32]),
     "lime_build_index": (_i, [_vp, _vp, _vp, _u32, C.c_uint8, _u32, _vp, _vp, _vp]),
@@ -155,6 +158,7 @@ SYMBOLS = {
     "lime_docs_device": (_i, [_vp, _pp, _pp]),
     "lime_docs_get": (_i, [_vp, _vp, _vp]),
     "lime_docs_free": (None, [_vp]),
+    "lime_docs_norms_dev": (_i, [_vp, _vp, _u32, _vp, _vp]),
     "lime_classify_sample_dev": (_i, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, C.c_float, _i, _i, _u32, _vp, _vp, _vp, _vp]),
     "lime_classify_sample_shards_dev": (_i, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, C.c_float, _i, _i, _u32, _vp, _vp, _vp, _vp]),
     "lime_seq_cut_dev": (_i, [_vp, _vp, _u64, _i, _u32, _i, _vp, _pu64, _pu64, _pu64]),

@@ -19,6 +19,7 @@ from ._lib import Cluster, LimeError, Stats, check, check_cls  # noqa: F401
 
 # lime_verdict_t: one read's classification (type C/U/A/H as a byte, rule 0 = U, 1, 2, 3)
 FASTA_BLOCK = _lib.FASTA_BLOCK          # LIME_FASTA_BLOCK: input bytes one workgroup pass of the device FASTA parser handles
+NORM_PER_READ = 0xFFFFFFFF              # LIME_NORM_PER_READ: the norm of the sample calls that normalises every read by its own length
 VERDICT = np.dtype([("taxon", "<u4"), ("sim", "<f4"), ("type", "u1"), ("rule", "u1"), ("pad", "u1", (2,))])
 
 
@@ -215,6 +216,30 @@ class Context:
         h = C.c_void_p()
         check(self.lib.lime_lists_concat_dev(self.h, k, hs, base.ctypes.data if k else None, cnt.ctypes.data if k else None, float(beta), C.byref(h), stream))
         return self._lists_of(h)
+
+    def lists_concat_norms(self, parts, id_base, n_refs_part, norms_t, beta, stream=None):
+        """lists_concat with clusterChoose's test taken per read: norms_t is a torch uint8 device tensor [n_reads] (docs_norms), read r
+        passes where float(max) / norms[r] > beta (lime_lists_concat_norms_dev).  One part with id_base 0 is the plain per-read filter.
+        -> Lists that own a copy of the norms (Lists.norms(); info() reports norm 0)"""
+        k = len(parts)
+        hs = (C.c_void_p * max(k, 1))(*[None if li is None else li.h for li in parts])
+        base = np.ascontiguousarray(id_base, dtype=np.uint32)
+        cnt = np.ascontiguousarray(n_refs_part, dtype=np.uint32)
+        if len(base) != k or len(cnt) != k:
+            raise ValueError("lists_concat_norms: one id_base and one n_refs_part per part")
+        h = C.c_void_p()
+        check(self.lib.lime_lists_concat_norms_dev(self.h, k, hs, base.ctypes.data if k else None, cnt.ctypes.data if k else None,
+                                                   None if norms_t is None else _ptr(norms_t), float(beta), C.byref(h), stream))
+        return self._lists_of(h)
+
+    def docs_norms(self, docs, alpha, stream=None, out=None):
+        """a norm per read from the documents' own lengths: len + 1 - alpha, 1 for a read shorter than alpha (lime_docs_norms_dev; a read of
+        more than 255 symbols: LimeError with its index and length) -> torch uint8 device tensor [n_docs] (out: a tensor or view to fill)"""
+        import torch
+        n = docs.info()[0]
+        t = out if out is not None else torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")      # (torch's current device: the ctx's, as for the other *_dev calls' tensors)
+        check(self.lib.lime_docs_norms_dev(self.h, docs.h, int(alpha), _ptr(t), stream))
+        return t[:n]
 
     def concat_info(self):
         """the last lists_concat of this context (lime_get_concat_info); the ms need set_timing(True)"""
@@ -594,7 +619,8 @@ class SeqReader:
 
     def close(self):
         if self.h:
-            self.ctx.lib.lime_seq_reader_close(self.h)
+            if self.ctx.h:                   # (a context that is closed already released it: lime_shutdown, also when both go in one collection)
+                self.ctx.lib.lime_seq_reader_close(self.h)
             self.h = None
 
     def __del__(self):
@@ -637,7 +663,8 @@ class Docs:
 
     def close(self):
         if self.h:
-            self.ctx.lib.lime_docs_free(self.h)
+            if self.ctx.h:                   # (a context that is closed already released it: lime_shutdown, also when both go in one collection)
+                self.ctx.lib.lime_docs_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -664,7 +691,8 @@ class GenomeIndex:
 
     def close(self):
         if self.h:
-            self.ctx.lib.lime_gindex_free(self.h)
+            if self.ctx.h:                   # (a context that is closed already released it: lime_shutdown, also when both go in one collection)
+                self.ctx.lib.lime_gindex_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -695,9 +723,17 @@ class Lists:
         check(self.ctx.lib.lime_lists_get(self.h, mx.ctypes.data, off.ctypes.data, C.byref(pp), C.byref(npairs)))
         return mx[:nr], off, self.ctx._pairs_out(pp, npairs)
 
+    def norms(self):
+        """the norms of Lists made with one per read (lists_concat_norms) -> u8[n_reads]; LimeError for Lists with one norm"""
+        nr = self.info()[0]
+        nm = np.zeros(nr + 1, dtype=np.uint8)
+        check(self.ctx.lib.lime_lists_get_norms(self.h, nm.ctypes.data))
+        return nm[:nr]
+
     def close(self):
         if self.h:
-            self.ctx.lib.lime_lists_free(self.h)
+            if self.ctx.h:                   # (a context that is closed already released it: lime_shutdown, also when both go in one collection)
+                self.ctx.lib.lime_lists_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -771,8 +807,9 @@ class ClassificationWriter:
             pass
 
 
-def classify_mem(lists, norms, betas, n_targ, taxonomy, binary=True):
-    """Classify on the host over 2 or 4 (row_max, row_off, pairs) triples (Lists.get's copies) -> (verdicts, counts)"""
+def classify_mem(lists, norms, betas, n_targ, taxonomy, binary=True, read_norms=None):
+    """Classify on the host over 2 or 4 (row_max, row_off, pairs) triples (Lists.get's copies) -> (verdicts, counts).  read_norms: per list
+    None or u8[n_reads], the list's norm for every read (lime_classify_mem_norms; norms[i] serves the lists whose entry is None)"""
     lib = _lib.load()
     k = len(lists)
     mx = [np.ascontiguousarray(l[0], dtype=np.uint8) for l in lists]
@@ -784,8 +821,19 @@ def classify_mem(lists, norms, betas, n_targ, taxonomy, binary=True):
     bt = np.ascontiguousarray(betas, dtype=np.float32)
     v = np.zeros(max(n_reads, 1), dtype=VERDICT)
     counts = (C.c_uint64 * 4)()
-    check_cls(lib.lime_classify_mem(k, P(mx), P(off), P(pr), nm.ctypes.data, bt.ctypes.data, int(bool(binary)), n_reads, n_targ,
-                                    taxonomy.h, v.ctypes.data, counts))
+    if read_norms is None:
+        check_cls(lib.lime_classify_mem(k, P(mx), P(off), P(pr), nm.ctypes.data, bt.ctypes.data, int(bool(binary)), n_reads, n_targ,
+                                        taxonomy.h, v.ctypes.data, counts))
+    else:
+        if len(read_norms) != k:
+            raise ValueError("classify_mem: one read_norms entry (None or u8[n_reads]) per list")
+        rn = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8) for a in read_norms]
+        for a in rn:
+            if a is not None and len(a) != n_reads:
+                raise ValueError("classify_mem: read_norms entries hold one norm per read")
+        prn = (C.c_void_p * k)(*[None if a is None else a.ctypes.data for a in rn])
+        check_cls(lib.lime_classify_mem_norms(k, P(mx), P(off), P(pr), nm.ctypes.data, prn, bt.ctypes.data, int(bool(binary)), n_reads, n_targ,
+                                              taxonomy.h, v.ctypes.data, counts))
     return v[:n_reads], list(counts)
 
 
@@ -977,8 +1025,8 @@ def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, thread
 
 def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16, beta=0.25, rank=1, trlcp=0, ebwt=True, higher=False, binary=True,
                ctx=None, batch_reads=0, window_bytes=0):
-    """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
-    [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta: the files are parsed on the device (each reads file
+    """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen (L | auto) --out output
+    [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta (read_len="auto": every read by its own length): the files are parsed on the device (each reads file
     FASTA or four-line FASTQ, by its first byte; refs FASTA), the
     genome index is built there (refs) or loaded (gidx: a file, or a list of files, the index shards of one database in genome order:
     repeated `--gidx`), only `output` is written.  batch_reads > 0: `--batch-reads N [--window-bytes W]`,
@@ -986,7 +1034,7 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
     if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
         raise ValueError("LiME_fasta takes one or two reads files and either refs or gidx")
-    norm = ((int(read_len) & 0xFF) + 1 - int(alpha)) & 0xFFFFFFFF
+    norm = NORM_PER_READ if read_len == "auto" else ((int(read_len) & 0xFF) + 1 - int(alpha)) & 0xFFFFFFFF     # (`--readlen auto`)
     own = ctx is None
     ctx = ctx or Context()
     tx = None

@@ -18,6 +18,8 @@
 // collection every shard is merged and scanned on its own and the shards' lists are made into the whole row's on the device
 // (lime_classify_sample_shards_dev / lime_classify_sample_stream_shards).  The verdicts are those of one index; the clusters and the
 // maximum length printed per collection are PER-SHARD figures in the same way (summed / the largest over the shards).
+// --readlen auto: no one read length; every read is normalised by its own (norm = its length + 1 - alpha, LIME_NORM_PER_READ of
+// lime_classify_sample_dev): files whose reads differ in length after trimming.  A read of more than 255 symbols ends the run with a text.
 // The defaults are the script's constants (LiME_paired.sh:21-23); norm = readLen + 1 - alpha (ClusterBWT_DA.cpp:555).  The reference's
 // compile-time switches are environment variables, as for the other drop-ins: LIME_EBWT (default 1), LIME_BIN (default 1), LIME_HIGHER (0).
 #include <string.h>
@@ -69,14 +71,18 @@ int main(int argc, char **argv)
     bool batched = false, have_window = false;
     float beta = 0.25f;
     unsigned char readLen = 0;                 // dataTypeSim, parsed with %hhu like ClusterBWT_DA (:519-521)
-    bool bad = false, have_len = false;
+    bool bad = false, have_len = false, len_auto = false;      // --readlen auto: every read by its own length (LIME_NORM_PER_READ)
     for (int i = 1; i < argc; ++i) {
         const bool more = i + 1 < argc;
         if (!strcmp(argv[i], "--refs")) { if (more) refs = argv[++i]; else bad = true; }
         else if (!strcmp(argv[i], "--gidx")) { if (more) gidx.push_back(argv[++i]); else bad = true; }
         else if (!strcmp(argv[i], "--lineage")) { if (more) lineage = argv[++i]; else bad = true; }
         else if (!strcmp(argv[i], "--out")) { if (more) output = argv[++i]; else bad = true; }
-        else if (!strcmp(argv[i], "--readlen")) { if (more && sscanf(argv[i + 1], "%hhu", &readLen) == 1) { ++i; have_len = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--readlen")) {
+            if (more && !strcmp(argv[i + 1], "auto")) { ++i; have_len = true; len_auto = true; }
+            else if (more && sscanf(argv[i + 1], "%hhu", &readLen) == 1) { ++i; have_len = true; len_auto = false; }
+            else bad = true;
+        }
         else if (!strcmp(argv[i], "--alpha")) { if (more && sscanf(argv[i + 1], "%u", &alpha) == 1) ++i; else bad = true; }
         else if (!strcmp(argv[i], "--beta")) { if (more && sscanf(argv[i + 1], "%f", &beta) == 1) ++i; else bad = true; }
         else if (!strcmp(argv[i], "--rank")) { if (more && sscanf(argv[i + 1], "%u", &rank) == 1) ++i; else bad = true; }
@@ -88,7 +94,7 @@ int main(int argc, char **argv)
     if (have_window && !batched) bad = true;
     if (reads.empty() || reads.size() > 2 || !refs == gidx.empty() || !lineage || !output || !have_len) bad = true;
     if (bad) {
-        std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx [--gidx next.gidx ...]) --lineage LineageFile --readlen L --out output\n"
+        std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx [--gidx next.gidx ...]) --lineage LineageFile --readlen (L | auto) --out output\n"
                   << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]]\n"
                   << "  classifies the reads of one sample (one file: single-end, two: paired-end) against the genomes of refs.fasta, or of an\n"
                   << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  A reads file is FASTA or\n"
@@ -99,11 +105,13 @@ int main(int argc, char **argv)
                   << "  --gidx given several times: the index shards of one genome database (BuildIndex --refs --shard-positions), in genome\n"
                   << "  order (the lineage file's order); the verdicts are those of one index, the clusters and maximum length printed per\n"
                   << "  collection are per-shard figures in the same way (summed / the largest over the shards).\n"
+                  << "  --readlen auto: every read is normalised by its own length (norm = its length + 1 - alpha), for reads of different\n"
+                  << "  lengths (trimmed FASTQ); a read of more than 255 symbols is refused.\n"
                   << "  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
     const int EBWT = env_flag("LIME_EBWT", 1), BIN = env_flag("LIME_BIN", 1), HIGHER = env_flag("LIME_HIGHER", 0);
-    const uint32_t norm = (uint32_t)(readLen + 1 - alpha);        // ClusterBWT_DA.cpp:555
+    const uint32_t norm = len_auto ? LIME_NORM_PER_READ : (uint32_t)(readLen + 1 - alpha);        // ClusterBWT_DA.cpp:555
     const uint32_t n_mates = (uint32_t)reads.size();
     const uint32_t n_shards = refs ? 1u : (uint32_t)gidx.size();
     if (n_shards > 1) {                        // the shards must agree and the lineage must hold their genomes: known before a device is opened

@@ -122,6 +122,7 @@ extern "C" int lime_choose_pairs_dev(lime_ctx *c, const uint8_t *d_sim, uint32_t
                                      lime_pair_t **pairs, uint64_t *n_pairs, void *stream)
 {
     int rc = check_ctx(c, "lime_choose_pairs_dev"); if (rc) return rc;
+    if (norm == LIME_NORM_PER_READ) return fail(LIME_ERR_ARG, "lime_choose_pairs_dev: LIME_NORM_PER_READ is taken by the sample calls only (lime_classify_sample_*); this call needs one norm");
     if (!pairs || !n_pairs || !row_off || (n_reads && (!d_sim || !row_max)))
         return fail(LIME_ERR_ARG, "lime_choose_pairs_dev: NULL array");
     *pairs = nullptr; *n_pairs = 0; row_off[0] = 0;
@@ -137,6 +138,7 @@ extern "C" int lime_choose_lists_dev(lime_ctx *c, const uint8_t *d_sim, uint32_t
                                      lime_lists **out, void *stream)
 {
     int rc = check_ctx(c, "lime_choose_lists_dev"); if (rc) return rc;
+    if (norm == LIME_NORM_PER_READ) return fail(LIME_ERR_ARG, "lime_choose_lists_dev: LIME_NORM_PER_READ is taken by the sample calls only (lime_classify_sample_*); this call needs one norm");
     if (!out || (n_reads && !d_sim)) return fail(LIME_ERR_ARG, "lime_choose_lists_dev: NULL argument");
     *out = nullptr;
     if (misaligned(d_sim, 16)) return fail(LIME_ERR_ARG, "lime_choose_lists_dev: d_sim must be 16-byte aligned (and lime_sim_bytes() long)");
@@ -250,6 +252,7 @@ extern "C" int lime_fused_choose_dev(lime_ctx *c, const uint32_t *d_lcp, const u
                                      lime_stats_t *stats, void *stream)
 {
     int rc = check_ctx(c, "lime_fused_choose_dev"); if (rc) return rc;
+    if (norm == LIME_NORM_PER_READ) return fail(LIME_ERR_ARG, "lime_fused_choose_dev: LIME_NORM_PER_READ is taken by the sample calls only (lime_classify_sample_*); this call needs one norm");
     if (!pairs || !n_pairs || !row_off || !row_max) return fail(LIME_ERR_ARG, "lime_fused_choose_dev: NULL output");
     if (!n_reads || !n_refs) return fail(LIME_ERR_ARG, "lime_fused_choose_dev: n_reads and n_refs must be > 0");
     *pairs = nullptr; *n_pairs = 0; row_off[0] = 0;
@@ -264,6 +267,7 @@ extern "C" int lime_fused_choose_lists_dev(lime_ctx *c, const uint32_t *d_lcp, c
                                            lime_stats_t *stats, void *stream)
 {
     int rc = check_ctx(c, "lime_fused_choose_lists_dev"); if (rc) return rc;
+    if (norm == LIME_NORM_PER_READ) return fail(LIME_ERR_ARG, "lime_fused_choose_lists_dev: LIME_NORM_PER_READ is taken by the sample calls only (lime_classify_sample_*); this call needs one norm");
     if (!out) return fail(LIME_ERR_ARG, "lime_fused_choose_lists_dev: NULL output");
     *out = nullptr;
     if (!n_reads || !n_refs) return fail(LIME_ERR_ARG, "lime_fused_choose_lists_dev: n_reads and n_refs must be > 0");
@@ -310,10 +314,11 @@ extern "C" void lime_lists_free(lime_lists *L)
 // A table column depends on its genome and the reads alone, so the lists of genome shards, each made with a
 // test every non-zero row passes, hold the whole table's non-zero cells; clusterChoose's test is applied here once, on the maximum over
 // the parts.  Passes: k_lc_rows (maxima and lengths), one 64-bit prefix sum, the total (8 bytes) to the host, k_lc_copy.
-extern "C" int lime_lists_concat_dev(lime_ctx *c, uint32_t n_parts, const lime_lists *const *parts, const uint32_t *id_base,
-                                     const uint32_t *n_refs_part, float beta, lime_lists **out, void *stream)
+// d_norms == NULL: lime_lists_concat_dev, one norm (the parts').  Else lime_lists_concat_norms_dev: the test by pass[norm[r]][max] (k_rn_rows,
+// lime_readnorm_kernel.hip), and *out owns a copy of the norms
+static int lists_concat_impl(const char *who, lime_ctx *c, uint32_t n_parts, const lime_lists *const *parts, const uint32_t *id_base,
+                             const uint32_t *n_refs_part, const uint8_t *d_norms, bool per_read, float beta, lime_lists **out, void *stream)
 {
-    const char *who = "lime_lists_concat_dev";
     if (!c) return fail(LIME_ERR_ARG, "%s: ctx is NULL", who);
     if (!out) return fail(LIME_ERR_ARG, "%s: NULL output", who);
     *out = nullptr;
@@ -331,7 +336,10 @@ extern "C" int lime_lists_concat_dev(lime_ctx *c, uint32_t n_parts, const lime_l
                         (unsigned long long)id_base[p - 1] + n_refs_part[p - 1]);
         if ((uint64_t)id_base[p] + n_refs_part[p] > 0xFFFFFFFFull)
             return fail(LIME_ERR_ARG, "%s: part %u: genome ids from %u on for %u genomes pass 2^32 - 1", who, p, id_base[p], n_refs_part[p]);
+        if (!per_read && parts[p]->per_read())
+            return fail(LIME_ERR_ARG, "%s: part %u holds a norm per read (lime_lists_concat_norms_dev takes such parts)", who, p);
     }
+    if (per_read && parts[0]->n_reads && !d_norms) return fail(LIME_ERR_ARG, "%s: d_norms is NULL", who);
     int rc = check_ctx(c, who); if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t n_reads = parts[0]->n_reads;
@@ -340,10 +348,15 @@ extern "C" int lime_lists_concat_dev(lime_ctx *c, uint32_t n_parts, const lime_l
     ListsGuard g;
     lime_lists *L = new (std::nothrow) lime_lists();
     if (!L) return fail(LIME_ERR_NOMEM, "%s: out of host memory", who);
-    L->ctx = c; L->n_reads = n_reads; L->norm = parts[0]->norm; L->beta = beta;
+    L->ctx = c; L->n_reads = n_reads; L->norm = per_read ? 0u : parts[0]->norm; L->beta = beta;
     c->lists.push_back(L);
     g.L = L;
     if ((rc = L->rows.acquire(off_bytes + n_reads + 16))) return rc;
+    if (per_read) {
+        if ((rc = L->norms.acquire((size_t)n_reads + 16))) return rc;
+        if (n_reads) HIP_TRY(hipMemcpyAsync(L->norms.p, d_norms, n_reads, hipMemcpyDeviceToDevice, st));
+    }
+    const size_t pass_bytes = per_read ? 65536 : 256;
 
     // scratch: the parts' table, the pass table, the rows' lengths, rocPRIM's
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -351,14 +364,14 @@ extern "C" int lime_lists_concat_dev(lime_ctx *c, uint32_t n_parts, const lime_l
     size_t tmp_bytes = 0;
     HIP_TRY(idx_scan_sum64(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)n_reads + 1, st));
     DevBuf scratch;
-    if ((rc = scratch.alloc(tab_bytes + 256 + up(off_bytes) + up(tmp_bytes))))
+    if ((rc = scratch.alloc(tab_bytes + pass_bytes + up(off_bytes) + up(tmp_bytes))))
         return fail(rc, "%s: no device memory for %u parts of %u reads: %s", who, n_parts, n_reads, lime_last_error());
     uint8_t *at = static_cast<uint8_t *>(scratch.p);
     LcPart *d_parts = reinterpret_cast<LcPart *>(at);
     uint8_t *d_pass = at + tab_bytes;
-    uint64_t *d_len = reinterpret_cast<uint64_t *>(at + tab_bytes + 256);
-    void *tmp = at + tab_bytes + 256 + up(off_bytes);
-    std::vector<uint8_t> h(tab_bytes + 256, 0);
+    uint64_t *d_len = reinterpret_cast<uint64_t *>(at + tab_bytes + pass_bytes);
+    void *tmp = at + tab_bytes + pass_bytes + up(off_bytes);
+    std::vector<uint8_t> h(tab_bytes + pass_bytes, 0);
     LcPart *hp = reinterpret_cast<LcPart *>(h.data());
     for (uint32_t p = 0; p < n_parts; ++p) {
         hp[p].row_off = parts[p]->row_off(); hp[p].row_max = parts[p]->row_max();
@@ -366,8 +379,15 @@ extern "C" int lime_lists_concat_dev(lime_ctx *c, uint32_t n_parts, const lime_l
         hp[p].id_base = id_base[p]; hp[p].pad = 0;
     }
     bool pass[256];
-    choose_pass_table(L->norm, beta, pass);                     // the reference's test, in the reference's types (ClusterBWT_DA.cpp:404-406)
-    for (int v = 0; v < 256; ++v) h[tab_bytes + v] = pass[v] ? 1 : 0;
+    if (!per_read) {
+        choose_pass_table(L->norm, beta, pass);                 // the reference's test, in the reference's types (ClusterBWT_DA.cpp:404-406)
+        for (int v = 0; v < 256; ++v) h[tab_bytes + v] = pass[v] ? 1 : 0;
+    } else {
+        for (uint32_t n = 1; n < 256u; ++n) {                   // the same expression once per norm a byte holds; row 0 stays all false
+            choose_pass_table(n, beta, pass);
+            for (int v = 0; v < 256; ++v) h[tab_bytes + n * 256u + v] = pass[v] ? 1 : 0;
+        }
+    }
     HIP_TRY(hipMemcpy(scratch.p, h.data(), h.size(), hipMemcpyHostToDevice));
     uint64_t *d_off = reinterpret_cast<uint64_t *>(L->rows.p);
     struct Events {                                             // timing on: the rows' pass, the prefix sum, the copy
@@ -377,7 +397,8 @@ extern "C" int lime_lists_concat_dev(lime_ctx *c, uint32_t n_parts, const lime_l
     if (c->timing) for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
     c->lc_info[0] = c->lc_info[1] = c->lc_info[2] = c->lc_info[3] = 0.0;
     if (c->timing) HIP_TRY(hipEventRecord(ev.e[0], st));
-    launch_lc_rows(d_parts, n_parts, n_reads, d_pass, L->rows.p + off_bytes, d_len, st);
+    if (per_read) launch_rn_rows(d_parts, n_parts, n_reads, L->norms.p, d_pass, L->rows.p + off_bytes, d_len, st);
+    else launch_lc_rows(d_parts, n_parts, n_reads, d_pass, L->rows.p + off_bytes, d_len, st);
     HIP_TRY(hipGetLastError());
     if (c->timing) HIP_TRY(hipEventRecord(ev.e[1], st));
     HIP_TRY(idx_scan_sum64(tmp, &tmp_bytes, d_len, d_off, (size_t)n_reads + 1, st));
@@ -405,6 +426,28 @@ extern "C" int lime_lists_concat_dev(lime_ctx *c, uint32_t n_parts, const lime_l
     return LIME_OK;
 }
 
+extern "C" int lime_lists_concat_dev(lime_ctx *c, uint32_t n_parts, const lime_lists *const *parts, const uint32_t *id_base,
+                                     const uint32_t *n_refs_part, float beta, lime_lists **out, void *stream)
+{
+    return lists_concat_impl("lime_lists_concat_dev", c, n_parts, parts, id_base, n_refs_part, nullptr, false, beta, out, stream);
+}
+
+extern "C" int lime_lists_concat_norms_dev(lime_ctx *c, uint32_t n_parts, const lime_lists *const *parts, const uint32_t *id_base,
+                                           const uint32_t *n_refs_part, const uint8_t *d_norms, float beta, lime_lists **out, void *stream)
+{
+    return lists_concat_impl("lime_lists_concat_norms_dev", c, n_parts, parts, id_base, n_refs_part, d_norms, true, beta, out, stream);
+}
+
+extern "C" int lime_lists_get_norms(const lime_lists *L, uint8_t *norms)
+{
+    if (!L) return fail(LIME_ERR_ARG, "lime_lists_get_norms: lists is NULL");
+    if (!L->per_read()) return fail(LIME_ERR_ARG, "lime_lists_get_norms: the lists were made with one norm (%u)", L->norm);
+    if (L->n_reads && !norms) return fail(LIME_ERR_ARG, "lime_lists_get_norms: NULL output");
+    int rc = check_ctx(L->ctx, "lime_lists_get_norms"); if (rc) return rc;
+    if (L->n_reads) HIP_TRY(hipMemcpy(norms, L->norms.p, L->n_reads, hipMemcpyDeviceToHost));
+    return LIME_OK;
+}
+
 extern "C" int lime_get_concat_info(lime_ctx *c, double out[4])
 {
     if (!c || !out) return fail(LIME_ERR_ARG, "lime_get_concat_info: NULL argument");
@@ -423,6 +466,25 @@ static void taxonomy_release_dev(lime_taxonomy *tx)
     dev_release(tx->d_tab);
     (void)hipSetDevice(cur);
     tx->d_tab = nullptr; tx->dev = -1;
+}
+
+// The tables of a list with per-read norms: value_tables for the norms 1 .. 255 at one beta, float[256][2][256] (row 0: zeros, a norm no
+// read has).  The .res.txt values (binary == 0) cost a print and a parse per entry, 65 280 of them, and a sample in batches asks for the same
+// block per batch: the last few blocks are kept, process-wide.
+static std::mutex g_normtab_mu;
+static const std::vector<float> &norm_tables(float beta, int binary, std::vector<float> &own)
+{
+    struct Entry { float beta; int binary; std::vector<float> tab; };
+    static std::vector<Entry> cache;
+    uint32_t key = 0, kb = 0;
+    memcpy(&key, &beta, 4);
+    std::lock_guard<std::mutex> lock(g_normtab_mu);
+    for (const Entry &e : cache) { memcpy(&kb, &e.beta, 4); if (kb == key && e.binary == (binary != 0)) { own = e.tab; return own; } }
+    own.assign((size_t)256 * 512, 0.0f);
+    for (uint32_t n = 1; n < 256u; ++n) lime_cls::value_tables(n, beta, binary, &own[(size_t)n * 512], &own[(size_t)n * 512 + 256]);
+    if (cache.size() >= 4) cache.erase(cache.begin());
+    cache.push_back(Entry{beta, binary != 0, own});
+    return own;
 }
 
 extern "C" int lime_classify_lists_dev(lime_ctx *c, uint32_t n_lists, const lime_lists *const *lists, uint32_t n_targ,
@@ -464,16 +526,50 @@ extern "C" int lime_classify_lists_dev(lime_ctx *c, uint32_t n_lists, const lime
         HIP_TRY(hipMemcpy(p, h.data(), words * 4, hipMemcpyHostToDevice));
     }
     // per list the 256 values the writer's expression gives a count (and the record tops), built here so that the device divides nothing
-    std::vector<float> tabs(4 * 2 * 256, 0.0f);
-    for (uint32_t i = 0; i < n_lists; ++i) lime_cls::value_tables(lists[i]->norm, lists[i]->beta, binary, &tabs[i * 512], &tabs[i * 512 + 256]);
+    bool per_read = false;
+    for (uint32_t i = 0; i < n_lists; ++i) per_read = per_read || lists[i]->per_read();
     DevBuf dt, dv;
-    const size_t tab_bytes = tabs.size() * 4;
-    if ((rc = dt.alloc(tab_bytes + 16)) || (rc = dv.alloc((size_t)n_reads * sizeof(lime_verdict_t)))) return rc;
+    size_t tab_bytes = 0;
+    ClsNormArgs na;
+    memset(&na, 0, sizeof na);
+    ClsArgs &a = na.a;
+    if (!per_read) {
+        std::vector<float> tabs(4 * 2 * 256, 0.0f);
+        for (uint32_t i = 0; i < n_lists; ++i) lime_cls::value_tables(lists[i]->norm, lists[i]->beta, binary, &tabs[i * 512], &tabs[i * 512 + 256]);
+        tab_bytes = tabs.size() * 4;
+        if ((rc = dt.alloc(tab_bytes + 16)) || (rc = dv.alloc((size_t)n_reads * sizeof(lime_verdict_t)))) return rc;
+        HIP_TRY(hipMemcpy(dt.p, tabs.data(), tab_bytes, hipMemcpyHostToDevice));
+    } else {
+        // a block of 256 tables per distinct (per-read, beta) and per (norm, beta) of the lists with one norm, which read row 0 of theirs
+        const size_t block_bytes = (size_t)256 * 512 * 4;
+        uint32_t n_blocks = 0, of[4] = {0, 0, 0, 0};
+        for (uint32_t i = 0; i < n_lists; ++i) {
+            uint32_t j = 0;
+            for (; j < i; ++j)
+                if (lists[j]->per_read() == lists[i]->per_read() && lists[j]->norm == lists[i]->norm && memcmp(&lists[j]->beta, &lists[i]->beta, 4) == 0) break;
+            of[i] = j < i ? of[j] : n_blocks++;
+            na.block |= of[i] << (8u * i);
+            na.norms[i] = lists[i]->per_read() ? lists[i]->norms.p : nullptr;
+        }
+        tab_bytes = block_bytes * n_blocks;
+        if ((rc = dt.alloc(tab_bytes + 16)) || (rc = dv.alloc((size_t)n_reads * sizeof(lime_verdict_t)))) return rc;
+        std::vector<float> own;
+        for (uint32_t i = 0, done = 0; i < n_lists; ++i) {
+            if (of[i] != done) continue;                      // (blocks are numbered in the order of their first list)
+            ++done;
+            uint8_t *dst = static_cast<uint8_t *>(dt.p) + block_bytes * of[i];
+            if (lists[i]->per_read()) {
+                const std::vector<float> &t = norm_tables(lists[i]->beta, binary, own);
+                HIP_TRY(hipMemcpy(dst, t.data(), block_bytes, hipMemcpyHostToDevice));
+            } else {
+                float one[512];
+                lime_cls::value_tables(lists[i]->norm, lists[i]->beta, binary, one, one + 256);
+                HIP_TRY(hipMemcpy(dst, one, sizeof one, hipMemcpyHostToDevice));
+            }
+        }
+    }
     uint32_t *d_err = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(dt.p) + tab_bytes);
-    HIP_TRY(hipMemcpy(dt.p, tabs.data(), tab_bytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(d_err, 0, 4, st));
-    ClsArgs a;
-    memset(&a, 0, sizeof a);
     for (uint32_t i = 0; i < n_lists; ++i) { a.row_max[i] = lists[i]->row_max(); a.row_off[i] = lists[i]->row_off(); a.pairs[i] = lists[i]->pairs.p; }
     a.tabs = static_cast<const float *>(dt.p);
     a.at_rank = static_cast<const uint32_t *>(tx->d_tab);
@@ -482,7 +578,7 @@ extern "C" int lime_classify_lists_dev(lime_ctx *c, uint32_t n_lists, const lime
     a.out = static_cast<lime_verdict_t *>(dv.p); a.err = d_err;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->timing) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, st)); }
-    launch_classify(a, st);
+    if (per_read) launch_classify_norms(na, st); else launch_classify(a, st);
     HIP_TRY(hipGetLastError());
     if (c->timing) HIP_TRY(hipEventRecord(e1, st));
     uint32_t err = 0;
@@ -506,6 +602,7 @@ extern "C" int lime_score_choose(lime_ctx *c, const uint32_t *da, const uint8_t 
                                  lime_pair_t **pairs, uint64_t *n_pairs, uint8_t *sim)
 {
     int rc = check_ctx(c, "lime_score_choose"); if (rc) return rc;
+    if (norm == LIME_NORM_PER_READ) return fail(LIME_ERR_ARG, "lime_score_choose: LIME_NORM_PER_READ is taken by the sample calls only (lime_classify_sample_*); this call needs one norm");
     if ((n && !da) || (n_clusters && !clusters)) return fail(LIME_ERR_ARG, "lime_score_choose: NULL array");
     if (!n_reads || !n_refs) return fail(LIME_ERR_ARG, "lime_score_choose: n_reads and n_refs must be > 0");
     DevBuf ds;
@@ -531,6 +628,7 @@ extern "C" int lime_score_choose_multi(int n_dev, const int *devices, const uint
 {
     if (n_dev < 1 || !pairs || !n_pairs || !row_off || (n_reads && !row_max) || (n && !da) || (n_clusters && !clusters))
         return fail(LIME_ERR_ARG, "lime_score_choose_multi: bad argument");
+    if (norm == LIME_NORM_PER_READ) return fail(LIME_ERR_ARG, "lime_score_choose_multi: LIME_NORM_PER_READ is taken by the sample calls only (lime_classify_sample_*); this call needs one norm");
     if (!n_reads || !n_refs) return fail(LIME_ERR_ARG, "lime_score_choose_multi: n_reads and n_refs must be > 0");
     if (n_dev > lime_device_count()) return fail(LIME_ERR_ARG, "lime_score_choose_multi: %d devices asked, %d visible", n_dev, lime_device_count());
     *pairs = nullptr; *n_pairs = 0; row_off[0] = 0;
@@ -619,6 +717,7 @@ extern "C" int lime_fused_choose_lists(lime_ctx *c, const uint32_t *lcp, const u
                                        lime_stats_t *stats)
 {
     int rc = check_ctx(c, "lime_fused_choose_lists"); if (rc) return rc;
+    if (norm == LIME_NORM_PER_READ) return fail(LIME_ERR_ARG, "lime_fused_choose_lists: LIME_NORM_PER_READ is taken by the sample calls only (lime_classify_sample_*); this call needs one norm");
     if (!out || (n && (!lcp || !da))) return fail(LIME_ERR_ARG, "lime_fused_choose_lists: NULL argument");
     *out = nullptr;
     DevBuf dl, dd, de;

@@ -387,39 +387,71 @@ extern "C" int lime_classification_writer_close(lime_classification_writer *w, i
     return rc;
 }
 
-extern "C" int lime_classify_mem(uint32_t n_files, const uint8_t *const *row_max, const uint64_t *const *row_off,
-                                 const lime_pair_t *const *pairs, const uint32_t *norms, const float *betas, int binary,
-                                 uint32_t n_reads, uint32_t n_targ, const lime_taxonomy *tx, lime_verdict_t *verdicts,
-                                 uint64_t counts[4])
+// lime_classify_mem (read_norms == NULL) and lime_classify_mem_norms: list i takes the values of read r from the tables of read_norms[i][r]
+// where read_norms[i] is there, else from those of norms[i]; both go through decide()
+static int classify_mem_impl(const char *who, uint32_t n_files, const uint8_t *const *row_max, const uint64_t *const *row_off,
+                             const lime_pair_t *const *pairs, const uint32_t *norms, const uint8_t *const *read_norms, const float *betas, int binary,
+                             uint32_t n_reads, uint32_t n_targ, const lime_taxonomy *tx, lime_verdict_t *verdicts, uint64_t counts[4])
 {
     uint64_t local[4] = {0, 0, 0, 0};
     if (!counts) counts = local;
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
     if ((n_files != 2 && n_files != 4) || !row_max || !row_off || !pairs || !norms || !betas || !tx || (n_reads && !verdicts)) {
-        g_cls_err = "lime_classify_mem: bad argument";
+        g_cls_err = std::string(who) + ": bad argument";
         return LIME_ERR_ARG;
     }
-    if (tx->n_targ != n_targ) { g_cls_err = "lime_classify_mem: the taxonomy was loaded for another number of genomes"; return LIME_ERR_ARG; }
+    if (tx->n_targ != n_targ) { g_cls_err = std::string(who) + ": the taxonomy was loaded for another number of genomes"; return LIME_ERR_ARG; }
     float vals[4][256], tops[4][256];
+    // per list with a norm per read: the tables of the norms met so far, [norm][2][256]; norm 0 (no read has it) gives no record
+    std::vector<float> per[4];
+    std::vector<uint8_t> have[4];
     for (uint32_t i = 0; i < n_files; ++i) {
-        if (!norms[i] || (n_reads && (!row_max[i] || !row_off[i]))) { g_cls_err = "lime_classify_mem: bad list"; return LIME_ERR_ARG; }
+        const bool pr = read_norms && read_norms[i];
+        if (n_reads && (!row_max[i] || !row_off[i])) { g_cls_err = std::string(who) + ": bad list"; return LIME_ERR_ARG; }
+        if (pr) { per[i].assign((size_t)256 * 512, 0.0f); have[i].assign(256, 0); have[i][0] = 1; continue; }
+        if (!norms[i]) { g_cls_err = std::string(who) + ": bad list"; return LIME_ERR_ARG; }
+        if (norms[i] == LIME_NORM_PER_READ) { g_cls_err = std::string(who) + ": LIME_NORM_PER_READ is no norm of a list (lime_classify_mem_norms takes the reads' norms)"; return LIME_ERR_ARG; }
         value_tables(norms[i], betas[i], binary, vals[i], tops[i]);
     }
     ReadLists L[4];
     std::vector<float> all[2];
-    std::ostringstream sink;
     for (uint32_t r = 0; r < n_reads; ++r) {
         for (uint32_t i = 0; i < n_files; ++i) {
+            const float *v = vals[i], *t = tops[i];
+            if (read_norms && read_norms[i]) {
+                const uint32_t n = read_norms[i][r];
+                float *tab = &per[i][(size_t)n * 512];
+                if (!have[i][n]) { value_tables(n, betas[i], binary, tab, tab + 256); have[i][n] = 1; }
+                v = tab; t = tab + 256;
+            }
             L[i].clear();
-            L[i].top = tops[i][row_max[i][r]];
+            L[i].top = t[row_max[i][r]];
             for (uint64_t k = row_off[i][r]; k < row_off[i][r + 1]; ++k) {
                 const lime_pair_t p = pairs[i][k];
                 if (p.id_ref >= n_targ) { g_cls_err = "genome index beyond numGenomes in list " + std::to_string(i); return LIME_ERR_ARG; }
-                L[i].cells.push_back(Cell{vals[i][(uint8_t)p.sim], p.id_ref});
+                L[i].cells.push_back(Cell{v[(uint8_t)p.sim], p.id_ref});
             }
         }
         verdicts[r] = decide(L, n_files, n_targ, tx->host, tx->rank, tx->higher != 0, all);
         switch (verdicts[r].type) { case 'C': ++counts[0]; break; case 'U': ++counts[1]; break; case 'A': ++counts[2]; break; default: ++counts[3]; }
     }
     return LIME_OK;
+}
+
+extern "C" int lime_classify_mem(uint32_t n_files, const uint8_t *const *row_max, const uint64_t *const *row_off,
+                                 const lime_pair_t *const *pairs, const uint32_t *norms, const float *betas, int binary,
+                                 uint32_t n_reads, uint32_t n_targ, const lime_taxonomy *tx, lime_verdict_t *verdicts,
+                                 uint64_t counts[4])
+{
+    return classify_mem_impl("lime_classify_mem", n_files, row_max, row_off, pairs, norms, nullptr, betas, binary, n_reads, n_targ, tx, verdicts, counts);
+}
+
+extern "C" int lime_classify_mem_norms(uint32_t n_files, const uint8_t *const *row_max, const uint64_t *const *row_off,
+                                       const lime_pair_t *const *pairs, const uint32_t *norms, const uint8_t *const *read_norms,
+                                       const float *betas, int binary, uint32_t n_reads, uint32_t n_targ, const lime_taxonomy *tx,
+                                       lime_verdict_t *verdicts, uint64_t counts[4])
+{
+    if (!read_norms) { g_cls_err = "lime_classify_mem_norms: bad argument"; return LIME_ERR_ARG; }
+    return classify_mem_impl("lime_classify_mem_norms", n_files, row_max, row_off, pairs, norms, read_norms, betas, binary, n_reads, n_targ, tx, verdicts,
+                             counts);
 }

@@ -13,6 +13,8 @@
 // Every float is a table lookup (the host builds the 256 values of each list with the writer's own expression), a float add or a
 // compare, in decide()'s order: no division, no multiply (so contraction cannot change a bit).  Cross-lane operations (the wave
 // reductions) run only at the read's top level, under wave-uniform conditions made scalar with readfirstlane.
+// Two kernels run the one decision: k_classify (a norm per list, the tables in LDS) and k_classify_norms (a norm per list and read,
+// lists with per-read norms: the tables in device memory).  A call without per-read lists launches k_classify, as it always did.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "lime_kernels.h"
@@ -64,8 +66,27 @@ __device__ __forceinline__ int find_in(const lime_pair_t *P, uint64_t b, uint32_
     return -1;
 }
 
+// Where the floats come from.  The decision is written once over an accessor: val(i, k) the value of count k in list i, top(i, m) the
+// record top of a row whose maximum is m (0: no record).
+//   TabLds    one norm per list (k_classify): the workgroup's copy in LDS of the lists' tables, [4][2][256].
+//   TabNorms  one norm per list AND read (k_classify_norms): the tables stay in device memory, [blocks][256][2][256]; per read the wave
+//             leaves in LDS the four addresses of its read's tables (block and norm chosen), and a lookup is one LDS read of the list's
+//             address and one load through the vector cache.  Nothing of a table is copied per read, and the scalar file, which
+//             k_classify fills, holds nothing more.
+struct TabLds {
+    const float (*t)[2][256];
+    template <typename K> __device__ __forceinline__ float val(uint32_t i, K k) const { return t[i][0][k]; }
+    template <typename K> __device__ __forceinline__ float top(uint32_t i, K m) const { return t[i][1][m]; }
+};
+struct TabNorms {
+    const float *const *rowp;                          // LDS: where the tables [2][256] of this wave's read start, one pointer per list
+    template <typename K> __device__ __forceinline__ float val(uint32_t i, K k) const { return rowp[i][(uint32_t)k]; }
+    template <typename K> __device__ __forceinline__ float top(uint32_t i, K m) const { return rowp[i][256u + (uint32_t)m]; }
+};
+
 // the values of genome g in every list (0 where absent); *earlier: g is in a list before `own` (own = 4: none is skipped)
-__device__ __forceinline__ void values_of(const ClsArgs &a, const ListPtrs &lp, const ReadRows &R, const float (*tab)[2][256], uint32_t g, uint32_t own,
+template <typename Tab>
+__device__ __forceinline__ void values_of(const ClsArgs &a, const ListPtrs &lp, const ReadRows &R, const Tab tab, uint32_t g, uint32_t own,
                                           float own_v, float v[4], bool *earlier)
 {
     bool e = false;
@@ -75,7 +96,7 @@ __device__ __forceinline__ void values_of(const ClsArgs &a, const ListPtrs &lp, 
         if (j >= a.n_lists) continue;                  // (uniform)
         if (j == own) { v[j] = own_v; continue; }
         const int k = find_in(lp.pairs[j], R.b[j], R.c[j + 1] - R.c[j], g);
-        if (k >= 0) { v[j] = tab[j][0][k]; if (j < own) e = true; }
+        if (k >= 0) { v[j] = tab.val(j, k); if (j < own) e = true; }
     }
     *earlier = e;
 }
@@ -132,7 +153,8 @@ __device__ __forceinline__ bool selected(uint32_t br, float h, float s0, float s
 }
 
 // the whole decision of read r by one wave; every value it returns is wave-uniform
-__device__ __forceinline__ lime_verdict_t classify_read(const ClsArgs &a, const ListPtrs &lp, const float (*tab)[2][256], uint32_t r)
+template <typename Tab>
+__device__ __forceinline__ lime_verdict_t classify_read(const ClsArgs &a, const ListPtrs &lp, const Tab tab, uint32_t r)
 {
     const uint32_t lane = __lane_id();
     ReadRows R;
@@ -146,7 +168,7 @@ __device__ __forceinline__ lime_verdict_t classify_read(const ClsArgs &a, const 
         const uint64_t b = lp.row_off[i][r], e = lp.row_off[i][r + 1];
         R.b[i] = b;
         c += uni((uint32_t)(e - b));
-        R.top[i] = unif(tab[i][1][lp.row_max[i][r]]);
+        R.top[i] = unif(tab.top(i, lp.row_max[i][r]));
         if (R.top[i] != 0.0f) { if (!any || R.top[i] > best) best = R.top[i]; any = true; }
     }
     R.c[4] = c;
@@ -162,7 +184,7 @@ __device__ __forceinline__ lime_verdict_t classify_read(const ClsArgs &a, const 
         if (t < T) {
             const Elem el = element(lp, R, t);
             if (el.g >= a.n_targ) bad = 1u;
-            if (candidate(best, top_of(R, el.i), tab[el.i][0][el.k])) acc.add(a, el.g);
+            if (candidate(best, top_of(R, el.i), tab.val(el.i, el.k))) acc.add(a, el.g);
         }
     }
     if (bad) atomicOr(a.err, 1u);
@@ -177,7 +199,7 @@ __device__ __forceinline__ lime_verdict_t classify_read(const ClsArgs &a, const 
         const uint32_t t = base + lane;
         if (t < T) {
             const Elem el = element(lp, R, t);
-            const float vi = tab[el.i][0][el.k];
+            const float vi = tab.val(el.i, el.k);
             float v[4]; bool earlier;
             values_of(a, lp, R, tab, el.g, el.i, vi, v, &earlier);
             const float s0 = v[0] + v[3], s1 = v[1] + v[2];
@@ -197,7 +219,7 @@ __device__ __forceinline__ lime_verdict_t classify_read(const ClsArgs &a, const 
             const uint32_t t = base + lane;
             if (t < T) {
                 const Elem el = element(lp, R, t);
-                const float vi = tab[el.i][0][el.k];
+                const float vi = tab.val(el.i, el.k);
                 if (candidate(best, top_of(R, el.i), vi)) {
                     float v[4]; bool earlier;
                     values_of(a, lp, R, tab, el.g, el.i, vi, v, &earlier);
@@ -230,7 +252,7 @@ __device__ __forceinline__ lime_verdict_t classify_read(const ClsArgs &a, const 
             if (t < T) {
                 const Elem el = element(lp, R, t);
                 float v[4]; bool earlier;
-                values_of(a, lp, R, tab, el.g, el.i, tab[el.i][0][el.k], v, &earlier);
+                values_of(a, lp, R, tab, el.g, el.i, tab.val(el.i, el.k), v, &earlier);
                 if (!earlier && el.g < a.n_targ && selected(br, h, v[0] + v[3], v[1] + v[2])) acc.add(a, el.g);
             }
         }
@@ -261,12 +283,55 @@ __global__ void __launch_bounds__(CLS_WG) k_classify(ClsArgs a)
     __syncthreads();
     const uint32_t wave = blockIdx.x * (CLS_WG / 64) + uni(threadIdx.x >> 6), n_waves = gridDim.x * (CLS_WG / 64);
     for (uint32_t r = wave; r < a.n_reads; r += n_waves) {
-        const lime_verdict_t v = classify_read(a, lp, tab, r);
+        const lime_verdict_t v = classify_read(a, lp, TabLds{tab}, r);
         if (__lane_id() == 0) a.out[r] = v;
     }
 }
 
+// the same decision, every read by the tables of its own norms; the lists' and the norms' pointers go through LDS like k_classify's
+__global__ void __launch_bounds__(CLS_WG) k_classify_norms(ClsNormArgs n)
+{
+    __shared__ ListPtrs lp;
+    __shared__ const uint8_t *np[4];
+    __shared__ const float *bp[4];                     // per list: its block of 256 tables
+    __shared__ lime_verdict_t *outp;
+    if (threadIdx.x == 0) outp = n.a.out;
+    __shared__ const float *rowp[CLS_WG / 64][4];      // per wave: its read's tables
+    if (threadIdx.x < 4) {
+        lp.row_max[threadIdx.x] = n.a.row_max[threadIdx.x]; lp.row_off[threadIdx.x] = n.a.row_off[threadIdx.x]; lp.pairs[threadIdx.x] = n.a.pairs[threadIdx.x];
+        np[threadIdx.x] = n.norms[threadIdx.x];        // (NULL for a list with one norm, and behind the last list)
+        bp[threadIdx.x] = n.a.tabs + ((size_t)((n.block >> (8u * threadIdx.x)) & 0xFFu) << 17);
+    }
+    __syncthreads();
+    const uint32_t w = uni(threadIdx.x >> 6), lane = __lane_id();
+    const uint32_t wave = blockIdx.x * (CLS_WG / 64) + w, n_waves = gridDim.x * (CLS_WG / 64);
+    TabNorms tab;
+    tab.rowp = rowp[w];
+    for (uint32_t r = wave; r < n.a.n_reads; r += n_waves) {
+        // lanes 0 .. 3 write the addresses, every lane reads them: one wave, whose LDS operations keep their order
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 4) {
+            const uint8_t *p = np[lane];
+            rowp[w][lane] = bp[lane] + ((size_t)(p ? (uint32_t)p[r] : 0u) << 9);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const lime_verdict_t v = classify_read(n.a, lp, tab, r);
+        if (lane == 0) outp[r] = v;
+    }
+}
+
 } // namespace
+
+void launch_classify_norms(const ClsNormArgs &a, hipStream_t st)
+{
+    if (!a.a.n_reads) return;
+    const uint32_t waves = CLS_WG / 64;
+    uint64_t blocks = ((uint64_t)a.a.n_reads + waves - 1) / waves;
+    if (blocks > 4096) blocks = 4096;                  // as launch_classify
+    hipLaunchKernelGGL(k_classify_norms, dim3((uint32_t)blocks), dim3(CLS_WG), 0, st, a);
+}
 
 void launch_classify(const ClsArgs &a, hipStream_t st)
 {

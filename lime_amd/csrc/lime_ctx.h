@@ -185,6 +185,8 @@ struct __attribute__((visibility("hidden"))) lime_lists {
     uint64_t n_pairs = 0;
     lime_host::DevArr<uint8_t> rows;
     lime_host::DevArr<lime_pair_t> pairs;
+    lime_host::DevArr<uint8_t> norms;       // a norm per read (lime_lists_concat_norms_dev: u8[n_reads], and norm is 0), else empty
+    bool per_read() const { return norms.p != nullptr; }
     const uint64_t *row_off() const { return reinterpret_cast<const uint64_t *>(rows.p); }
     const uint8_t *row_max() const { return rows.p + ((size_t)n_reads + 1) * 8; }
 };
@@ -287,6 +289,15 @@ int docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, u
 int sample_check_shards(const char *who, lime_ctx *c, uint32_t n_shards, const lime_gindex *const *shards);
 int sample_check_rules(const char *who, uint32_t n_shards, const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha,
                        uint32_t lcp_cap, uint32_t *n_refs, uint32_t *cap);
+// lime_docs.cpp: the reads' norms of lime_docs_norms_dev without its refusal: *n_long reads hold more than 255 symbols, the lowest of them is
+// *first with *first_len symbols (d_norms is then unspecified); the callers word the refusal
+int docs_norms_impl(lime_ctx *c, const lime_docs *docs, uint32_t alpha, uint8_t *d_norms, hipStream_t st, uint32_t *n_long, uint32_t *first,
+                    uint64_t *first_len);
+// lime_docs.cpp: lime_classify_sample_dev / lime_classify_sample_shards_dev for a batch whose first read is read_base of the whole sample
+// (a refusal under LIME_NORM_PER_READ names the read by its index in the sample)
+int classify_sample_at(const char *who, lime_ctx *c, uint32_t n_mates, const lime_docs *const *mates, uint32_t n_shards,
+                       const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
+                       uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream, uint64_t read_base);
 // lime_stream.cpp
 int score_in_chunks(lime_ctx *c, const uint32_t *da, const uint8_t *ebwt, uint64_t n,
                     const lime_cluster_t *clusters, uint64_t n_clusters, uint32_t n_reads, uint32_t n_refs,

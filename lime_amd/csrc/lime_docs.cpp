@@ -344,6 +344,45 @@ extern "C" void lime_docs_free(lime_docs *d)
     (void)hipSetDevice(cur);
 }
 
+// ---- a norm per read from the documents' lengths (lime_readnorm_kernel.hip: k_rn_norms) ----------------------------------------------
+int lime_host::docs_norms_impl(lime_ctx *c, const lime_docs *docs, uint32_t alpha, uint8_t *d_norms, hipStream_t st, uint32_t *n_long, uint32_t *first,
+                               uint64_t *first_len)
+{
+    *n_long = 0; *first = 0; *first_len = 0;
+    if (!docs->n_docs) return LIME_OK;
+    DevBuf info;
+    int rc = info.alloc(16); if (rc) return rc;
+    const uint32_t init[2] = {0u, 0xFFFFFFFFu};
+    uint32_t got[2] = {0u, 0u};
+    HIP_TRY(hipMemcpyAsync(info.p, init, 8, hipMemcpyHostToDevice, st));
+    launch_rn_norms(docs->doc_off.p, docs->n_docs, alpha, d_norms, (uint32_t *)info.p, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(got, info.p, 8, hipMemcpyDeviceToHost, st));      // the 8 bytes that come back
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!got[0]) return LIME_OK;
+    uint64_t off[2] = {0, 0};                                                // (a refusal only: the offending read's bounds)
+    HIP_TRY(hipMemcpy(off, docs->doc_off.p + got[1], 16, hipMemcpyDeviceToHost));
+    *n_long = got[0]; *first = got[1]; *first_len = off[1] - off[0];
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_norms_dev(lime_ctx *c, const lime_docs *docs, uint32_t alpha, uint8_t *d_norms, void *stream)
+{
+    const char *who = "lime_docs_norms_dev";
+    if (!c || !docs) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (docs->ctx != c) return fail(LIME_ERR_ARG, "%s: the documents belong to another context", who);
+    if (!alpha) return fail(LIME_ERR_ARG, "%s: alpha is 0", who);
+    if (docs->n_docs && !d_norms) return fail(LIME_ERR_ARG, "%s: d_norms is NULL", who);
+    int rc = check_ctx(c, who); if (rc) return rc;
+    uint32_t n_long = 0, first = 0;
+    uint64_t len = 0;
+    if ((rc = docs_norms_impl(c, docs, alpha, d_norms, (hipStream_t)stream, &n_long, &first, &len))) return rc;
+    if (n_long)
+        return fail(LIME_ERR_ARG, "%s: read %u holds %llu symbols (and %u reads in all more than 255): a norm is a byte, as the cells are", who, first,
+                    (unsigned long long)len, n_long);
+    return LIME_OK;
+}
+
 // ---- a sample: documents -> verdicts -----------------------------------------------------------------------------------------
 // The refusals about the genome side that lime_classify_sample[_shards]_dev and lime_classify_sample_stream[_shards] share, in two steps
 // (the read sets' own come between them): the shards are there and of this context; then alpha, shards that agree on term and lcp_cap, a
@@ -391,9 +430,10 @@ struct PartsGuard {                                      // one collection's unf
 }
 
 // lime_classify_sample_dev (one shard: the calls it always made) and lime_classify_sample_shards_dev
-static int classify_sample_impl(const char *who, lime_ctx *c, uint32_t n_mates, const lime_docs *const *mates, uint32_t n_shards,
-                                const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt,
-                                int binary, uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream)
+int lime_host::classify_sample_at(const char *who, lime_ctx *c, uint32_t n_mates, const lime_docs *const *mates, uint32_t n_shards,
+                                  const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt,
+                                  int binary, uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream,
+                                  uint64_t read_base)
 {
     uint64_t local[4];
     if (!counts) counts = local;
@@ -417,6 +457,22 @@ static int classify_sample_impl(const char *who, lime_ctx *c, uint32_t n_mates, 
     std::vector<uint32_t> id_base(n_shards), n_part(n_shards);
     for (uint32_t s = 0, at = 0; s < n_shards; ++s) { id_base[s] = at; n_part[s] = shards[s]->n_docs; at += shards[s]->n_docs; }
 
+    // LIME_NORM_PER_READ: every mate's norms from its documents' lengths, before anything else is made (F and RC of a mate share them: a
+    // reverse complement has its read's length); the lists are then made unfiltered and the test follows per read, for one shard or many
+    const bool per_read = norm == LIME_NORM_PER_READ;
+    DevBuf d_norms[2];
+    for (uint32_t m = 0; m < n_mates && per_read; ++m) {
+        if ((rc = d_norms[m].alloc((size_t)n_reads + 16))) return rc;
+        uint32_t n_long = 0, first = 0;
+        uint64_t len = 0;
+        if ((rc = docs_norms_impl(c, mates[m], alpha, (uint8_t *)d_norms[m].p, st, &n_long, &first, &len))) return rc;
+        if (n_long)
+            return fail(LIME_ERR_ARG, "%s: read set %u: read %llu holds %llu symbols; a read normalised by its own length holds at most 255 (the cells are bytes)",
+                        who, m, (unsigned long long)(read_base + first), (unsigned long long)len);
+    }
+    const bool whole = n_shards == 1 && !per_read;                          // the one list of a collection is made in one step
+    const uint32_t list_norm = per_read ? 1u : norm;                        // (unfiltered lists: their own norm plays no part)
+
     ListsGuard lg;
     for (uint32_t k = 0; k < n_coll; ++k) {                                 // the script's order: F, F_RC, R, R_RC
         const lime_docs *src = mates[k >> 1];
@@ -437,13 +493,17 @@ static int classify_sample_impl(const char *who, lime_ctx *c, uint32_t n_mates, 
                                            (uint32_t *)da.p, stream)))
                 return rc;
             // one shard: the list itself.  More: every non-zero row (beta -1: pass[0] holds and such rows are empty); the test follows on the whole row
-            lime_lists **dst = n_shards == 1 ? &lg.l[k] : &parts.l[s];
+            lime_lists **dst = whole ? &lg.l[k] : &parts.l[s];
             if ((rc = lime_fused_choose_lists_dev(c, (const uint32_t *)lcp.p, (const uint32_t *)da.p, (const uint8_t *)ebwt.p, n, n_reads, gi->n_docs, alpha,
-                                                  norm, n_shards == 1 ? beta : -1.0f, dst, stats ? &stats[(size_t)s * n_coll + k] : nullptr, stream)))
+                                                  list_norm, whole ? beta : -1.0f, dst, stats ? &stats[(size_t)s * n_coll + k] : nullptr, stream)))
                 return rc;
             HIP_TRY(hipStreamSynchronize(st));                              // (the arrays go back when the round ends)
         }
-        if (n_shards > 1) {
+        if (per_read) {
+            if ((rc = lime_lists_concat_norms_dev(c, n_shards, parts.l.data(), id_base.data(), n_part.data(), (const uint8_t *)d_norms[k >> 1].p, beta,
+                                                  &lg.l[k], stream)))
+                return rc;
+        } else if (n_shards > 1) {
             if ((rc = lime_lists_concat_dev(c, n_shards, parts.l.data(), id_base.data(), n_part.data(), beta, &lg.l[k], stream))) return rc;
         }
     }
@@ -454,8 +514,8 @@ extern "C" int lime_classify_sample_dev(lime_ctx *c, uint32_t n_mates, const lim
                                         const lime_taxonomy *tx, uint32_t alpha, uint32_t norm, float beta, int use_ebwt, int binary,
                                         uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4], lime_stats_t *stats, void *stream)
 {
-    return classify_sample_impl("lime_classify_sample_dev", c, n_mates, mates, 1, &gi, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap, verdicts, counts,
-                                stats, stream);
+    return classify_sample_at("lime_classify_sample_dev", c, n_mates, mates, 1, &gi, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap, verdicts, counts,
+                              stats, stream, 0);
 }
 
 extern "C" int lime_classify_sample_shards_dev(lime_ctx *c, uint32_t n_mates, const lime_docs *const *mates, uint32_t n_shards,
@@ -463,8 +523,8 @@ extern "C" int lime_classify_sample_shards_dev(lime_ctx *c, uint32_t n_mates, co
                                                int use_ebwt, int binary, uint32_t lcp_cap, lime_verdict_t *verdicts, uint64_t counts[4],
                                                lime_stats_t *stats, void *stream)
 {
-    return classify_sample_impl("lime_classify_sample_shards_dev", c, n_mates, mates, n_shards, shards, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap,
-                                verdicts, counts, stats, stream);
+    return classify_sample_at("lime_classify_sample_shards_dev", c, n_mates, mates, n_shards, shards, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap,
+                              verdicts, counts, stats, stream, 0);
 }
 
 // ---- the genomes cut into index shards (pure host code) ------------------------------------------------------------------------

@@ -64,6 +64,7 @@ static uint8_t row_maximum(const uint8_t *row, uint32_t n)
 extern "C" int lime_write_res_txt(const char *path, const uint8_t *sim, const uint8_t *row_max,
                                   uint32_t n_reads, uint32_t n_refs, uint32_t norm, float beta)
 {
+    if (norm == LIME_NORM_PER_READ) return LIME_ERR_ARG;      // (the .res files are written with one norm)
     File o(path, "w");
     if (!o.f) return LIME_ERR_IO;
     std::vector<char> buf(1 << 16);
@@ -89,6 +90,7 @@ extern "C" int lime_write_res_bin(const char *path_bin, const char *path_pos, co
                                   const uint8_t *row_max, uint32_t n_reads, uint32_t n_refs,
                                   uint32_t norm, float beta)
 {
+    if (norm == LIME_NORM_PER_READ) return LIME_ERR_ARG;      // (the .res files are written with one norm)
     File ob(path_bin, "wb"), op(path_pos, "wb");
     if (!ob.f || !op.f) return LIME_ERR_IO;
     std::vector<PairSim> recs;
@@ -132,6 +134,7 @@ extern "C" int lime_write_res_bin(const char *path_bin, const char *path_pos, co
 extern "C" int lime_write_res_txt_pairs(const char *path, const uint8_t *row_max, const uint64_t *row_off,
                                         const lime_pair_t *pairs, uint32_t n_reads, uint32_t norm, float beta)
 {
+    if (norm == LIME_NORM_PER_READ) return LIME_ERR_ARG;      // (the .res files are written with one norm)
     File o(path, "w");
     if (!o.f) return LIME_ERR_IO;
     std::vector<char> buf(1 << 16);
@@ -152,6 +155,7 @@ extern "C" int lime_write_res_bin_pairs(const char *path_bin, const char *path_p
                                         const uint64_t *row_off, const lime_pair_t *pairs, uint32_t n_reads,
                                         uint32_t norm, float beta)
 {
+    if (norm == LIME_NORM_PER_READ) return LIME_ERR_ARG;      // (the .res files are written with one norm)
     File ob(path_bin, "wb"), op(path_pos, "wb");
     if (!ob.f || !op.f) return LIME_ERR_IO;
     std::vector<PairSim> recs;

@@ -180,6 +180,16 @@ struct ClsArgs {
     uint32_t *err;                                  // |= 1: an idRef >= n_targ was met
 };
 void launch_classify(const ClsArgs &a, hipStream_t st);
+// the same decision with every read's values taken from the table of its own norm (k_classify_norms).
+// a.tabs is [n_blocks][256][2][256] in device memory: a block is the 255 tables of lime_cls::value_tables for the norms 1 .. 255 at one
+// beta (row 0: zeros).  List i reads block (block >> 8 i) & 255, row norms[i][r]; a list with one norm has norms[i] = NULL and reads
+// row 0 of a block of its own, which holds its one table.
+struct ClsNormArgs {
+    ClsArgs a;
+    const uint8_t *norms[4];                        // [n_reads] each, or NULL
+    uint32_t block;                                 // 8 bits per list
+};
+void launch_classify_norms(const ClsNormArgs &a, hipStream_t st);
 
 // lists of column shards of one table made into the whole table's list (lime_listcat_kernel.hip; lime_choose.cpp lime_lists_concat_dev).
 // One part: its rows, its pairs (NULL where it has none) and the whole table's column its genome 0 is.  The table of parts is device memory.
@@ -188,5 +198,14 @@ struct LcPart { const uint64_t *row_off; const uint8_t *row_max; const lime_pair
 void launch_lc_rows(const LcPart *parts, uint32_t n_parts, uint32_t n_reads, const uint8_t *pass, uint8_t *row_max, uint64_t *len, hipStream_t st);
 // row_off = the exclusive sum of len; out[row_off[r] .. row_off[r + 1]) = the parts' rows r one after the other, id_ref + id_base
 void launch_lc_copy(const LcPart *parts, uint32_t n_parts, uint32_t n_reads, const uint64_t *row_off, lime_pair_t *out, hipStream_t st);
+
+// every read normalised by its own length (lime_readnorm_kernel.hip; lime_docs.cpp lime_docs_norms_dev, lime_choose.cpp lime_lists_concat_norms_dev)
+// norm[r] = len + 1 - alpha where len = doc_off[r + 1] - doc_off[r] >= alpha, else 1; info[0] += the reads longer than 255, info[1] = min(info[1], the
+// lowest such r): the caller sets info to {0, 0xFFFFFFFF}
+void launch_rn_norms(const uint64_t *doc_off, uint32_t n_docs, uint32_t alpha, uint8_t *norm, uint32_t *info, hipStream_t st);
+uint32_t rn_norms_lanes();                          // the lanes of its largest grid: more reads go by grid stride
+// launch_lc_rows with the test per read: pass is 256 x 256 bytes, row n the test for norm n
+void launch_rn_rows(const LcPart *parts, uint32_t n_parts, uint32_t n_reads, const uint8_t *norm, const uint8_t *pass, uint8_t *row_max, uint64_t *len,
+                    hipStream_t st);
 
 } // namespace lime

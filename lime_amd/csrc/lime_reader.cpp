@@ -342,10 +342,8 @@ static int sample_stream_impl(const char *who, lime_ctx *c, uint32_t n_mates, li
         if (!got[0]) break;
         if (verdicts.size() < got[0]) verdicts.resize(got[0]);
         uint64_t part[4];
-        rc = n_shards == 1 ? lime_classify_sample_dev(c, n_mates, batch.d, shards[0], tx, alpha, norm, beta, use_ebwt, binary, lcp_cap, verdicts.data(), part,
-                                                      stats.data(), stream)
-                           : lime_classify_sample_shards_dev(c, n_mates, batch.d, n_shards, shards, tx, alpha, norm, beta, use_ebwt, binary, lcp_cap,
-                                                             verdicts.data(), part, stats.data(), stream);
+        rc = classify_sample_at(n_shards == 1 ? "lime_classify_sample_dev" : "lime_classify_sample_shards_dev", c, n_mates, batch.d, n_shards, shards, tx, alpha,
+                                norm, beta, use_ebwt, binary, lcp_cap, verdicts.data(), part, stats.data(), stream, total);
         if (rc) return rc;
         batch.release();
         for (int k = 0; k < 4; ++k) counts[k] += part[k];
