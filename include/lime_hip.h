@@ -531,6 +531,29 @@ int lime_fasta_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off
  *   "truncated record"                             the number of lines is no multiple of 4; L is the last line
  * Pure host code, a plain line reader: the oracle of the device parser below. */
 int lime_fastq_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs);
+/* lime_fastq_read(path, 0) and the quality strings: *qual holds, laid out by the same *doc_off as *text, the bytes of every line 4k + 3
+ * that are neither CR nor LF, as they are (no offset is taken off).  The same refusals, codes and texts (they start with this call's name).
+ * *qual is library-owned too (lime_free).  Pure host code: the oracle of lime_docs_from_fastq_qual*. */
+int lime_fastq_read_qual(const char *path, uint8_t **text, uint8_t **qual, uint64_t **doc_off, uint32_t *n_docs);
+/* Quality trimming, the BWA / cutadapt rule.  For a read with quality bytes b[0 .. L) let q[i] = b[i] - 33 as a signed integer (Phred+33,
+ * the only offset; a byte below 33 is a negative quality).  Two cutoffs, q5 for the 5' end and q3 for the 3' end, each 0 .. 93; a cutoff
+ * of 0 leaves that end alone whatever the bytes.
+ *   3' end  S(i) = sum over j in [i, L) of (q[j] - q3).  B = the largest i with S(i) > 0, or -1.  m = min S(j) over B < j < L.  If
+ *           B + 1 < L and m < 0, hi = the LARGEST j in that range with S(j) = m; otherwise hi = L.  As a loop: walk from the end, add
+ *           q[i] - q3, stop at the first sum above 0, keep the index of the strictly lowest sum seen.
+ *   5' end  P(i) = sum over j in [0, i] of (q5 - q[j]).  E = the smallest i with P(i) < 0, or L.  M = max P(j) over 0 <= j < E.  If E > 0
+ *           and M > 0, lo = 1 + the SMALLEST such j with P(j) = M; otherwise lo = 0.
+ *   Both ends are computed on the whole read, independently.  lo >= hi: the read becomes empty; otherwise it becomes text[lo .. hi).
+ * The sums are exact for every read (64 bits).  Read indices never change: as many documents come out as went in, an emptied read is an
+ * empty document, and no read is dropped for its length.
+ * lime_trim_info_t: n_reads; n_changed, the reads that lost a symbol; n_empty, the reads that held symbols and keep none; the symbols
+ * before and after.
+ * lime_quality_trim is the loop form in plain host code, the oracle of lime_docs_trim_dev: text / qual / doc_off[n_docs + 1] as
+ * lime_fastq_read_qual gives them; *out_text (at least one byte) and *out_doc_off[n_docs + 1] are library-owned (lime_free); info may
+ * be NULL.  LIME_ERR_ARG with a text: a NULL array, a cutoff above 93, doc_off that does not start at 0 or decreases. */
+typedef struct { uint64_t n_reads, n_changed, n_empty, symbols_in, symbols_out; } lime_trim_info_t;
+int lime_quality_trim(const uint8_t *text, const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t q5, uint32_t q3,
+                      uint8_t **out_text, uint64_t **out_doc_off, lime_trim_info_t *info);
 /* *format = 1 (FASTQ) if the file's first byte is '@', else 0 (FASTA: an empty file and text in front of the first header included).
  * LIME_ERR_IO when the file cannot be read.  Pure host code. */
 int lime_seq_format(const char *path, int *format);
@@ -620,6 +643,25 @@ int  lime_docs_from_bytes_dev(lime_ctx *ctx, const uint8_t *d_bytes, uint64_t n,
 int  lime_docs_from_fastq(lime_ctx *ctx, const char *path, lime_docs **out);
 int  lime_docs_from_fastq_bytes(lime_ctx *ctx, const uint8_t *bytes, uint64_t n, lime_docs **out);
 int  lime_docs_from_fastq_bytes_dev(lime_ctx *ctx, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out);
+/* The same three, keeping the quality strings: text, doc_off and every refusal (code, line, reason; the text starts with the name of the
+ * call that was made) are exactly those of the calls above; next to them the handle holds qual[0 .. n_text), lime_fastq_read_qual's,
+ * written by a fourth pass (lime_fqtrim_kernel.hip: k_fq_qual) from the prefix sums the other passes made: 1 more read per input byte
+ * and 1 write per quality byte.  A malformed file may hold more quality bytes than sequence bytes: only qual[0 .. n_text) is ever
+ * written, and the file is refused as above.  lime_docs_qual_device: *d_qual = the device pointer, or NULL for documents without
+ * qualities -- those of every other lime_docs_from_*, of lime_docs_revcomp, lime_docs_trim_dev and a reader without set_trim.
+ * lime_docs_get_qual: the host copy into the caller's n_text bytes; LIME_ERR_ARG for documents without qualities. */
+int  lime_docs_from_fastq_qual(lime_ctx *ctx, const char *path, lime_docs **out);
+int  lime_docs_from_fastq_qual_bytes(lime_ctx *ctx, const uint8_t *bytes, uint64_t n, lime_docs **out);
+int  lime_docs_from_fastq_qual_bytes_dev(lime_ctx *ctx, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out);
+int  lime_docs_qual_device(const lime_docs *docs, const uint8_t **d_qual);
+int  lime_docs_get_qual(const lime_docs *docs, uint8_t *qual);
+/* The documents cut by the rule at lime_quality_trim, on the device: *out = new documents (the caller's; no qualities) whose text and
+ * doc_off are byte for byte lime_quality_trim's, *info (may be NULL) its counts.  k_trim_bounds finds (lo, hi) of every read -- 16 lanes
+ * on a read, 256 quality bytes a step, the running sums carried in 64 bits -- one rocPRIM prefix sum places the new lengths, k_trim_copy
+ * moves text[lo .. hi) and writes doc_off.  Device memory next to the two handles: 12 bytes per read + the prefix sum's, given back
+ * before the call returns.  LIME_ERR_ARG with a text, before any launch: documents without qualities, a cutoff above 93, documents of
+ * another context.  On every error nothing stays allocated and *out is NULL.  Synchronises `stream`. */
+int  lime_docs_trim_dev(lime_ctx *ctx, const lime_docs *docs, uint32_t q5, uint32_t q3, void *stream, lime_docs **out, lime_trim_info_t *info);
 /* lime_docs_from_fastq or lime_docs_from_fasta, by lime_seq_format(path): the one place a file's format is decided */
 int  lime_docs_from_file(lime_ctx *ctx, const char *path, lime_docs **out);
 /* documents that are parsed already (copied); doc_off is checked on the device by lime_build_index's rules: LIME_ERR_ARG */
@@ -721,6 +763,12 @@ int  lime_seq_reader_open_bytes(lime_ctx *ctx, const uint8_t *bytes, uint64_t n,
 int  lime_seq_reader_next(lime_seq_reader *r, uint32_t max_reads, lime_docs **docs, uint64_t *first_record);
 int  lime_seq_reader_info(const lime_seq_reader *r, int *format, uint64_t *n_records, uint64_t *n_lines, uint64_t *n_bytes,
                           uint64_t *window_bytes);
+/* set_trim: from here on every batch is parsed with its qualities (lime_docs_from_fastq_qual_bytes_dev's passes) and handed out trimmed
+ * (lime_docs_trim_dev with q5, q3): the batches, concatenated, are the whole file's trimmed documents.  LIME_ERR_ARG with a text: a FASTA
+ * reader, a cutoff above 93, a reader whose lime_seq_reader_next has been called.  trim_info: the sums over the batches handed out so
+ * far (zeros without set_trim). */
+int  lime_seq_reader_set_trim(lime_seq_reader *r, uint32_t q5, uint32_t q3);
+int  lime_seq_reader_trim_info(const lime_seq_reader *r, lime_trim_info_t *info);
 void lime_seq_reader_close(lime_seq_reader *r);
 
 /* lime_classify_sample_dev batch by batch: per batch, batch_reads (>= 1) records from each of the n_mates readers, one unchanged

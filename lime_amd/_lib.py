@@ -34,6 +34,10 @@ class Records(C.Structure):
                 ("d_bigrecs", C.c_void_p), ("n_bigrecs", C.c_uint64)]
 
 
+class TrimInfo(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_changed", C.c_uint64), ("n_empty", C.c_uint64), ("symbols_in", C.c_uint64), ("symbols_out", C.c_uint64)]
+
+
 class LimeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"lime error {code}: {msg}")
@@ -151,6 +155,16 @@ SYMBOLS = {
     "lime_docs_from_fastq": (_i, [_vp, C.c_char_p, _pp]),
     "lime_docs_from_fastq_bytes": (_i, [_vp, _vp, _u64, _pp]),
     "lime_docs_from_fastq_bytes_dev": (_i, [_vp, _vp, _u64, _vp, _pp]),
+    "lime_fastq_read_qual": (_i, [C.c_char_p, _pp, _pp, _pp, C.POINTER(_u32)]),
+    "lime_quality_trim": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _pp, _pp, C.POINTER(TrimInfo)]),
+    "lime_docs_from_fastq_qual": (_i, [_vp, C.c_char_p, _pp]),
+    "lime_docs_from_fastq_qual_bytes": (_i, [_vp, _vp, _u64, _pp]),
+    "lime_docs_from_fastq_qual_bytes_dev": (_i, [_vp, _vp, _u64, _vp, _pp]),
+    "lime_docs_qual_device": (_i, [_vp, _pp]),
+    "lime_docs_get_qual": (_i, [_vp, _vp]),
+    "lime_docs_trim_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _pp, C.POINTER(TrimInfo)]),
+    "lime_seq_reader_set_trim": (_i, [_vp, _u32, _u32]),
+    "lime_seq_reader_trim_info": (_i, [_vp, C.POINTER(TrimInfo)]),
     "lime_docs_from_file": (_i, [_vp, C.c_char_p, _pp]),
     "lime_docs_from_arrays_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _pp]),
     "lime_docs_revcomp": (_i, [_vp, _vp, _vp, _pp]),

@@ -470,6 +470,33 @@ class Context:
         check(self.lib.lime_docs_from_fastq_bytes_dev(self.h, _ptr(bytes_t), n, stream, C.byref(h)))
         return self._docs_of(h)
 
+    def docs_from_fastq_qual(self, path):
+        """docs_from_fastq, keeping the quality strings next to the reads (Docs.qual) -> Docs"""
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_fastq_qual(self.h, os.fsencode(path), C.byref(h)))
+        return self._docs_of(h)
+
+    def docs_from_fastq_qual_bytes(self, data):
+        """the same from the bytes of a FASTQ file (bytes or a uint8 array)"""
+        a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_fastq_qual_bytes(self.h, a.ctypes.data if len(a) else None, len(a), C.byref(h)))
+        return self._docs_of(h)
+
+    def docs_from_fastq_qual_bytes_dev(self, bytes_t, n=None, stream=None):
+        """the same from a torch uint8 device tensor (a view at any alignment); n as for docs_from_bytes_dev"""
+        n = int(bytes_t.numel()) if n is None else int(n)
+        h = C.c_void_p()
+        check(self.lib.lime_docs_from_fastq_qual_bytes_dev(self.h, _ptr(bytes_t), n, stream, C.byref(h)))
+        return self._docs_of(h)
+
+    def docs_trim(self, docs, q5, q3, stream=None):
+        """Docs with qualities cut at both ends by the quality rule (lime_docs_trim_dev; a cutoff of 0 leaves that end alone)
+        -> (Docs without qualities, info: dict of n_reads, n_changed, n_empty, symbols_in, symbols_out)"""
+        h, ti = C.c_void_p(), _lib.TrimInfo()
+        check(self.lib.lime_docs_trim_dev(self.h, docs.h, int(q5), int(q3), stream, C.byref(h), C.byref(ti)))
+        return self._docs_of(h), _trim_info(ti)
+
     def docs_from_file(self, path):
         """a FASTA or FASTQ file, by seq_format(path) -> Docs"""
         h = C.c_void_p()
@@ -584,6 +611,20 @@ class Context:
         return int(n_reads.value), list(counts), int(n_batches.value)
 
 
+def _trim_info(ti):
+    return {k: int(getattr(ti, k)) for k, _ in _lib.TrimInfo._fields_}
+
+
+def _trim_cutoffs(trim_qual):
+    """Q, "Q", (Q5, Q3) or "Q5,Q3" -> (q5, q3), as `--trim-qual` reads them"""
+    if isinstance(trim_qual, str):
+        trim_qual = [int(x) for x in trim_qual.split(",")]
+    q = [int(trim_qual)] if isinstance(trim_qual, (int, np.integer)) else [int(x) for x in trim_qual]
+    if len(q) not in (1, 2) or any(not 0 <= x <= 93 for x in q):
+        raise ValueError("trim_qual is Q or (Q5, Q3), each 0 .. 93")
+    return (0, q[0]) if len(q) == 1 else (q[0], q[1])
+
+
 def _format_of(fmt):
     if fmt in ("fasta", "fastq"):
         return int(fmt == "fastq")
@@ -610,6 +651,16 @@ class SeqReader:
             if b is None:
                 return
             yield b[0]
+
+    def set_trim(self, q5, q3):
+        """every batch from here on is parsed with its qualities and handed out trimmed (lime_seq_reader_set_trim: before the first next, FASTQ only)"""
+        check(self.ctx.lib.lime_seq_reader_set_trim(self.h, int(q5), int(q3)))
+
+    def trim_info(self):
+        """the trim's counts summed over the batches handed out so far -> dict as Context.docs_trim gives"""
+        ti = _lib.TrimInfo()
+        check(self.ctx.lib.lime_seq_reader_trim_info(self.h, C.byref(ti)))
+        return _trim_info(ti)
 
     def info(self):
         f, nr, nl, nb, w = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
@@ -654,6 +705,27 @@ class Docs:
         text, off = np.zeros(max(nt, 1), dtype=np.uint8), np.zeros(nd + 1, dtype=np.uint64)
         check(self.ctx.lib.lime_docs_get(self.h, text.ctypes.data, off.ctypes.data))
         return text[:nt], off
+
+    @property
+    def has_qual(self):
+        """do the documents hold their reads' quality strings (docs_from_fastq_qual*)?"""
+        p = C.c_void_p()
+        check(self.ctx.lib.lime_docs_qual_device(self.h, C.byref(p)))
+        return bool(p.value)
+
+    @property
+    def qual(self):
+        """host copy of the quality bytes, uint8[n_text], laid out like text by doc_off (LimeError for documents without)"""
+        nt = self.info()[1]
+        q = np.zeros(max(nt, 1), dtype=np.uint8)
+        check(self.ctx.lib.lime_docs_get_qual(self.h, q.ctypes.data))
+        return q[:nt]
+
+    def qual_device(self):
+        """-> address of the quality bytes in HBM, or None"""
+        p = C.c_void_p()
+        check(self.ctx.lib.lime_docs_qual_device(self.h, C.byref(p)))
+        return p.value
 
     def revcomp(self, stream=None):
         """every document reversed and complemented (fasta_read(path, rc=True)'s records) -> Docs"""
@@ -937,6 +1009,35 @@ def fastq_read(path, rc=False):
     return [raw[int(off[k]):int(off[k + 1])] for k in range(nd.value)]
 
 
+def fastq_read_qual(path):
+    """fastq_read with the quality strings (lime_fastq_read_qual) -> (text uint8[n], qual uint8[n], doc_off uint64[n_docs + 1])"""
+    lib = _lib.load()
+    pt, pq, po, nd = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32(0)
+    check(lib.lime_fastq_read_qual(os.fsencode(path), C.byref(pt), C.byref(pq), C.byref(po), C.byref(nd)))
+    try:
+        off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(nd.value + 1,)).copy()
+        text = np.frombuffer(C.string_at(pt, int(off[-1])), dtype=np.uint8).copy()
+        qual = np.frombuffer(C.string_at(pq, int(off[-1])), dtype=np.uint8).copy()
+    finally:
+        lib.lime_free(pt); lib.lime_free(pq); lib.lime_free(po)
+    return text, qual, off
+
+
+def quality_trim(text, qual, doc_off, q5, q3):
+    """the quality rule in plain host code (lime_quality_trim) -> (text, doc_off, info dict)"""
+    lib = _lib.load()
+    t = np.ascontiguousarray(text, dtype=np.uint8); q = np.ascontiguousarray(qual, dtype=np.uint8); off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    pt, po, ti = C.c_void_p(), C.c_void_p(), _lib.TrimInfo()
+    check(lib.lime_quality_trim(t.ctypes.data if len(t) else None, q.ctypes.data if len(q) else None, off.ctypes.data, len(off) - 1, int(q5), int(q3),
+                                C.byref(pt), C.byref(po), C.byref(ti)))
+    try:
+        new_off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(len(off),)).copy()
+        new_text = np.frombuffer(C.string_at(pt, int(new_off[-1])), dtype=np.uint8).copy()
+    finally:
+        lib.lime_free(pt); lib.lime_free(po)
+    return new_text, new_off, _trim_info(ti)
+
+
 def seq_format(path):
     """"fastq" if the file's first byte is '@', else "fasta" (lime_seq_format)"""
     f = C.c_int(0)
@@ -1024,16 +1125,25 @@ def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, thread
 
 
 def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16, beta=0.25, rank=1, trlcp=0, ebwt=True, higher=False, binary=True,
-               ctx=None, batch_reads=0, window_bytes=0):
+               ctx=None, batch_reads=0, window_bytes=0, trim_qual=None):
     """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen (L | auto) --out output
     [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta (read_len="auto": every read by its own length): the files are parsed on the device (each reads file
     FASTA or four-line FASTQ, by its first byte; refs FASTA), the
     genome index is built there (refs) or loaded (gidx: a file, or a list of files, the index shards of one database in genome order:
     repeated `--gidx`), only `output` is written.  batch_reads > 0: `--batch-reads N [--window-bytes W]`,
-    the sample read and classified N reads at a time, `output` appended to batch by batch and renamed at the end.  -> counts {C, U, A, H}"""
+    the sample read and classified N reads at a time, `output` appended to batch by batch and renamed at the end.  trim_qual: `--trim-qual`,
+    Q (the 3' end) or (Q5, Q3): the reads, FASTQ, are cut by the quality rule on the device first; read_len must be "auto".
+    -> counts {C, U, A, H}"""
     reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
     if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
         raise ValueError("LiME_fasta takes one or two reads files and either refs or gidx")
+    if trim_qual is not None:
+        q5, q3 = _trim_cutoffs(trim_qual)
+        if read_len != "auto":
+            raise ValueError("LiME_fasta: trim_qual needs read_len=\"auto\": a fixed norm does not fit trimmed reads")
+        for r in reads:
+            if seq_format(r) != "fastq":
+                raise ValueError(f"LiME_fasta: {os.fspath(r)}: trim_qual needs the qualities of a FASTQ file; this one is FASTA")
     norm = NORM_PER_READ if read_len == "auto" else ((int(read_len) & 0xFF) + 1 - int(alpha)) & 0xFFFFFFFF     # (`--readlen auto`)
     own = ctx is None
     ctx = ctx or Context()
@@ -1041,6 +1151,15 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     try:
         if batch_reads:
             mates = [ctx.seq_reader(r, window_bytes) for r in reads]
+            if trim_qual is not None:
+                for m in mates:
+                    m.set_trim(q5, q3)
+        elif trim_qual is not None:
+            mates = []
+            for r in reads:
+                raw = ctx.docs_from_fastq_qual(r)
+                mates.append(ctx.docs_trim(raw, q5, q3)[0])
+                raw.close()
         else:
             mates = [ctx.docs_from_file(r) for r in reads]
         if refs is not None:

@@ -1,6 +1,6 @@
 // LiME_fasta -- Preprocessing.sh + LiME_paired.sh for one sample, from FASTA or FASTQ files, as ONE process with nothing on disk in between:
 //   LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
-//              [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]]
+//              [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]
 // Each reads file is FASTA or four-line FASTQ, decided by its first byte ('@': FASTQ; lime_docs_from_file), the mates each on their own;
 // --refs is FASTA.  The files' bytes go to the device as they are and are parsed there; per collection (reads_1, its reverse
 // complements, reads_2, its reverse complements: the script's `seqtk seq -r`) the reads are merged into the genome index, scanned and
@@ -20,6 +20,12 @@
 // maximum length printed per collection are PER-SHARD figures in the same way (summed / the largest over the shards).
 // --readlen auto: no one read length; every read is normalised by its own (norm = its length + 1 - alpha, LIME_NORM_PER_READ of
 // lime_classify_sample_dev): files whose reads differ in length after trimming.  A read of more than 255 symbols ends the run with a text.
+// --trim-qual Q: every read is cut at its 3' end by the BWA / cutadapt quality rule with cutoff Q (include/lime_hip.h: lime_quality_trim;
+// Phred+33) on the device, before anything else is made of it; --trim-qual Q5,Q3: at both ends.  Every reads file must then be FASTQ, and
+// --readlen must be auto: a fixed norm on trimmed reads is the mistake --readlen auto removes.  Each mate is trimmed on its own, the reverse
+// complements are made from the trimmed reads, an emptied read stays in its place as an empty read (verdict U), and the 255-symbol limit
+// holds for the trimmed length.  Per reads file one line is printed: the reads changed and emptied, the symbols before and after (with
+// --batch-reads: summed over the batches).  Nothing else is written.
 // The defaults are the script's constants (LiME_paired.sh:21-23); norm = readLen + 1 - alpha (ClusterBWT_DA.cpp:555).  The reference's
 // compile-time switches are environment variables, as for the other drop-ins: LIME_EBWT (default 1), LIME_BIN (default 1), LIME_HIGHER (0).
 #include <string.h>
@@ -29,6 +35,27 @@
 #include <vector>
 
 #include "cli_common.h"
+
+// "Q" -> (0, Q), "Q5,Q3": digits only, each 0 .. 93
+static bool parse_trim(const char *s, unsigned *q5, unsigned *q3)
+{
+    unsigned v[2] = {0, 0};
+    int k = 0, digits = 0;
+    for (; *s; ++s) {
+        if (*s == ',') { if (!digits || k == 1) return false; k = 1; digits = 0; continue; }
+        if (*s < '0' || *s > '9' || digits == 2) return false;
+        v[k] = v[k] * 10 + (unsigned)(*s - '0'); ++digits;
+    }
+    if (!digits || v[0] > 93 || v[1] > 93) return false;
+    if (k == 0) { *q5 = 0; *q3 = v[0]; } else { *q5 = v[0]; *q3 = v[1]; }
+    return true;
+}
+
+static void print_trim(const char *file, unsigned q5, unsigned q3, const lime_trim_info_t &t)
+{
+    std::cout << file << ": quality trim " << q5 << "," << q3 << ": " << t.n_changed << " of " << t.n_reads << " reads changed, " << t.n_empty << " emptied, "
+              << t.symbols_in << " symbols before, " << t.symbols_out << " after." << std::endl;
+}
 
 static int env_flag(const char *name, int dflt)
 {
@@ -66,7 +93,8 @@ int main(int argc, char **argv)
     std::vector<const char *> reads;
     std::vector<const char *> gidx;
     const char *refs = nullptr, *lineage = nullptr, *output = nullptr;
-    unsigned alpha = 16, rank = 1, trlcp = 0, batch_reads = 0;
+    unsigned alpha = 16, rank = 1, trlcp = 0, batch_reads = 0, q5 = 0, q3 = 0;
+    bool trim = false;
     unsigned long long window_bytes = 0;
     bool batched = false, have_window = false;
     float beta = 0.25f;
@@ -88,14 +116,16 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--rank")) { if (more && sscanf(argv[i + 1], "%u", &rank) == 1) ++i; else bad = true; }
         else if (!strcmp(argv[i], "--trlcp")) { if (more && sscanf(argv[i + 1], "%u", &trlcp) == 1) ++i; else bad = true; }
         else if (!strcmp(argv[i], "--batch-reads")) { if (more && sscanf(argv[i + 1], "%u", &batch_reads) == 1 && batch_reads) { ++i; batched = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--trim-qual")) { if (more && parse_trim(argv[i + 1], &q5, &q3)) { ++i; trim = true; } else bad = true; }
         else if (!strcmp(argv[i], "--window-bytes")) { if (more && sscanf(argv[i + 1], "%llu", &window_bytes) == 1 && window_bytes) { ++i; have_window = true; } else bad = true; }
         else reads.push_back(argv[i]);
     }
     if (have_window && !batched) bad = true;
+    if (trim && !len_auto) bad = true;             // (a fixed norm on trimmed reads)
     if (reads.empty() || reads.size() > 2 || !refs == gidx.empty() || !lineage || !output || !have_len) bad = true;
     if (bad) {
         std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx [--gidx next.gidx ...]) --lineage LineageFile --readlen (L | auto) --out output\n"
-                  << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]]\n"
+                  << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]\n"
                   << "  classifies the reads of one sample (one file: single-end, two: paired-end) against the genomes of refs.fasta, or of an\n"
                   << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  A reads file is FASTA or\n"
                   << "  four-line FASTQ, by its first byte ('@': FASTQ), each mate on its own; refs.fasta is FASTA.  --trlcp k: lcp values\n"
@@ -107,6 +137,9 @@ int main(int argc, char **argv)
                   << "  collection are per-shard figures in the same way (summed / the largest over the shards).\n"
                   << "  --readlen auto: every read is normalised by its own length (norm = its length + 1 - alpha), for reads of different\n"
                   << "  lengths (trimmed FASTQ); a read of more than 255 symbols is refused.\n"
+                  << "  --trim-qual Q: every read is cut at its 3' end by the BWA / cutadapt quality rule, cutoff Q (0 .. 93, Phred+33), on the\n"
+                  << "  device; Q5,Q3: at both ends.  The reads files must be FASTQ and --readlen must be auto; one line per reads file\n"
+                  << "  gives the reads changed and emptied and the symbols before and after.\n"
                   << "  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
@@ -137,6 +170,12 @@ int main(int argc, char **argv)
         lime_taxonomy_free(probe);
     }
 
+    for (uint32_t m = 0; m < n_mates && trim; ++m) {      // known before a device is opened, like the shards' headers
+        int format = 0;
+        if (lime_seq_format(reads[m], &format) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return -LIME_ERR_IO; }
+        if (format != 1) { std::cerr << "Error reading " << reads[m] << ": --trim-qual needs the qualities of a FASTQ file; this one is FASTA." << std::endl; return 1; }
+    }
+
     lime_ctx *ctx = nullptr;
     if (lime_init(pick_device(), &ctx) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(EXIT_FAILURE); }
     clk.mark("lime_init (HIP runtime)");
@@ -146,9 +185,19 @@ int main(int argc, char **argv)
     for (uint32_t m = 0; m < n_mates && batched; ++m) {
         const int rc = lime_seq_reader_open(ctx, reads[m], window_bytes, &readers[m]);
         if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
+        if (trim && lime_seq_reader_set_trim(readers[m], q5, q3) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
     }
     for (uint32_t m = 0; m < n_mates && !batched; ++m) {
-        const int rc = lime_docs_from_file(ctx, reads[m], &mates[m]);
+        int rc;
+        if (trim) {                                // the raw reads with their qualities, then the trimmed reads alone
+            lime_docs *raw = nullptr;
+            lime_trim_info_t ti;
+            if ((rc = lime_docs_from_fastq_qual(ctx, reads[m], &raw)) == LIME_OK) {
+                rc = lime_docs_trim_dev(ctx, raw, q5, q3, nullptr, &mates[m], &ti);
+                lime_docs_free(raw);
+                if (rc == LIME_OK) print_trim(reads[m], q5, q3, ti);
+            }
+        } else rc = lime_docs_from_file(ctx, reads[m], &mates[m]);
         if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
     }
     if (!batched) { uint32_t nd = 0; lime_docs_info(mates[0], &nd, nullptr); numReads = nd; }
@@ -203,6 +252,11 @@ int main(int argc, char **argv)
         for (uint32_t k = 0; k < 2 * n_mates; ++k)
             std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << sink.n_clusters[k] << " clusters summed over the batches"
                       << (n_shards > 1 ? " and shards" : "") << ", maximum length " << sink.max_len[k] << " in a batch" << (n_shards > 1 ? " and shard" : "") << "." << std::endl;
+        for (uint32_t m = 0; m < n_mates && trim; ++m) {
+            lime_trim_info_t ti;
+            lime_seq_reader_trim_info(readers[m], &ti);
+            print_trim(reads[m], q5, q3, ti);
+        }
         clk.mark("batches: reads, collections, classification");
         if (lime_classification_writer_close(sink.w, 1) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
         clk.mark("output file");

@@ -221,6 +221,7 @@ struct __attribute__((visibility("hidden"))) lime_docs {
     uint64_t n_text = 0;
     lime_host::DevArr<uint8_t> text;
     lime_host::DevArr<uint64_t> doc_off;
+    lime_host::DevArr<uint8_t> qual;        // the reads' quality bytes, laid out like text (lime_docs_from_fastq_qual*), or none
 };
 
 // a reads file handed out in batches of records (lime_reader.cpp): the raw bytes win[start .. fill) of the file, which begin at a record
@@ -236,6 +237,9 @@ struct __attribute__((visibility("hidden"))) lime_seq_reader {
     void *pin[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; size_t pin_bytes = 0; int pin_k = 0;
     uint64_t n_records = 0, n_lines = 0, n_bytes = 0;      // handed out so far
     int failed = 0; std::string failure;    // a refusal is final: later calls repeat it
+    bool asked = false;                     // lime_seq_reader_next has been called
+    bool trim = false; uint32_t q5 = 0, q3 = 0;            // lime_seq_reader_set_trim: every batch is parsed with its qualities and trimmed
+    lime_trim_info_t trimmed = {0, 0, 0, 0, 0};            // summed over the batches handed out
     ~lime_seq_reader();
 };
 
@@ -284,7 +288,10 @@ int build_index_impl(lime_ctx *c, const char *who, const uint8_t *d_text, const 
                      uint8_t term, uint32_t lcp_cap, uint8_t *d_ebwt, uint32_t *d_lcp, uint32_t *d_da, uint32_t *d_sa, hipStream_t st);
 // lime_docs.cpp: the device parsers behind lime_docs_from_* on d_bytes[0 .. n), n < 2^32; line_base: the lines in front of d_bytes[0]
 int docs_parse_fasta_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out);
-int docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, uint64_t line_base, hipStream_t st, lime_docs **out);
+int docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, uint64_t line_base, hipStream_t st, lime_docs **out,
+                         bool with_qual = false);
+// lime_docs.cpp: lime_docs_trim_dev without its argument checks
+int docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t q5, uint32_t q3, hipStream_t st, lime_docs **out, lime_trim_info_t *info);
 // lime_docs.cpp: the genome side's refusals of the sample calls, with one index or with shards (the read sets' own come between the two)
 int sample_check_shards(const char *who, lime_ctx *c, uint32_t n_shards, const lime_gindex *const *shards);
 int sample_check_rules(const char *who, uint32_t n_shards, const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha,

@@ -1,5 +1,6 @@
 // lime_docs.cpp -- document collections that stay in HBM (lime_docs: made from the raw bytes of a FASTA or FASTQ file by the kernels of
-// lime_fasta_kernel.hip / lime_fastq_kernel.hip, or copied from parsed arrays), their reverse complements, and a whole sample from documents to verdicts
+// lime_fasta_kernel.hip / lime_fastq_kernel.hip, or copied from parsed arrays), their reverse complements, FASTQ reads with their quality strings and
+// the quality trim (lime_fqtrim_kernel.hip), and a whole sample from documents to verdicts
 // (lime_classify_sample_dev: per collection the merge into the genome index, the scan and clusterChoose, then Classify over the lists).
 // include/lime_hip.h states the contract.
 #include <hip/hip_runtime.h>
@@ -117,7 +118,9 @@ int lime_host::docs_parse_fasta_dev(lime_ctx *c, const char *who, const uint8_t 
 // the same for four-line FASTQ: 24 bytes per block + rocPRIM's + one error word.  The error word comes back with the copy the write pass
 // is waited for anyway: two synchronisations, like parse_dev.  line_base: the lines in front of d_bytes[0] (a batch of lime_seq_reader), added to
 // the line a refusal names
-int lime_host::docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, uint64_t line_base, hipStream_t st, lime_docs **out)
+// with_qual: the quality bytes too, by a fourth pass (lime_fqtrim_kernel.hip) into n_keep + 16 bytes of which only the first n_keep are written
+int lime_host::docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, uint64_t line_base, hipStream_t st, lime_docs **out,
+                                    bool with_qual)
 {
     static const char *const reason[4] = {"record does not start with '@'", "separator line does not start with '+'",
                                           "quality length differs from sequence length", "truncated record"};
@@ -156,9 +159,15 @@ int lime_host::docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t 
     }
     DocsGuard dg;
     int rc = docs_new(c, who, n_lines / 4, n_keep, dg); if (rc) return rc;
+    if (with_qual && (rc = dg.d->qual.acquire((size_t)n_keep + 16)))
+        return fail(rc, "%s: no device memory for %u quality bytes: %s", who, n_keep, lime_last_error());
     if (nb) {
         fq_launch_write(d_bytes, n, nb, line0, off_keep, off_diff, n_lines / 4, dg.d->text.p, dg.d->doc_off.p, err, st);
         HIP_TRY(hipGetLastError());
+        if (with_qual) {
+            fqt_launch_qual(d_bytes, n, nb, line0, off_keep, off_diff, dg.d->qual.p, n_keep, st);
+            HIP_TRY(hipGetLastError());
+        }
         HIP_TRY(hipMemcpyAsync(&err_word, err, 8, hipMemcpyDeviceToHost, st));
     } else {
         HIP_TRY(hipMemsetAsync(dg.d->doc_off.p, 0, 8, st));
@@ -176,6 +185,11 @@ static int parse_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint6
 static int parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out)
 {
     return docs_parse_fastq_dev(c, who, d_bytes, n, 0, st, out);
+}
+
+static int parse_fastq_qual_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out)
+{
+    return docs_parse_fastq_dev(c, who, d_bytes, n, 0, st, out, true);
 }
 
 typedef int (*ParseFn)(lime_ctx *, const char *, const uint8_t *, uint64_t, hipStream_t, lime_docs **);
@@ -248,6 +262,19 @@ extern "C" int lime_docs_from_fastq_bytes(lime_ctx *c, const uint8_t *bytes, uin
     return from_bytes(c, "lime_docs_from_fastq_bytes", parse_fastq_dev, bytes, n, out);
 }
 extern "C" int lime_docs_from_fastq(lime_ctx *c, const char *path, lime_docs **out) { return from_path(c, "lime_docs_from_fastq", parse_fastq_dev, path, out); }
+
+extern "C" int lime_docs_from_fastq_qual_bytes_dev(lime_ctx *c, const uint8_t *d_bytes, uint64_t n, void *stream, lime_docs **out)
+{
+    return from_bytes_dev(c, "lime_docs_from_fastq_qual_bytes_dev", parse_fastq_qual_dev, d_bytes, n, stream, out);
+}
+extern "C" int lime_docs_from_fastq_qual_bytes(lime_ctx *c, const uint8_t *bytes, uint64_t n, lime_docs **out)
+{
+    return from_bytes(c, "lime_docs_from_fastq_qual_bytes", parse_fastq_qual_dev, bytes, n, out);
+}
+extern "C" int lime_docs_from_fastq_qual(lime_ctx *c, const char *path, lime_docs **out)
+{
+    return from_path(c, "lime_docs_from_fastq_qual", parse_fastq_qual_dev, path, out);
+}
 
 // the one place a sequence file's format is decided (lime_seq_format: the first byte)
 extern "C" int lime_docs_from_file(lime_ctx *c, const char *path, lime_docs **out)
@@ -332,6 +359,85 @@ extern "C" int lime_docs_get(const lime_docs *d, uint8_t *text, uint64_t *doc_of
     if (text && d->n_text && (rc = d2h_pageable(d->ctx, text, d->text.p, (size_t)d->n_text, nullptr))) return rc;
     if (doc_off && (rc = d2h_pageable(d->ctx, doc_off, d->doc_off.p, ((size_t)d->n_docs + 1) * 8, nullptr))) return rc;
     return LIME_OK;
+}
+
+extern "C" int lime_docs_qual_device(const lime_docs *d, const uint8_t **d_qual)
+{
+    if (!d || !d_qual) return fail(LIME_ERR_ARG, "lime_docs_qual_device: NULL argument");
+    *d_qual = d->qual.p;                                 // (NULL: documents without qualities)
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_get_qual(const lime_docs *d, uint8_t *qual)
+{
+    const char *who = "lime_docs_get_qual";
+    if (!d) return fail(LIME_ERR_ARG, "%s: the documents are NULL", who);
+    if (!d->qual.p) return fail(LIME_ERR_ARG, "%s: the documents hold no qualities (lime_docs_from_fastq_qual* keeps them)", who);
+    int rc = check_ctx(d->ctx, who); if (rc) return rc;
+    if (qual && d->n_text && (rc = d2h_pageable(d->ctx, qual, d->qual.p, (size_t)d->n_text, nullptr))) return rc;
+    return LIME_OK;
+}
+
+// ---- the quality trim (lime_fqtrim_kernel.hip: k_trim_bounds, k_trim_copy) ---------------------------------------------------------
+// Scratch: 12 bytes per read (lo, length, new offset) + rocPRIM's + two counters, given back before this returns.  The new lengths' total
+// sizes the handle: two synchronisations, like the parse
+int lime_host::docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t q5, uint32_t q3, hipStream_t st, lime_docs **out,
+                              lime_trim_info_t *info)
+{
+    const uint32_t nd = docs->n_docs;
+    lime_trim_info_t ti = {nd, 0, 0, docs->n_text, 0};
+    uint32_t n_out = 0;
+    uint64_t counts[2] = {0, 0};
+    DevBuf scratch;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t words = up(((size_t)nd + 1) * 4);
+    uint32_t *lo32 = nullptr, *len32 = nullptr, *new_off = nullptr;
+    uint64_t *d_counts = nullptr;
+    if (nd) {
+        size_t tmp_bytes = 0;
+        HIP_TRY(idx_scan_sum(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)nd + 1, false, st));
+        int rc = scratch.alloc(3 * words + 256 + up(tmp_bytes));
+        if (rc) return fail(rc, "%s: no device memory for the trim of %u reads: %s", who, nd, lime_last_error());
+        uint8_t *at = static_cast<uint8_t *>(scratch.p);
+        auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
+        lo32 = (uint32_t *)take(words); len32 = (uint32_t *)take(words); new_off = (uint32_t *)take(words);
+        d_counts = (uint64_t *)take(256);
+        void *tmp = take(up(tmp_bytes));
+        HIP_TRY(hipMemsetAsync(len32 + nd, 0, 4, st));   // (the 0 behind the last read's length: the sum's last entry is the total)
+        HIP_TRY(hipMemsetAsync(d_counts, 0, 16, st));
+        fqt_launch_bounds(docs->qual.p, docs->doc_off.p, nd, q5, q3, lo32, len32, d_counts, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(idx_scan_sum(tmp, &tmp_bytes, len32, new_off, (size_t)nd + 1, false, st));
+        HIP_TRY(hipMemcpyAsync(&n_out, new_off + nd, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));               // (the total sizes the handle)
+    }
+    DocsGuard dg;
+    int rc = docs_new(c, who, nd, n_out, dg); if (rc) return rc;
+    if (nd) {
+        fqt_launch_copy(docs->text.p, docs->doc_off.p, nd, lo32, len32, new_off, dg.d->text.p, dg.d->doc_off.p, st);
+        HIP_TRY(hipGetLastError());
+    } else {
+        HIP_TRY(hipMemsetAsync(dg.d->doc_off.p, 0, 8, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                   // (the scratch goes back when this returns)
+    ti.n_changed = counts[0]; ti.n_empty = counts[1]; ti.symbols_out = n_out;
+    if (info) *info = ti;
+    *out = dg.take();
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_trim_dev(lime_ctx *c, const lime_docs *docs, uint32_t q5, uint32_t q3, void *stream, lime_docs **out, lime_trim_info_t *info)
+{
+    const char *who = "lime_docs_trim_dev";
+    if (info) memset(info, 0, sizeof *info);
+    if (!c || !docs || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    *out = nullptr;
+    if (docs->ctx != c) return fail(LIME_ERR_ARG, "%s: the documents belong to another context", who);
+    if (q5 > 93 || q3 > 93) return fail(LIME_ERR_ARG, "%s: cutoffs %u,%u; a Phred+33 quality is 0 .. 93", who, q5, q3);
+    if (!docs->qual.p) return fail(LIME_ERR_ARG, "%s: the documents hold no qualities (lime_docs_from_fastq_qual* keeps them)", who);
+    int rc = check_ctx(c, who); if (rc) return rc;
+    return docs_trim_impl(c, who, docs, q5, q3, (hipStream_t)stream, out, info);
 }
 
 extern "C" void lime_docs_free(lime_docs *d)

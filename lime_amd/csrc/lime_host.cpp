@@ -255,11 +255,12 @@ extern "C" int lime_fasta_read(const char *path, int rc, uint8_t **text, uint64_
 // dropped, are the record's symbols as they are; the quality string only has to be as long as the sequence.  A line ends at its LF
 // or at the end of the file; what follows the last LF is a line only if it has a byte.  The first offending line is refused
 // (include/lime_hip.h lists the four reasons and their texts).  rc as in lime_fasta_read.
-extern "C" int lime_fastq_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs)
+// qual != NULL (lime_fastq_read_qual): the quality lines' bytes, CR dropped, too
+static int fastq_read_impl(const char *who, const char *path, int rc, uint8_t **text, uint8_t **qual, uint64_t **doc_off, uint32_t *n_docs)
 {
-    const char *who = "lime_fastq_read";
-    if (!path || !text || !doc_off || !n_docs) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument", who);
     *text = nullptr; *doc_off = nullptr; *n_docs = 0;
+    if (qual) *qual = nullptr;
+    std::vector<uint8_t> qsym;
     File in(path, "rb");
     if (!in.f) return lime_host::fail(LIME_ERR_IO, "%s: cannot open %s", who, path);
     uint8_t comp[256];
@@ -293,6 +294,7 @@ extern "C" int lime_fastq_read(const char *path, int rc, uint8_t **text, uint64_
             break;
         default:
             if (len != seq_len) return lime_host::fail(LIME_ERR_ARG, "%s: line %llu: quality length differs from sequence length", who, (unsigned long long)no);
+            if (qual) for (uint8_t ch : line) if (ch != '\r') qsym.push_back(ch);
             break;
         }
         line.clear();
@@ -315,10 +317,83 @@ extern "C" int lime_fastq_read(const char *path, int rc, uint8_t **text, uint64_
     const uint32_t nd = (uint32_t)(off.size() - 1);
     uint8_t *t = static_cast<uint8_t *>(malloc(sym.size() ? sym.size() : 1));
     uint64_t *o = static_cast<uint64_t *>(malloc(off.size() * 8));
+    uint8_t *q = qual ? static_cast<uint8_t *>(malloc(qsym.size() ? qsym.size() : 1)) : nullptr;
+    if (!t || !o || (qual && !q)) { free(t); free(o); free(q); return lime_host::fail(LIME_ERR_NOMEM, "%s: out of host memory", who); }
+    if (!sym.empty()) memcpy(t, sym.data(), sym.size());
+    if (q && !qsym.empty()) memcpy(q, qsym.data(), qsym.size());
+    memcpy(o, off.data(), off.size() * 8);
+    *text = t; *doc_off = o; *n_docs = nd;
+    if (qual) *qual = q;
+    return LIME_OK;
+}
+
+extern "C" int lime_fastq_read(const char *path, int rc, uint8_t **text, uint64_t **doc_off, uint32_t *n_docs)
+{
+    const char *who = "lime_fastq_read";
+    if (!path || !text || !doc_off || !n_docs) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    return fastq_read_impl(who, path, rc, text, nullptr, doc_off, n_docs);
+}
+
+extern "C" int lime_fastq_read_qual(const char *path, uint8_t **text, uint8_t **qual, uint64_t **doc_off, uint32_t *n_docs)
+{
+    const char *who = "lime_fastq_read_qual";
+    if (!path || !text || !qual || !doc_off || !n_docs) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    return fastq_read_impl(who, path, 0, text, qual, doc_off, n_docs);
+}
+
+// ---- the quality trim: the loop form of the rule (include/lime_hip.h), the oracle of lime_docs_trim_dev ------------------------
+extern "C" int lime_quality_trim(const uint8_t *text, const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t q5, uint32_t q3,
+                                 uint8_t **out_text, uint64_t **out_doc_off, lime_trim_info_t *info)
+{
+    const char *who = "lime_quality_trim";
+    if (out_text) *out_text = nullptr;
+    if (out_doc_off) *out_doc_off = nullptr;
+    if (info) memset(info, 0, sizeof *info);
+    if (!doc_off || !out_text || !out_doc_off) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (q5 > 93 || q3 > 93) return lime_host::fail(LIME_ERR_ARG, "%s: cutoffs %u,%u; a Phred+33 quality is 0 .. 93", who, q5, q3);
+    if (doc_off[0] != 0) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off does not start at 0", who);
+    for (uint32_t r = 0; r < n_docs; ++r)
+        if (doc_off[r + 1] < doc_off[r]) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off decreases at read %u", who, r);
+    if (doc_off[n_docs] && (!text || !qual)) return lime_host::fail(LIME_ERR_ARG, "%s: NULL array", who);
+    std::vector<uint8_t> sym;
+    std::vector<uint64_t> off;
+    off.reserve((size_t)n_docs + 1);
+    lime_trim_info_t ti = {n_docs, 0, 0, doc_off[n_docs], 0};
+    for (uint32_t r = 0; r < n_docs; ++r) {
+        const uint64_t a = doc_off[r], L = doc_off[r + 1] - a;
+        const uint8_t *b = qual + a;
+        uint64_t lo = 0, hi = L;
+        if (q3) {
+            int64_t s = 0, lowest = 0;
+            for (uint64_t i = L; i-- > 0; ) {
+                s += (int64_t)b[i] - 33 - (int64_t)q3;
+                if (s > 0) break;
+                if (s < lowest) { lowest = s; hi = i; }
+            }
+        }
+        if (q5) {
+            int64_t s = 0, highest = 0;
+            for (uint64_t i = 0; i < L; ++i) {
+                s += (int64_t)q5 - ((int64_t)b[i] - 33);
+                if (s < 0) break;
+                if (s > highest) { highest = s; lo = i + 1; }
+            }
+        }
+        off.push_back(sym.size());
+        const uint64_t len = lo < hi ? hi - lo : 0;
+        if (len) sym.insert(sym.end(), text + a + lo, text + a + hi);
+        ti.n_changed += len != L;
+        ti.n_empty += L != 0 && len == 0;
+    }
+    off.push_back(sym.size());
+    ti.symbols_out = sym.size();
+    uint8_t *t = static_cast<uint8_t *>(malloc(sym.size() ? sym.size() : 1));
+    uint64_t *o = static_cast<uint64_t *>(malloc(off.size() * 8));
     if (!t || !o) { free(t); free(o); return lime_host::fail(LIME_ERR_NOMEM, "%s: out of host memory", who); }
     if (!sym.empty()) memcpy(t, sym.data(), sym.size());
     memcpy(o, off.data(), off.size() * 8);
-    *text = t; *doc_off = o; *n_docs = nd;
+    *out_text = t; *out_doc_off = o;
+    if (info) *info = ti;
     return LIME_OK;
 }
 

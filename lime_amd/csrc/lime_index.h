@@ -102,6 +102,19 @@ void fq_launch_count(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint
 void fq_launch_write(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep, const uint32_t *off_diff,
                      uint32_t n_docs, uint8_t *text, uint64_t *doc_off, uint64_t *err, hipStream_t st);
 
+// ---- lime_fqtrim_kernel.hip: the quality bytes of a FASTQ parse, and the quality trim (lime_docs.cpp) ----
+// The parse's fourth pass, behind fq_launch_count's prefix sums: the quality bytes in order to qual (16-byte aligned); only qual[0 .. cap)
+// is written, whatever the input holds
+void fqt_launch_qual(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep, const uint32_t *off_diff, uint8_t *qual,
+                     uint64_t cap, hipStream_t st);
+// lo32[r], len32[r]: what the rule (include/lime_hip.h: lime_quality_trim) keeps of read r, text[doc_off[r] + lo32[r] .. + len32[r]);
+// counts[0] += the reads it changes, counts[1] += the reads with symbols of which it keeps none.  q5, q3 <= 93
+void fqt_launch_bounds(const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t q5, uint32_t q3, uint32_t *lo32, uint32_t *len32,
+                       uint64_t *counts, hipStream_t st);
+// new_off = the exclusive sum of len32 over n_docs + 1 entries (a 0 appended).  out (new_off[n_docs] bytes) and out_off[n_docs + 1] are written
+void fqt_launch_copy(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint32_t *lo32, const uint32_t *len32, const uint32_t *new_off,
+                     uint8_t *out, uint64_t *out_off, hipStream_t st);
+
 // ---- lime_seqcut_kernel.hip: where a window of a reads file is cut into whole records (lime_reader.cpp) ----
 // The same blocks; the markers and the rule are at the head of the kernel file.  cnt[k] = the line-first '>' of block k (FASTQ counts
 // its markers with fq_launch_lines)

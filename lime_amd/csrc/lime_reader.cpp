@@ -230,9 +230,19 @@ static int reader_next(lime_seq_reader *r, const char *who, uint32_t max_reads, 
         if (cut[0] > n) return fail(LIME_ERR_HIP, "%s: the cut lies behind the window", who);
         lime_docs *d = nullptr;
         const uint8_t *b = r->win.p + r->start;
-        if (r->format) rc = docs_parse_fastq_dev(r->ctx, who, b, cut[0], r->n_lines, nullptr, &d);
+        if (r->format) rc = docs_parse_fastq_dev(r->ctx, who, b, cut[0], r->n_lines, nullptr, &d, r->trim);
         else rc = docs_parse_fasta_dev(r->ctx, who, b, cut[0], nullptr, &d);
         if (rc) return rc;
+        if (r->trim) {                                   // the batch as it is handed out: trimmed, without qualities
+            lime_docs *t = nullptr;
+            lime_trim_info_t ti;
+            rc = docs_trim_impl(r->ctx, who, d, r->q5, r->q3, nullptr, &t, &ti);
+            lime_docs_free(d);
+            if (rc) return rc;
+            d = t;
+            r->trimmed.n_reads += ti.n_reads; r->trimmed.n_changed += ti.n_changed; r->trimmed.n_empty += ti.n_empty;
+            r->trimmed.symbols_in += ti.symbols_in; r->trimmed.symbols_out += ti.symbols_out;
+        }
         uint32_t nd = 0;
         lime_docs_info(d, &nd, nullptr);
         if (r->n_records + nd > 0xFFFFFFFFull) {
@@ -257,9 +267,28 @@ extern "C" int lime_seq_reader_next(lime_seq_reader *r, uint32_t max_reads, lime
     if (!max_reads) return fail(LIME_ERR_ARG, "%s: max_reads is 0", who);
     if (r->failed) return fail(r->failed, "%s", r->failure.c_str());
     int rc = check_ctx(r->ctx, who); if (rc) return rc;
+    r->asked = true;
     rc = reader_next(r, who, max_reads, docs, first_record);
     if (rc == LIME_ERR_ARG) { r->failed = rc; r->failure = lime_last_error(); }     // a refusal of the file is final
     return rc;
+}
+
+extern "C" int lime_seq_reader_set_trim(lime_seq_reader *r, uint32_t q5, uint32_t q3)
+{
+    const char *who = "lime_seq_reader_set_trim";
+    if (!r) return fail(LIME_ERR_ARG, "%s: the reader is NULL", who);
+    if (!r->format) return fail(LIME_ERR_ARG, "%s: the reader's file is FASTA; only FASTQ holds qualities", who);
+    if (q5 > 93 || q3 > 93) return fail(LIME_ERR_ARG, "%s: cutoffs %u,%u; a Phred+33 quality is 0 .. 93", who, q5, q3);
+    if (r->asked) return fail(LIME_ERR_ARG, "%s: the reader has handed out records already; the trim is set before the first lime_seq_reader_next", who);
+    r->trim = true; r->q5 = q5; r->q3 = q3;
+    return LIME_OK;
+}
+
+extern "C" int lime_seq_reader_trim_info(const lime_seq_reader *r, lime_trim_info_t *info)
+{
+    if (!r || !info) return fail(LIME_ERR_ARG, "lime_seq_reader_trim_info: NULL argument");
+    *info = r->trimmed;
+    return LIME_OK;
 }
 
 extern "C" int lime_seq_reader_info(const lime_seq_reader *r, int *format, uint64_t *n_records, uint64_t *n_lines, uint64_t *n_bytes, uint64_t *window_bytes)
