@@ -554,6 +554,21 @@ int lime_fastq_read_qual(const char *path, uint8_t **text, uint8_t **qual, uint6
 typedef struct { uint64_t n_reads, n_changed, n_empty, symbols_in, symbols_out; } lime_trim_info_t;
 int lime_quality_trim(const uint8_t *text, const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t q5, uint32_t q3,
                       uint8_t **out_text, uint64_t **out_doc_off, lime_trim_info_t *info);
+/* Adapter trimming: a 3' adapter with mismatches only and no indels, the leftmost match (cutadapt's `-a ADAPTER --no-indels`; the simple
+ * mode of fastp and Trimmomatic).  Integers only.  The read is s[0 .. L), the adapter a[0 .. M) with 1 <= M <= 64, every byte of it one
+ * of ACGT after folding with & 0xDF (acgt are taken as ACGT).  min_overlap O, 1 <= O <= M (LiME_fasta's default: 3); max_err_pct E, whole
+ * percent, 0 <= E <= 50 (default: 10).
+ *   For a start p in [0, L): k(p) = min(M, L - p), the places at which read and adapter overlap; mm(p) = the number of j < k(p) with
+ *   (s[p + j] & 0xDF) != a[j] -- lower case in the read matches; N, IUPAC codes and every other byte are mismatches.
+ *   p is a hit when k(p) >= O and mm(p) <= (k(p) * E) / 100 by integer division.
+ *   The read keeps s[0 .. p*), p* the SMALLEST hit; without a hit it is unchanged.  p* = 0 leaves an empty read.
+ * Read indices never change, as for lime_quality_trim: an emptied read is an empty document and no read is dropped.
+ * lime_adapter_trim is the loop form in plain host code, the oracle of lime_docs_trim_adapter_dev: text / doc_off[n_docs + 1] as the
+ * readers give them; *out_text (at least one byte) and *out_doc_off[n_docs + 1] are library-owned (lime_free); info may be NULL.
+ * LIME_ERR_ARG with a text: a NULL array, m of 0 or above 64, an adapter byte outside ACGTacgt, min_overlap of 0 or above m,
+ * max_err_pct above 50, doc_off that does not start at 0 or decreases. */
+int lime_adapter_trim(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint8_t *adapter, uint32_t m, uint32_t min_overlap,
+                      uint32_t max_err_pct, uint8_t **out_text, uint64_t **out_doc_off, lime_trim_info_t *info);
 /* *format = 1 (FASTQ) if the file's first byte is '@', else 0 (FASTA: an empty file and text in front of the first header included).
  * LIME_ERR_IO when the file cannot be read.  Pure host code. */
 int lime_seq_format(const char *path, int *format);
@@ -662,6 +677,16 @@ int  lime_docs_get_qual(const lime_docs *docs, uint8_t *qual);
  * before the call returns.  LIME_ERR_ARG with a text, before any launch: documents without qualities, a cutoff above 93, documents of
  * another context.  On every error nothing stays allocated and *out is NULL.  Synchronises `stream`. */
 int  lime_docs_trim_dev(lime_ctx *ctx, const lime_docs *docs, uint32_t q5, uint32_t q3, void *stream, lime_docs **out, lime_trim_info_t *info);
+/* The documents cut by the rule at lime_adapter_trim, on the device: *out = new documents (the caller's; no qualities) whose text and
+ * doc_off are byte for byte lime_adapter_trim's, *info (may be NULL) its counts.  Any documents are taken: of a FASTA or FASTQ parse, with
+ * or without qualities, or lime_docs_trim_dev's.  k_adapter_bounds (lime_adapter_kernel.hip) finds p* of every read -- one wave on a
+ * read, 64 symbols a step, the read as four 64-bit words of ballots against the adapter's four masks -- and the prefix sum and
+ * k_trim_copy of lime_docs_trim_dev follow.  Device memory next to the two handles: 12 bytes per read + the prefix sum's, given back
+ * before the call returns.  LIME_ERR_ARG with a text, before any launch: a NULL argument, documents of another context, m of 0 or above
+ * 64, an adapter byte outside ACGTacgt, min_overlap of 0 or above m, max_err_pct above 50.  On every error nothing stays allocated and
+ * *out is NULL.  Synchronises `stream`. */
+int  lime_docs_trim_adapter_dev(lime_ctx *ctx, const lime_docs *docs, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct,
+                                void *stream, lime_docs **out, lime_trim_info_t *info);
 /* lime_docs_from_fastq or lime_docs_from_fasta, by lime_seq_format(path): the one place a file's format is decided */
 int  lime_docs_from_file(lime_ctx *ctx, const char *path, lime_docs **out);
 /* documents that are parsed already (copied); doc_off is checked on the device by lime_build_index's rules: LIME_ERR_ARG */
@@ -769,6 +794,13 @@ int  lime_seq_reader_info(const lime_seq_reader *r, int *format, uint64_t *n_rec
  * far (zeros without set_trim). */
 int  lime_seq_reader_set_trim(lime_seq_reader *r, uint32_t q5, uint32_t q3);
 int  lime_seq_reader_trim_info(const lime_seq_reader *r, lime_trim_info_t *info);
+/* set_adapter: from here on every batch is handed out cut at its reads' adapters (lime_docs_trim_adapter_dev), a FASTA reader's too.  With
+ * set_trim as well every batch is quality-trimmed first and adapter-trimmed second (the order of an outside trimmer, and the only one:
+ * the quality trim's output holds no qualities).  The batches, concatenated, are the whole file's trimmed documents.  LIME_ERR_ARG with a
+ * text: the adapter's refusals as above, a reader whose lime_seq_reader_next has been called.  adapter_info: the sums over the batches
+ * handed out so far (zeros without set_adapter); symbols_in counts what the adapter trim was given, the quality trim's output included. */
+int  lime_seq_reader_set_adapter(lime_seq_reader *r, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct);
+int  lime_seq_reader_adapter_info(const lime_seq_reader *r, lime_trim_info_t *info);
 void lime_seq_reader_close(lime_seq_reader *r);
 
 /* lime_classify_sample_dev batch by batch: per batch, batch_reads (>= 1) records from each of the n_mates readers, one unchanged

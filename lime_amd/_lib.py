@@ -165,6 +165,10 @@ SYMBOLS = {
     "lime_docs_trim_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _pp, C.POINTER(TrimInfo)]),
     "lime_seq_reader_set_trim": (_i, [_vp, _u32, _u32]),
     "lime_seq_reader_trim_info": (_i, [_vp, C.POINTER(TrimInfo)]),
+    "lime_adapter_trim": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _pp, _pp, C.POINTER(TrimInfo)]),
+    "lime_docs_trim_adapter_dev": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _pp, C.POINTER(TrimInfo)]),
+    "lime_seq_reader_set_adapter": (_i, [_vp, _vp, _u32, _u32, _u32]),
+    "lime_seq_reader_adapter_info": (_i, [_vp, C.POINTER(TrimInfo)]),
     "lime_docs_from_file": (_i, [_vp, C.c_char_p, _pp]),
     "lime_docs_from_arrays_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _pp]),
     "lime_docs_revcomp": (_i, [_vp, _vp, _vp, _pp]),

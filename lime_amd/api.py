@@ -497,6 +497,14 @@ class Context:
         check(self.lib.lime_docs_trim_dev(self.h, docs.h, int(q5), int(q3), stream, C.byref(h), C.byref(ti)))
         return self._docs_of(h), _trim_info(ti)
 
+    def docs_trim_adapter(self, docs, adapter, min_overlap=3, max_err_pct=10, stream=None):
+        """any Docs cut where the 3' adapter (str or bytes, 1 .. 64 of ACGT) begins in each read (lime_docs_trim_adapter_dev; the rule is at
+        lime_adapter_trim in include/lime_hip.h) -> (Docs without qualities, info: dict as docs_trim gives)"""
+        a = _adapter_bytes(adapter)
+        h, ti = C.c_void_p(), _lib.TrimInfo()
+        check(self.lib.lime_docs_trim_adapter_dev(self.h, docs.h, a, len(a), int(min_overlap), int(max_err_pct), stream, C.byref(h), C.byref(ti)))
+        return self._docs_of(h), _trim_info(ti)
+
     def docs_from_file(self, path):
         """a FASTA or FASTQ file, by seq_format(path) -> Docs"""
         h = C.c_void_p()
@@ -615,6 +623,21 @@ def _trim_info(ti):
     return {k: int(getattr(ti, k)) for k, _ in _lib.TrimInfo._fields_}
 
 
+def _adapter_bytes(adapter):
+    return adapter.encode("latin-1") if isinstance(adapter, str) else bytes(adapter)
+
+
+def _adapters(trim_adapter, n_reads):
+    """SEQ, "SEQ,SEQ2" or (SEQ, SEQ2) -> one adapter per reads file, as `--trim-adapter` reads them"""
+    ad = trim_adapter.split(",") if isinstance(trim_adapter, str) else ([trim_adapter] if isinstance(trim_adapter, bytes) else list(trim_adapter))
+    ad = [_adapter_bytes(x) for x in ad]
+    if len(ad) not in (1, 2) or any(not 1 <= len(x) <= 64 or any(chr(b & 0xDF) not in "ACGT" for b in x) for x in ad):
+        raise ValueError("trim_adapter is SEQ or (SEQ, SEQ2), each 1 .. 64 of ACGT")
+    if len(ad) == 2 and n_reads != 2:
+        raise ValueError("trim_adapter: a second adapter needs a second reads file")
+    return ad * 2 if len(ad) == 1 else ad
+
+
 def _trim_cutoffs(trim_qual):
     """Q, "Q", (Q5, Q3) or "Q5,Q3" -> (q5, q3), as `--trim-qual` reads them"""
     if isinstance(trim_qual, str):
@@ -655,6 +678,18 @@ class SeqReader:
     def set_trim(self, q5, q3):
         """every batch from here on is parsed with its qualities and handed out trimmed (lime_seq_reader_set_trim: before the first next, FASTQ only)"""
         check(self.ctx.lib.lime_seq_reader_set_trim(self.h, int(q5), int(q3)))
+
+    def set_adapter(self, adapter, min_overlap=3, max_err_pct=10):
+        """every batch from here on is handed out cut at its reads' adapters, behind the quality trim where set_trim is set too
+        (lime_seq_reader_set_adapter: before the first next; FASTA or FASTQ)"""
+        a = _adapter_bytes(adapter)
+        check(self.ctx.lib.lime_seq_reader_set_adapter(self.h, a, len(a), int(min_overlap), int(max_err_pct)))
+
+    def adapter_info(self):
+        """the adapter trim's counts summed over the batches handed out so far -> dict as Context.docs_trim gives"""
+        ti = _lib.TrimInfo()
+        check(self.ctx.lib.lime_seq_reader_adapter_info(self.h, C.byref(ti)))
+        return _trim_info(ti)
 
     def trim_info(self):
         """the trim's counts summed over the batches handed out so far -> dict as Context.docs_trim gives"""
@@ -1038,6 +1073,22 @@ def quality_trim(text, qual, doc_off, q5, q3):
     return new_text, new_off, _trim_info(ti)
 
 
+def adapter_trim(text, doc_off, adapter, min_overlap=3, max_err_pct=10):
+    """the adapter rule in plain host code (lime_adapter_trim) -> (text, doc_off, info dict)"""
+    lib = _lib.load()
+    t = np.ascontiguousarray(text, dtype=np.uint8); off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    a = _adapter_bytes(adapter)
+    pt, po, ti = C.c_void_p(), C.c_void_p(), _lib.TrimInfo()
+    check(lib.lime_adapter_trim(t.ctypes.data if len(t) else None, off.ctypes.data, len(off) - 1, a, len(a), int(min_overlap), int(max_err_pct),
+                                C.byref(pt), C.byref(po), C.byref(ti)))
+    try:
+        new_off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(len(off),)).copy()
+        new_text = np.frombuffer(C.string_at(pt, int(new_off[-1])), dtype=np.uint8).copy()
+    finally:
+        lib.lime_free(pt); lib.lime_free(po)
+    return new_text, new_off, _trim_info(ti)
+
+
 def seq_format(path):
     """"fastq" if the file's first byte is '@', else "fasta" (lime_seq_format)"""
     f = C.c_int(0)
@@ -1125,7 +1176,8 @@ def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, thread
 
 
 def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16, beta=0.25, rank=1, trlcp=0, ebwt=True, higher=False, binary=True,
-               ctx=None, batch_reads=0, window_bytes=0, trim_qual=None):
+               ctx=None, batch_reads=0, window_bytes=0, trim_qual=None, trim_adapter=None,
+               adapter_overlap=3, adapter_error=10):
     """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen (L | auto) --out output
     [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta (read_len="auto": every read by its own length): the files are parsed on the device (each reads file
     FASTA or four-line FASTQ, by its first byte; refs FASTA), the
@@ -1133,6 +1185,9 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     repeated `--gidx`), only `output` is written.  batch_reads > 0: `--batch-reads N [--window-bytes W]`,
     the sample read and classified N reads at a time, `output` appended to batch by batch and renamed at the end.  trim_qual: `--trim-qual`,
     Q (the 3' end) or (Q5, Q3): the reads, FASTQ, are cut by the quality rule on the device first; read_len must be "auto".
+    trim_adapter: `--trim-adapter`, SEQ or (SEQ, SEQ2) (SEQ2 for the second reads file), with adapter_overlap and adapter_error
+    (`--adapter-overlap`, `--adapter-error`): the reads, FASTA or FASTQ, are cut where the 3' adapter begins, behind the quality trim;
+    read_len must be "auto".
     -> counts {C, U, A, H}"""
     reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
     if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
@@ -1144,6 +1199,12 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
         for r in reads:
             if seq_format(r) != "fastq":
                 raise ValueError(f"LiME_fasta: {os.fspath(r)}: trim_qual needs the qualities of a FASTQ file; this one is FASTA")
+    if trim_adapter is not None:
+        adapters = _adapters(trim_adapter, len(reads))
+        if read_len != "auto":
+            raise ValueError("LiME_fasta: trim_adapter needs read_len=\"auto\": a fixed norm does not fit trimmed reads")
+        if not 1 <= int(adapter_overlap) <= min(len(a) for a in adapters) or not 0 <= int(adapter_error) <= 50:
+            raise ValueError("LiME_fasta: adapter_overlap is 1 .. the adapter's length, adapter_error 0 .. 50")
     norm = NORM_PER_READ if read_len == "auto" else ((int(read_len) & 0xFF) + 1 - int(alpha)) & 0xFFFFFFFF     # (`--readlen auto`)
     own = ctx is None
     ctx = ctx or Context()
@@ -1162,6 +1223,13 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
                 raw.close()
         else:
             mates = [ctx.docs_from_file(r) for r in reads]
+        if trim_adapter is not None:
+            for k, m in enumerate(mates):
+                if batch_reads:
+                    m.set_adapter(adapters[k], adapter_overlap, adapter_error)
+                else:
+                    mates[k] = ctx.docs_trim_adapter(m, adapters[k], adapter_overlap, adapter_error)[0]
+                    m.close()
         if refs is not None:
             g = ctx.docs_from_fasta(refs)
             nd, nt = g.info()

@@ -1,6 +1,7 @@
 // LiME_fasta -- Preprocessing.sh + LiME_paired.sh for one sample, from FASTA or FASTQ files, as ONE process with nothing on disk in between:
 //   LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
 //              [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]
+//              [--trim-adapter SEQ[,SEQ2] [--adapter-overlap O] [--adapter-error E]]
 // Each reads file is FASTA or four-line FASTQ, decided by its first byte ('@': FASTQ; lime_docs_from_file), the mates each on their own;
 // --refs is FASTA.  The files' bytes go to the device as they are and are parsed there; per collection (reads_1, its reverse
 // complements, reads_2, its reverse complements: the script's `seqtk seq -r`) the reads are merged into the genome index, scanned and
@@ -26,6 +27,12 @@
 // complements are made from the trimmed reads, an emptied read stays in its place as an empty read (verdict U), and the 255-symbol limit
 // holds for the trimmed length.  Per reads file one line is printed: the reads changed and emptied, the symbols before and after (with
 // --batch-reads: summed over the batches).  Nothing else is written.
+// --trim-adapter SEQ: every read is cut where the 3' adapter SEQ (1 .. 64 of ACGT) begins in it, by the rule at lime_adapter_trim in
+// include/lime_hip.h (mismatches only, the leftmost match; a match is at least --adapter-overlap O symbols long, default 3, with at most
+// E percent of them wrong, --adapter-error E, 0 .. 50, default 10), on the device.  SEQ,SEQ2: SEQ2 for reads_2 (the R1 and R2 adapters of a
+// kit differ); one SEQ serves every mate.  FASTA and FASTQ reads files are taken; --readlen must be auto, for --trim-qual's reason.  With
+// --trim-qual every read is cut by quality first and at its adapter second.  The rest is as for --trim-qual: each mate on its own, the
+// reverse complements from the trimmed reads, an emptied read stays in its place, one line of counts per reads file.
 // The defaults are the script's constants (LiME_paired.sh:21-23); norm = readLen + 1 - alpha (ClusterBWT_DA.cpp:555).  The reference's
 // compile-time switches are environment variables, as for the other drop-ins: LIME_EBWT (default 1), LIME_BIN (default 1), LIME_HIGHER (0).
 #include <string.h>
@@ -55,6 +62,26 @@ static void print_trim(const char *file, unsigned q5, unsigned q3, const lime_tr
 {
     std::cout << file << ": quality trim " << q5 << "," << q3 << ": " << t.n_changed << " of " << t.n_reads << " reads changed, " << t.n_empty << " emptied, "
               << t.symbols_in << " symbols before, " << t.symbols_out << " after." << std::endl;
+}
+
+// "SEQ" or "SEQ,SEQ2": 1 .. 64 of ACGTacgt each
+static bool parse_adapters(const char *s, std::string ad[2], int *n)
+{
+    const char *comma = strchr(s, ',');
+    ad[0] = comma ? std::string(s, comma) : std::string(s);
+    ad[1] = comma ? std::string(comma + 1) : std::string();
+    *n = comma ? 2 : 1;
+    for (int k = 0; k < *n; ++k) {
+        if (ad[k].empty() || ad[k].size() > 64) return false;
+        for (char ch : ad[k]) if (!memchr("ACGT", ch & 0xDF, 4)) return false;
+    }
+    return true;
+}
+
+static void print_adapter(const char *file, const std::string &ad, unsigned overlap, unsigned err, const lime_trim_info_t &t)
+{
+    std::cout << file << ": adapter trim " << ad << " (overlap " << overlap << ", error " << err << "%): " << t.n_changed << " of " << t.n_reads << " reads changed, "
+              << t.n_empty << " emptied, " << t.symbols_in << " symbols before, " << t.symbols_out << " after." << std::endl;
 }
 
 static int env_flag(const char *name, int dflt)
@@ -95,6 +122,10 @@ int main(int argc, char **argv)
     const char *refs = nullptr, *lineage = nullptr, *output = nullptr;
     unsigned alpha = 16, rank = 1, trlcp = 0, batch_reads = 0, q5 = 0, q3 = 0;
     bool trim = false;
+    std::string adapters[2];                   // --trim-adapter: [0] for reads_1 (and reads_2 when one is given), [1] for reads_2
+    int n_adapters = 0;
+    unsigned ad_overlap = 3, ad_err = 10;
+    bool have_ad_opt = false;
     unsigned long long window_bytes = 0;
     bool batched = false, have_window = false;
     float beta = 0.25f;
@@ -117,15 +148,25 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--trlcp")) { if (more && sscanf(argv[i + 1], "%u", &trlcp) == 1) ++i; else bad = true; }
         else if (!strcmp(argv[i], "--batch-reads")) { if (more && sscanf(argv[i + 1], "%u", &batch_reads) == 1 && batch_reads) { ++i; batched = true; } else bad = true; }
         else if (!strcmp(argv[i], "--trim-qual")) { if (more && parse_trim(argv[i + 1], &q5, &q3)) { ++i; trim = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--trim-adapter")) { if (more && parse_adapters(argv[i + 1], adapters, &n_adapters)) ++i; else bad = true; }
+        else if (!strcmp(argv[i], "--adapter-overlap")) { if (more && sscanf(argv[i + 1], "%u", &ad_overlap) == 1 && ad_overlap) { ++i; have_ad_opt = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--adapter-error")) { if (more && sscanf(argv[i + 1], "%u", &ad_err) == 1 && ad_err <= 50) { ++i; have_ad_opt = true; } else bad = true; }
         else if (!strcmp(argv[i], "--window-bytes")) { if (more && sscanf(argv[i + 1], "%llu", &window_bytes) == 1 && window_bytes) { ++i; have_window = true; } else bad = true; }
         else reads.push_back(argv[i]);
     }
     if (have_window && !batched) bad = true;
     if (trim && !len_auto) bad = true;             // (a fixed norm on trimmed reads)
+    const bool cut_adapter = n_adapters > 0;
+    if (cut_adapter && !len_auto) bad = true;      // (the same)
+    if (have_ad_opt && !cut_adapter) bad = true;
+    if (n_adapters == 2 && reads.size() != 2) bad = true;
+    for (int k = 0; k < n_adapters; ++k) if (ad_overlap > adapters[k].size()) bad = true;
+    if (n_adapters == 1) adapters[1] = adapters[0];
     if (reads.empty() || reads.size() > 2 || !refs == gidx.empty() || !lineage || !output || !have_len) bad = true;
     if (bad) {
         std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx [--gidx next.gidx ...]) --lineage LineageFile --readlen (L | auto) --out output\n"
                   << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]\n"
+                  << "           [--trim-adapter SEQ[,SEQ2] [--adapter-overlap 3] [--adapter-error 10]]\n"
                   << "  classifies the reads of one sample (one file: single-end, two: paired-end) against the genomes of refs.fasta, or of an\n"
                   << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  A reads file is FASTA or\n"
                   << "  four-line FASTQ, by its first byte ('@': FASTQ), each mate on its own; refs.fasta is FASTA.  --trlcp k: lcp values\n"
@@ -140,6 +181,10 @@ int main(int argc, char **argv)
                   << "  --trim-qual Q: every read is cut at its 3' end by the BWA / cutadapt quality rule, cutoff Q (0 .. 93, Phred+33), on the\n"
                   << "  device; Q5,Q3: at both ends.  The reads files must be FASTQ and --readlen must be auto; one line per reads file\n"
                   << "  gives the reads changed and emptied and the symbols before and after.\n"
+                  << "  --trim-adapter SEQ: every read is cut where the 3' adapter SEQ (1 .. 64 of ACGT) begins in it: mismatches only, the\n"
+                  << "  leftmost match of at least --adapter-overlap O symbols (1 .. the adapter's length) with at most --adapter-error E percent\n"
+                  << "  of them wrong (0 .. 50), on the device; SEQ,SEQ2: SEQ2 for reads_2.  FASTA or FASTQ; --readlen must be auto; behind\n"
+                  << "  --trim-qual where both are given; one line of counts per reads file.\n"
                   << "  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
@@ -186,6 +231,9 @@ int main(int argc, char **argv)
         const int rc = lime_seq_reader_open(ctx, reads[m], window_bytes, &readers[m]);
         if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
         if (trim && lime_seq_reader_set_trim(readers[m], q5, q3) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
+        if (cut_adapter && lime_seq_reader_set_adapter(readers[m], (const uint8_t *)adapters[m].data(), (uint32_t)adapters[m].size(), ad_overlap, ad_err) != LIME_OK) {
+            std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1;
+        }
     }
     for (uint32_t m = 0; m < n_mates && !batched; ++m) {
         int rc;
@@ -198,6 +246,14 @@ int main(int argc, char **argv)
                 if (rc == LIME_OK) print_trim(reads[m], q5, q3, ti);
             }
         } else rc = lime_docs_from_file(ctx, reads[m], &mates[m]);
+        if (rc == LIME_OK && cut_adapter) {        // the reads as parsed or as the quality trim left them, then cut at their adapters
+            lime_docs *whole = mates[m];
+            lime_trim_info_t ti;
+            mates[m] = nullptr;
+            rc = lime_docs_trim_adapter_dev(ctx, whole, (const uint8_t *)adapters[m].data(), (uint32_t)adapters[m].size(), ad_overlap, ad_err, nullptr, &mates[m], &ti);
+            lime_docs_free(whole);
+            if (rc == LIME_OK) print_adapter(reads[m], adapters[m], ad_overlap, ad_err, ti);
+        }
         if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
     }
     if (!batched) { uint32_t nd = 0; lime_docs_info(mates[0], &nd, nullptr); numReads = nd; }
@@ -256,6 +312,11 @@ int main(int argc, char **argv)
             lime_trim_info_t ti;
             lime_seq_reader_trim_info(readers[m], &ti);
             print_trim(reads[m], q5, q3, ti);
+        }
+        for (uint32_t m = 0; m < n_mates && cut_adapter; ++m) {
+            lime_trim_info_t ti;
+            lime_seq_reader_adapter_info(readers[m], &ti);
+            print_adapter(reads[m], adapters[m], ad_overlap, ad_err, ti);
         }
         clk.mark("batches: reads, collections, classification");
         if (lime_classification_writer_close(sink.w, 1) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }

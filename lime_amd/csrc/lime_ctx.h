@@ -240,6 +240,8 @@ struct __attribute__((visibility("hidden"))) lime_seq_reader {
     bool asked = false;                     // lime_seq_reader_next has been called
     bool trim = false; uint32_t q5 = 0, q3 = 0;            // lime_seq_reader_set_trim: every batch is parsed with its qualities and trimmed
     lime_trim_info_t trimmed = {0, 0, 0, 0, 0};            // summed over the batches handed out
+    bool adapter = false; uint64_t ad_masks[4] = {0, 0, 0, 0}; uint32_t ad_m = 0, ad_overlap = 0, ad_err = 0;     // lime_seq_reader_set_adapter: every
+    lime_trim_info_t ad_trimmed = {0, 0, 0, 0, 0};         // batch is cut at its reads' adapters (behind the quality trim, where both are set)
     ~lime_seq_reader();
 };
 
@@ -292,6 +294,11 @@ int docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, u
                          bool with_qual = false);
 // lime_docs.cpp: lime_docs_trim_dev without its argument checks
 int docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t q5, uint32_t q3, hipStream_t st, lime_docs **out, lime_trim_info_t *info);
+// lime_docs.cpp: the adapter's refusals (LIME_ERR_ARG with a text) and its four masks, bit j of masks[b] set where symbol j is "ACGT"[b];
+// lime_docs_trim_adapter_dev without its argument checks
+int adapter_masks(const char *who, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct, uint64_t masks[4]);
+int docs_adapter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const uint64_t masks[4], uint32_t m, uint32_t min_overlap, uint32_t max_err_pct,
+                      hipStream_t st, lime_docs **out, lime_trim_info_t *info);
 // lime_docs.cpp: the genome side's refusals of the sample calls, with one index or with shards (the read sets' own come between the two)
 int sample_check_shards(const char *who, lime_ctx *c, uint32_t n_shards, const lime_gindex *const *shards);
 int sample_check_rules(const char *who, uint32_t n_shards, const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha,

@@ -1,6 +1,6 @@
 // lime_docs.cpp -- document collections that stay in HBM (lime_docs: made from the raw bytes of a FASTA or FASTQ file by the kernels of
 // lime_fasta_kernel.hip / lime_fastq_kernel.hip, or copied from parsed arrays), their reverse complements, FASTQ reads with their quality strings and
-// the quality trim (lime_fqtrim_kernel.hip), and a whole sample from documents to verdicts
+// the quality trim (lime_fqtrim_kernel.hip), the adapter trim (lime_adapter_kernel.hip), and a whole sample from documents to verdicts
 // (lime_classify_sample_dev: per collection the merge into the genome index, the scan and clusterChoose, then Classify over the lists).
 // include/lime_hip.h states the contract.
 #include <hip/hip_runtime.h>
@@ -378,53 +378,118 @@ extern "C" int lime_docs_get_qual(const lime_docs *d, uint8_t *qual)
     return LIME_OK;
 }
 
-// ---- the quality trim (lime_fqtrim_kernel.hip: k_trim_bounds, k_trim_copy) ---------------------------------------------------------
-// Scratch: 12 bytes per read (lo, length, new offset) + rocPRIM's + two counters, given back before this returns.  The new lengths' total
+// ---- the quality trim (lime_fqtrim_kernel.hip: k_trim_bounds, k_trim_copy) and the adapter trim (lime_adapter_kernel.hip: k_adapter_bounds) ----
+// Scratch: 12 bytes per read (lo, length, new offset) + rocPRIM's + two counters, given back before either returns.  The new lengths' total
 // sizes the handle: two synchronisations, like the parse
-int lime_host::docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t q5, uint32_t q3, hipStream_t st, lime_docs **out,
-                              lime_trim_info_t *info)
+namespace {
+struct TrimScratch {                                     // what a bounds kernel fills and trim_finish reads
+    DevBuf buf;
+    uint32_t *lo32 = nullptr, *len32 = nullptr, *new_off = nullptr;
+    uint64_t *d_counts = nullptr;
+    void *tmp = nullptr;
+    size_t tmp_bytes = 0;
+};
+}
+
+// nd >= 1 reads: the arrays, with the 0 behind the last read's length and the counters cleared
+static int trim_begin(const char *who, uint32_t nd, hipStream_t st, TrimScratch &ts)
+{
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t words = up(((size_t)nd + 1) * 4);
+    HIP_TRY(idx_scan_sum(nullptr, &ts.tmp_bytes, nullptr, nullptr, (size_t)nd + 1, false, st));
+    int rc = ts.buf.alloc(3 * words + 256 + up(ts.tmp_bytes));
+    if (rc) return fail(rc, "%s: no device memory for the trim of %u reads: %s", who, nd, lime_last_error());
+    uint8_t *at = static_cast<uint8_t *>(ts.buf.p);
+    auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
+    ts.lo32 = (uint32_t *)take(words); ts.len32 = (uint32_t *)take(words); ts.new_off = (uint32_t *)take(words);
+    ts.d_counts = (uint64_t *)take(256);
+    ts.tmp = take(up(ts.tmp_bytes));
+    HIP_TRY(hipMemsetAsync(ts.len32 + nd, 0, 4, st));    // (the 0 behind the last read's length: the sum's last entry is the total)
+    HIP_TRY(hipMemsetAsync(ts.d_counts, 0, 16, st));
+    return LIME_OK;
+}
+
+// behind a bounds kernel's launch (none for no reads): the prefix sum, the total, the handle, the copy and the counts
+static int trim_finish(lime_ctx *c, const char *who, const lime_docs *docs, TrimScratch &ts, hipStream_t st, lime_docs **out, lime_trim_info_t *info)
 {
     const uint32_t nd = docs->n_docs;
     lime_trim_info_t ti = {nd, 0, 0, docs->n_text, 0};
     uint32_t n_out = 0;
     uint64_t counts[2] = {0, 0};
-    DevBuf scratch;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t words = up(((size_t)nd + 1) * 4);
-    uint32_t *lo32 = nullptr, *len32 = nullptr, *new_off = nullptr;
-    uint64_t *d_counts = nullptr;
     if (nd) {
-        size_t tmp_bytes = 0;
-        HIP_TRY(idx_scan_sum(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)nd + 1, false, st));
-        int rc = scratch.alloc(3 * words + 256 + up(tmp_bytes));
-        if (rc) return fail(rc, "%s: no device memory for the trim of %u reads: %s", who, nd, lime_last_error());
-        uint8_t *at = static_cast<uint8_t *>(scratch.p);
-        auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
-        lo32 = (uint32_t *)take(words); len32 = (uint32_t *)take(words); new_off = (uint32_t *)take(words);
-        d_counts = (uint64_t *)take(256);
-        void *tmp = take(up(tmp_bytes));
-        HIP_TRY(hipMemsetAsync(len32 + nd, 0, 4, st));   // (the 0 behind the last read's length: the sum's last entry is the total)
-        HIP_TRY(hipMemsetAsync(d_counts, 0, 16, st));
-        fqt_launch_bounds(docs->qual.p, docs->doc_off.p, nd, q5, q3, lo32, len32, d_counts, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(idx_scan_sum(tmp, &tmp_bytes, len32, new_off, (size_t)nd + 1, false, st));
-        HIP_TRY(hipMemcpyAsync(&n_out, new_off + nd, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(idx_scan_sum(ts.tmp, &ts.tmp_bytes, ts.len32, ts.new_off, (size_t)nd + 1, false, st));
+        HIP_TRY(hipMemcpyAsync(&n_out, ts.new_off + nd, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(counts, ts.d_counts, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));               // (the total sizes the handle)
     }
     DocsGuard dg;
     int rc = docs_new(c, who, nd, n_out, dg); if (rc) return rc;
     if (nd) {
-        fqt_launch_copy(docs->text.p, docs->doc_off.p, nd, lo32, len32, new_off, dg.d->text.p, dg.d->doc_off.p, st);
+        fqt_launch_copy(docs->text.p, docs->doc_off.p, nd, ts.lo32, ts.len32, ts.new_off, dg.d->text.p, dg.d->doc_off.p, st);
         HIP_TRY(hipGetLastError());
     } else {
         HIP_TRY(hipMemsetAsync(dg.d->doc_off.p, 0, 8, st));
     }
-    HIP_TRY(hipStreamSynchronize(st));                   // (the scratch goes back when this returns)
+    HIP_TRY(hipStreamSynchronize(st));                   // (the scratch goes back when the caller returns)
     ti.n_changed = counts[0]; ti.n_empty = counts[1]; ti.symbols_out = n_out;
     if (info) *info = ti;
     *out = dg.take();
     return LIME_OK;
+}
+
+int lime_host::docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t q5, uint32_t q3, hipStream_t st, lime_docs **out,
+                              lime_trim_info_t *info)
+{
+    const uint32_t nd = docs->n_docs;
+    TrimScratch ts;
+    if (nd) {
+        int rc = trim_begin(who, nd, st, ts); if (rc) return rc;
+        fqt_launch_bounds(docs->qual.p, docs->doc_off.p, nd, q5, q3, ts.lo32, ts.len32, ts.d_counts, st);
+    }
+    return trim_finish(c, who, docs, ts, st, out, info);
+}
+
+// the adapter's refusals, shared by lime_adapter_trim's callers on the device side; -> masks[b]: bit j set where symbol j is "ACGT"[b]
+int lime_host::adapter_masks(const char *who, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct, uint64_t masks[4])
+{
+    masks[0] = masks[1] = masks[2] = masks[3] = 0;
+    if (!adapter) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (!m || m > 64) return fail(LIME_ERR_ARG, "%s: an adapter of %u symbols; it holds 1 .. 64", who, m);
+    for (uint32_t j = 0; j < m; ++j) {
+        const char *at = static_cast<const char *>(memchr("ACGT", adapter[j] & 0xDF, 4));
+        if (!at) return fail(LIME_ERR_ARG, "%s: adapter symbol %u is byte %u; an adapter holds A, C, G and T only", who, j, (unsigned)adapter[j]);
+        masks[at - "ACGT"] |= 1ull << j;
+    }
+    if (!min_overlap || min_overlap > m) return fail(LIME_ERR_ARG, "%s: a minimum overlap of %u with an adapter of %u symbols; it is 1 .. %u", who, min_overlap, m, m);
+    if (max_err_pct > 50) return fail(LIME_ERR_ARG, "%s: an error rate of %u percent; it is 0 .. 50", who, max_err_pct);
+    return LIME_OK;
+}
+
+int lime_host::docs_adapter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const uint64_t masks[4], uint32_t m, uint32_t min_overlap,
+                                 uint32_t max_err_pct, hipStream_t st, lime_docs **out, lime_trim_info_t *info)
+{
+    const uint32_t nd = docs->n_docs;
+    TrimScratch ts;
+    if (nd) {
+        int rc = trim_begin(who, nd, st, ts); if (rc) return rc;
+        ad_launch_bounds(docs->text.p, docs->doc_off.p, nd, masks, m, min_overlap, max_err_pct, ts.lo32, ts.len32, ts.d_counts, st);
+    }
+    return trim_finish(c, who, docs, ts, st, out, info);
+}
+
+extern "C" int lime_docs_trim_adapter_dev(lime_ctx *c, const lime_docs *docs, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct,
+                                          void *stream, lime_docs **out, lime_trim_info_t *info)
+{
+    const char *who = "lime_docs_trim_adapter_dev";
+    if (info) memset(info, 0, sizeof *info);
+    if (out) *out = nullptr;
+    if (!c || !docs || !adapter || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (docs->ctx != c) return fail(LIME_ERR_ARG, "%s: the documents belong to another context", who);
+    uint64_t masks[4];
+    int rc = adapter_masks(who, adapter, m, min_overlap, max_err_pct, masks); if (rc) return rc;
+    if ((rc = check_ctx(c, who))) return rc;
+    return docs_adapter_impl(c, who, docs, masks, m, min_overlap, max_err_pct, (hipStream_t)stream, out, info);
 }
 
 extern "C" int lime_docs_trim_dev(lime_ctx *c, const lime_docs *docs, uint32_t q5, uint32_t q3, void *stream, lime_docs **out, lime_trim_info_t *info)

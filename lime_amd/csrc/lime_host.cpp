@@ -397,6 +397,61 @@ extern "C" int lime_quality_trim(const uint8_t *text, const uint8_t *qual, const
     return LIME_OK;
 }
 
+// ---- the adapter trim: the loop form of the rule (include/lime_hip.h), the oracle of lime_docs_trim_adapter_dev -----------------
+extern "C" int lime_adapter_trim(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint8_t *adapter, uint32_t m, uint32_t min_overlap,
+                                 uint32_t max_err_pct, uint8_t **out_text, uint64_t **out_doc_off, lime_trim_info_t *info)
+{
+    const char *who = "lime_adapter_trim";
+    if (out_text) *out_text = nullptr;
+    if (out_doc_off) *out_doc_off = nullptr;
+    if (info) memset(info, 0, sizeof *info);
+    if (!doc_off || !adapter || !out_text || !out_doc_off) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (!m || m > 64) return lime_host::fail(LIME_ERR_ARG, "%s: an adapter of %u symbols; it holds 1 .. 64", who, m);
+    uint8_t ad[64];
+    for (uint32_t j = 0; j < m; ++j) {
+        ad[j] = adapter[j] & 0xDF;
+        if (ad[j] != 'A' && ad[j] != 'C' && ad[j] != 'G' && ad[j] != 'T')
+            return lime_host::fail(LIME_ERR_ARG, "%s: adapter symbol %u is byte %u; an adapter holds A, C, G and T only", who, j, (unsigned)adapter[j]);
+    }
+    if (!min_overlap || min_overlap > m)
+        return lime_host::fail(LIME_ERR_ARG, "%s: a minimum overlap of %u with an adapter of %u symbols; it is 1 .. %u", who, min_overlap, m, m);
+    if (max_err_pct > 50) return lime_host::fail(LIME_ERR_ARG, "%s: an error rate of %u percent; it is 0 .. 50", who, max_err_pct);
+    if (doc_off[0] != 0) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off does not start at 0", who);
+    for (uint32_t r = 0; r < n_docs; ++r)
+        if (doc_off[r + 1] < doc_off[r]) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off decreases at read %u", who, r);
+    if (doc_off[n_docs] && !text) return lime_host::fail(LIME_ERR_ARG, "%s: NULL array", who);
+    std::vector<uint8_t> sym;
+    std::vector<uint64_t> off;
+    off.reserve((size_t)n_docs + 1);
+    lime_trim_info_t ti = {n_docs, 0, 0, doc_off[n_docs], 0};
+    for (uint32_t r = 0; r < n_docs; ++r) {
+        const uint64_t a = doc_off[r], L = doc_off[r + 1] - a;
+        const uint8_t *s = text + a;
+        uint64_t keep = L;
+        for (uint64_t p = 0; p < L; ++p) {
+            const uint32_t k = L - p < m ? (uint32_t)(L - p) : m;
+            if (k < min_overlap) break;                  // (k only falls from here on)
+            uint32_t mm = 0;
+            for (uint32_t j = 0; j < k; ++j) mm += (s[p + j] & 0xDF) != ad[j];
+            if (mm <= (k * max_err_pct) / 100) { keep = p; break; }
+        }
+        off.push_back(sym.size());
+        if (keep) sym.insert(sym.end(), s, s + keep);
+        ti.n_changed += keep != L;
+        ti.n_empty += L != 0 && keep == 0;
+    }
+    off.push_back(sym.size());
+    ti.symbols_out = sym.size();
+    uint8_t *t = static_cast<uint8_t *>(malloc(sym.size() ? sym.size() : 1));
+    uint64_t *o = static_cast<uint64_t *>(malloc(off.size() * 8));
+    if (!t || !o) { free(t); free(o); return lime_host::fail(LIME_ERR_NOMEM, "%s: out of host memory", who); }
+    if (!sym.empty()) memcpy(t, sym.data(), sym.size());
+    memcpy(o, off.data(), off.size() * 8);
+    *out_text = t; *out_doc_off = o;
+    if (info) *info = ti;
+    return LIME_OK;
+}
+
 // the format of a sequence file by its first byte: '@' is FASTQ (1), anything else FASTA (0) -- an empty file and text in front of the
 // first FASTA header included
 extern "C" int lime_seq_format(const char *path, int *format)

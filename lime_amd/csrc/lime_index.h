@@ -115,6 +115,13 @@ void fqt_launch_bounds(const uint8_t *qual, const uint64_t *doc_off, uint32_t n_
 void fqt_launch_copy(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint32_t *lo32, const uint32_t *len32, const uint32_t *new_off,
                      uint8_t *out, uint64_t *out_off, hipStream_t st);
 
+// ---- lime_adapter_kernel.hip: where a 3' adapter begins in every read (lime_docs.cpp) ----
+// lo32[r] = 0, len32[r] = what the rule (include/lime_hip.h: lime_adapter_trim) keeps of read r, in fqt_launch_bounds' conventions, so that
+// the prefix sum and fqt_launch_copy follow unchanged; counts as there.  masks[b]: bit j set where the adapter's symbol j is "ACGT"[b];
+// 1 <= min_overlap <= m <= 64, max_err_pct <= 50
+void ad_launch_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint64_t masks[4], uint32_t m, uint32_t min_overlap,
+                      uint32_t max_err_pct, uint32_t *lo32, uint32_t *len32, uint64_t *counts, hipStream_t st);
+
 // ---- lime_seqcut_kernel.hip: where a window of a reads file is cut into whole records (lime_reader.cpp) ----
 // The same blocks; the markers and the rule are at the head of the kernel file.  cnt[k] = the line-first '>' of block k (FASTQ counts
 // its markers with fq_launch_lines)

@@ -243,6 +243,16 @@ static int reader_next(lime_seq_reader *r, const char *who, uint32_t max_reads, 
             r->trimmed.n_reads += ti.n_reads; r->trimmed.n_changed += ti.n_changed; r->trimmed.n_empty += ti.n_empty;
             r->trimmed.symbols_in += ti.symbols_in; r->trimmed.symbols_out += ti.symbols_out;
         }
+        if (r->adapter) {                                // second, as an outside trimmer does it: the quality trim's output holds no qualities
+            lime_docs *t = nullptr;
+            lime_trim_info_t ti;
+            rc = docs_adapter_impl(r->ctx, who, d, r->ad_masks, r->ad_m, r->ad_overlap, r->ad_err, nullptr, &t, &ti);
+            lime_docs_free(d);
+            if (rc) return rc;
+            d = t;
+            r->ad_trimmed.n_reads += ti.n_reads; r->ad_trimmed.n_changed += ti.n_changed; r->ad_trimmed.n_empty += ti.n_empty;
+            r->ad_trimmed.symbols_in += ti.symbols_in; r->ad_trimmed.symbols_out += ti.symbols_out;
+        }
         uint32_t nd = 0;
         lime_docs_info(d, &nd, nullptr);
         if (r->n_records + nd > 0xFFFFFFFFull) {
@@ -288,6 +298,25 @@ extern "C" int lime_seq_reader_trim_info(const lime_seq_reader *r, lime_trim_inf
 {
     if (!r || !info) return fail(LIME_ERR_ARG, "lime_seq_reader_trim_info: NULL argument");
     *info = r->trimmed;
+    return LIME_OK;
+}
+
+extern "C" int lime_seq_reader_set_adapter(lime_seq_reader *r, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct)
+{
+    const char *who = "lime_seq_reader_set_adapter";
+    if (!r) return fail(LIME_ERR_ARG, "%s: the reader is NULL", who);
+    uint64_t masks[4];
+    int rc = adapter_masks(who, adapter, m, min_overlap, max_err_pct, masks); if (rc) return rc;
+    if (r->asked) return fail(LIME_ERR_ARG, "%s: the reader has handed out records already; the adapter is set before the first lime_seq_reader_next", who);
+    r->adapter = true; r->ad_m = m; r->ad_overlap = min_overlap; r->ad_err = max_err_pct;
+    memcpy(r->ad_masks, masks, sizeof masks);
+    return LIME_OK;
+}
+
+extern "C" int lime_seq_reader_adapter_info(const lime_seq_reader *r, lime_trim_info_t *info)
+{
+    if (!r || !info) return fail(LIME_ERR_ARG, "lime_seq_reader_adapter_info: NULL argument");
+    *info = r->ad_trimmed;
     return LIME_OK;
 }
 
