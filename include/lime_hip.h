@@ -102,7 +102,7 @@ int  lime_pick_device(unsigned salt);    /* the device with the most free memory
  * most pick which kernel variant or update path runs.  Not a stable interface -- lime_amd/csrc/lime_api.cpp:set_option is the list:
  * update_path (cas|bin|auto), bin_levels ("one,two"), pool_density, pool_slack, scan_static_pct, second_level (tiles|sweeps), part_split, no_probe,
  * probe_min, force_p64, p64_test_base, max_blocks, choose_free, apply_wide, sort_nt, part_lines, no_staging, force_staging, detect_chunk,
- * score_chunk, force_rccl, io_threads, dense_min, no_direct, apply_group, debug_stats, debug_alloc, poison_cache.
+ * score_chunk, force_rccl, io_threads, dense_min, no_direct, flush_gran (16|64), apply_group, debug_stats, debug_alloc, poison_cache.
  * The ENVIRONMENT is read by lime_init only: LIME_IO_THREADS (host staging threads; the reference's `threads` argument, ClusterLCP.cpp:73-84)
  * always, and -- only when LIME_TEST_HOOKS=1 is set -- a LIME_<KNOB> variable per knob above (tests, experiments).  bench.py refuses to run
  * under LIME_TEST_HOOKS. */
@@ -367,6 +367,11 @@ uint32_t lime_rec_sub2(uint32_t rd, uint32_t gd, uint32_t sub_rb, uint32_t sub_g
 uint32_t lime_rec_bin(uint32_t rec, uint32_t sub, uint32_t bin_shift);
 int      lime_rec_batch(const uint32_t *rd, const uint32_t *gd, uint64_t n, uint32_t n_refs, const lime_rec_layout_t *layout,
                         int fixed_slot, uint8_t *valid, uint8_t *stored, uint32_t *rec, uint32_t *sub, uint32_t *bin);
+/* The record buffers of a scan wave whose scorers write the records (tables of one or two sub-regions): records each holds in the
+ * EBWT=0 / EBWT=1 kernel, the most a flush that makes room leaves waiting (whole lines of 16 leave), and the most the flush at a
+ * window's top leaves where it takes batches of 64 (option flush_gran). */
+typedef struct { uint32_t cap, cap_short, room_left, top_left; } lime_scan_queue_t;
+void     lime_scan_queue(lime_scan_queue_t *out);
 
 /* Writers of the reference's files (byte-identical formats). */
 int lime_write_clrs(const char *path, const lime_cluster_t *clusters, uint64_t n_clusters); /* ClusterLCP.cpp:229-235 */

@@ -85,6 +85,7 @@ SYMBOLS = {
     "lime_rec_sub2": (_u32, [_u32, _u32, _u32, _u32]),
     "lime_rec_bin": (_u32, [_u32, _u32, _u32]),
     "lime_rec_batch": (_i, [_vp, _vp, _u64, _u32, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lime_scan_queue": (None, [_vp]),
     "lime_write_clrs": (_i, [C.c_char_p, _vp, _u64]),
     "lime_write_aux": (_i, [C.c_char_p, _u32, _u32, _u32, _u64, _u64]),
     "lime_read_aux": (_i, [C.c_char_p, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), _pu64, _pu64]),

@@ -97,6 +97,11 @@ static int set_option(lime_ctx *c, const char *key, const char *s)
     else if (is("poison_cache")) g_poison_cache.store(v != 0 || !*s, std::memory_order_relaxed);
     else if (is("no_direct")) c->no_direct = v != 0 || !*s;
     else if (is("dense_min")) c->dense_min = *s ? (uint32_t)strtoul(s, nullptr, 0) : 64u;
+    else if (is("flush_gran")) {
+        if (!*s) c->flush_gran = 0;
+        else if (v == 16 || v == 64) c->flush_gran = (uint32_t)v;
+        else return fail(LIME_ERR_ARG, "flush_gran: want 16 or 64");
+    }
     else if (is("io_threads")) c->io_threads = v >= 1 ? (v > 64 ? 64 : (int)v) : 0;
     else return fail(LIME_ERR_ARG, "lime_set_option: unknown option \"%s\"", key);
     return LIME_OK;
@@ -143,7 +148,7 @@ extern "C" int lime_init(int device, lime_ctx **out)
             {"LIME_PROBE_MIN", "probe_min"}, {"LIME_FORCE_P64", "force_p64"}, {"LIME_P64_TEST_BASE", "p64_test_base"}, {"LIME_MAX_BLOCKS", "max_blocks"},
             {"LIME_CHOOSE_FREE", "choose_free"}, {"LIME_APPLY_WIDE", "apply_wide"}, {"LIME_SORT_NT", "sort_nt"}, {"LIME_PART_LINES", "part_lines"},
             {"LIME_NO_STAGING", "no_staging"}, {"LIME_FORCE_STAGING", "force_staging"}, {"LIME_DETECT_CHUNK", "detect_chunk"}, {"LIME_SCORE_CHUNK", "score_chunk"},
-            {"LIME_FORCE_RCCL", "force_rccl"}, {"LIME_DENSE_MIN", "dense_min"}, {"LIME_NO_DIRECT", "no_direct"}, {"LIME_DEBUG_STATS", "debug_stats"}, {"LIME_DEBUG_ALLOC", "debug_alloc"}, {"LIME_APPLY_GROUP", "apply_group"}};
+            {"LIME_FORCE_RCCL", "force_rccl"}, {"LIME_DENSE_MIN", "dense_min"}, {"LIME_NO_DIRECT", "no_direct"}, {"LIME_FLUSH_GRAN", "flush_gran"}, {"LIME_DEBUG_STATS", "debug_stats"}, {"LIME_DEBUG_ALLOC", "debug_alloc"}, {"LIME_APPLY_GROUP", "apply_group"}};
         for (const auto &hk : hooks)
             if (const char *s = getenv(hk[0])) {
                 if ((rc = set_option(c, hk[1], s))) return fail(rc, "lime_init: %s=%s: %s", hk[0], s, g_err.c_str());
@@ -372,6 +377,10 @@ extern "C" int lime_rec_valid(uint32_t gd, uint32_t n_refs) { return genome_ok(g
 extern "C" uint32_t lime_rec_of(uint32_t rd, uint32_t gd, uint32_t n_refs) { return rec_of(rd, gd, n_refs); }
 extern "C" uint32_t lime_rec_sub2(uint32_t rd, uint32_t gd, uint32_t sub_rb, uint32_t sub_gb) { return rec_sub2(rd, gd, sub_rb, sub_gb); }
 extern "C" uint32_t lime_rec_bin(uint32_t rec, uint32_t sub, uint32_t bin_shift) { return rec_bin(rec, sub, bin_shift); }
+extern "C" void lime_scan_queue(lime_scan_queue_t *out)
+{
+    if (out) { out->cap = QCAP_SCAN; out->cap_short = QCAP_SCAN_SHORT; out->room_left = ROOM_LEFT; out->top_left = FLUSH_GRAN - 1u; }
+}
 // What the scan stores for each pair (read rd[i], genome index gd[i]) and where the partition kernels put it: valid[i] = genome_ok;
 // stored[i] = 0: nothing (the pass ends in LIME_ERR_DOCID), else rec[i] / sub[i] = the record and its sub-region, bin[i] = rec_bin of them.
 // `fixed_slot`: the pair's slot was given out before its id was looked at (score_small3, one sub-region): a bad id leaves the stand-in.

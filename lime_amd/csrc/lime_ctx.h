@@ -163,6 +163,7 @@ struct __attribute__((visibility("hidden"))) lime_ctx {              // (hidden:
     uint64_t detect_chunk = 0, score_chunk = 0;             // symbols per chunk of lime_detect / lime_score* walks (0: by the sources)
     bool no_direct = false;                 // binned updates through the update queue (k_scan<., 0, 1>) even for tables of one or two sub-regions (option no_direct: comparison runs, tests)
     uint32_t dense_min = 64;                // k_scan: windows with more accepted clusters list their 2-symbol clusters apart (option dense_min; tests: 0 = every window)
+    uint32_t flush_gran = 0;                // k_scan<., 0, 2>: records per batch that leaves at a window's top (option flush_gran: 16 or 64; 0 = by the table's sub-regions)
     int io_threads = 0;                     // host threads that stage pageable sources into the pinned ring (0: 8, at most the CPUs this process may use)
     // timing with HIP events on the launch stream: per pass {pass start, scan start, scan end, pass end}
     bool timing = false;

@@ -66,7 +66,12 @@ constexpr uint32_t BIN_ONE_LEVEL = 1024;     // tables of up to this many region
 constexpr uint32_t BIN_TWO_LEVEL = 2048;     // larger tables: at most this many bins of 2^k regions each (while k allows); measured best of 256..2048 on configs[2]
 constexpr uint32_t BIN_SHIFT_MAX = 25;       // bin-relative cell offset + 7 bits of t must fit 32 bits
 constexpr uint32_t CELL_BITS = 40;           // a cell (byte index of the table) has at most this many bits
-constexpr uint32_t MAX_SUB = 8;              // binned updates: a pool record is the cell's low 32 bits, its high part the number of the wave's sub-region: tables up to 32 GB
+// k_scan: entries of a wave's update queue = records of each of its two record buffers (k_scan<., 0, 2>)
+constexpr uint32_t QCAP_SCAN = 286;          // >= the 256 hits one batch of 64 clusters of <= 4 symbols can add + the 2 x 15 entries a binned drain leaves behind
+constexpr uint32_t QCAP_SCAN_SHORT = 160;    // EBWT=1 with records (16 waves per CU): a batch that would not fit is emitted in two halves (score_small3)
+constexpr uint32_t ROOM_LEFT = 15;           // flush_direct: most records a flush that makes room leaves waiting in a sub-region (whole lines of 16 leave)
+constexpr uint32_t FLUSH_GRAN = 64;          // flush_direct at a window's top: whole groups of this many records leave where flush_direct flushes in batches (option flush_gran)
+constexpr uint32_t MAX_SUB = 8;             // binned updates: a pool record is the cell's low 32 bits, its high part the number of the wave's sub-region: tables up to 32 GB
 constexpr int APPLY_WG = 512;
 constexpr uint32_t BIG_GRID = 32;            // workgroups of k_score_big (each owns a scratch table)
 constexpr size_t BIG_SCRATCH_WORDS = (size_t)HT_SIZE + (size_t)HT_SIZE * 16u + 2u * LIME_MAX_CLUSTER;
@@ -100,6 +105,7 @@ struct ScanArgs {
     uint32_t *edge;                              // LIME_EDGE_* word of this shard (default: &stats->edge)
     uint32_t no_direct;                          // binned updates: 1 = through the update queue (k_scan<., 0, 1>) even where the scorers could write the records themselves (option no_direct: comparison runs, tests)
     uint32_t dense_min;                          // k_scan: a window with more accepted clusters than this lists its 2-symbol clusters apart (64)
+    uint32_t flush_gran;                         // k_scan<., 0, 2>: records per batch that leaves at a window's top: 16, 64 (FLUSH_GRAN), or 0 = 64 for two sub-regions, else 16 (option flush_gran)
     uint32_t probe_shift;                        // density probe (lime_pass.cpp): only every 2^probe_shift-th chunk of a workgroup's wave count of windows is scanned; 0 = a pass
     uint32_t *dyn; uint32_t n_static, static_pct;           // k_scan: rounds of round-robin window chunks before the chunks come from the counter dyn[0] (dyn[1]: workgroups done; both are left at 0); set by the launch wrapper from static_pct
     uint32_t sub_rb, sub_gb;                     // binned, two sub-regions: cell >= 2^32 <=> read > sub_rb or (read == sub_rb and genome >= sub_gb); one sub-region: sub_rb = ~0

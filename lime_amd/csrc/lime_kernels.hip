@@ -67,8 +67,7 @@ struct alignas(16) WaveLds {
 // EBWT = 0: 16 waves = 4 per SIMD; EBWT = 1: 12 waves = 3 per SIMD); the LDS of one wave is kept small: it bounds them
 constexpr uint32_t DUP_SLOTS = 8;     // clusters with a repeated document a wave of k_scan holds before scoring them
 constexpr uint32_t DUP_SLOTS_E = 4;   // ... with symbols (EBWT=1: 16 waves per CU, the LDS is short): one flush of four 16-lane groups
-constexpr uint32_t QCAP_SCAN = 286;   // >= the 256 hits one batch of 64 clusters of <= 4 symbols can add + the 2 x 15 entries a binned drain leaves behind
-constexpr uint32_t QCAP_SCAN_SHORT = 160;   // EBWT=1 with records (16 waves per CU): a batch that would not fit is emitted in two halves (score_small3)
+// QCAP_SCAN, QCAP_SCAN_SHORT (the update queue / record buffers of a wave): lime_kernels.h
 
 
 // byte -> symbol index, and symbol index -> set of symbol indices it scores 1 against
@@ -288,22 +287,49 @@ __device__ __forceinline__ void drain_lines(UpdQueue &q, const ScanArgs &a, bool
 // memory floor, 1234 us) -- two LDS reads per entry, a quarter-rate multiply, two ballots and ranks, an LDS write, then the line buffer's read-back, and
 // all of it in front of the next window's loads.  Here the scorers compute the record themselves (one multiply-add where they used to write two words)
 // and write it where its 64-byte line is being gathered; what is left for the flush is: read 64 records, count them in the bin histogram, store.
-__device__ __forceinline__ void flush_direct(UpdQueue &q, const ScanArgs &a, bool final)
+//
+// A flush stores the LAST nl records waiting in a sub-region's buffer, buf[n - nl .. n), and the front stays where it is (the order of a wave's
+// records is free: drain_bin takes the queue's last 64 for the same reason) -- until round 7 it stored the first nl and moved the <= 15 behind them
+// to the front, an LDS read, a wait and an LDS write per sub-region and window in front of the next window's loads.  How many leave (`why`):
+//   FLUSH_ROOM   a scorer needs room: every whole line, nl = n & ~15, so at most 15 records stay -- the loops `while (n + batch > cap) flush` of
+//                put_rec, score_small3 and drain() end after ONE call because of that (static_asserts below), and only this form is reachable from them;
+//   FLUSH_TOP    the window's top: whole groups of ScanArgs::flush_gran records (64: every iteration runs with all lanes and every store instruction
+//                writes four whole lines; a sub-region with fewer waiting is skipped this window -- up to 63 stay; 16: as FLUSH_ROOM; 0, the default:
+//                64 for a table of two sub-regions, whose second one gets a trickle of records that fills a batch every few windows -- configs[2]:
+//                scan 1.49 -> 1.46 ms --, 16 for one sub-region, where batches of 64 measured 0.8 % SLOWER at N = 1e10: profiles/r07_flush_ab.txt);
+//   FLUSH_FINAL  the kernel's end: everything, the partial line too.
+// base0 / base1 advance by multiples of 16 except in the final flush, so every store before it is a whole 64-byte line of the pool.
+enum FlushWhy { FLUSH_ROOM = 0, FLUSH_TOP = 1, FLUSH_FINAL = 2 };
+static_assert(ROOM_LEFT + 256u <= QCAP_SCAN, "EBWT=0: a whole batch of score_small3 (64 clusters x 4 pairs) fits behind what a room flush leaves");
+static_assert(ROOM_LEFT + 128u <= QCAP_SCAN_SHORT, "EBWT=1: half a batch of score_small3 (64 clusters x 2 pair slots) fits behind what a room flush leaves");
+static_assert(256u + 2u * ROOM_LEFT <= QCAP_SCAN, "EBWT=0: score_small3's `halves` rule never splits a batch of the long queue");
+static_assert(ROOM_LEFT + 64u <= QCAP_SCAN_SHORT && ROOM_LEFT + 64u <= QCAP_SCAN, "a put_rec (<= 64 records) fits behind what a room flush leaves");
+// the kernel arguments a flush reads: loaded where it is called, or -- the window's top -- ahead of it
+struct FlushK { uint32_t cap_w, bin_shift, n_sub, n_bins, prod_waves, flush_gran; uint32_t *pool; };
+__device__ __forceinline__ FlushK flush_args(const ScanArgs &a)
+{
+    const ScanArgs &ca = cold(a);
+    return FlushK{ca.cap_w, ca.bin_shift, ca.n_sub, ca.n_bins, ca.prod_waves, ca.flush_gran, ca.pool};
+}
+__device__ __forceinline__ void flush_direct(UpdQueue &q, const ScanArgs &a, FlushWhy why, const FlushK &ca)
 {
     if (ABL(13)) return;
     if (ABL(14)) { q.n = 0; q.n1 = 0; return; }                      // (timing experiments: the scorers' share of the record work without the flush)
     const uint32_t lane = lane_id();
-    const ScanArgs &ca = cold(a);
     const uint32_t cap_w = ca.cap_w, bin_shift = ca.bin_shift, n_sub = ca.n_sub, bin_lim = ca.n_bins;
     const uint32_t hoff = ((uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) / ca.prod_waves) * bin_lim;     // the producer group's part of the workgroup's histogram
+    // records that may stay: a compile-time constant except at the window's top (flush_gran is 0, 16 or 64: lime_set_option)
+    const bool batches = ca.flush_gran ? ca.flush_gran == FLUSH_GRAN : n_sub == 2u;
+    const uint32_t keep = why == FLUSH_FINAL ? 0u : why == FLUSH_TOP && batches ? FLUSH_GRAN - 1u : ROOM_LEFT;
     report_bad(q, a);
-    uint32_t *const out = pool_of(ca, n_sub, cap_w);
+    const uint32_t wave_gid = blockIdx.x * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t *const out = ca.pool + (size_t)wave_gid * n_sub * cap_w;      // the wave's region of the pool (pool_of)
 #pragma unroll
     for (uint32_t sub = 0; sub < 2u; ++sub) {
         if (sub && !q.two()) break;
-        const uint32_t n = sub ? q.n1 : q.n, nl = final ? n : n & ~15u;
+        const uint32_t n = sub ? q.n1 : q.n, nl = n & ~keep;
         if (!nl) continue;                                           // wave-uniform
-        uint32_t *buf = sub ? q.qg : q.qr;
+        const uint32_t *buf = (sub ? q.qg : q.qr) + (n - nl);        // the last nl records
         const uint32_t base = sub ? q.base1 : q.base0;
         for (uint32_t k0 = 0; k0 < nl; k0 += 64u) {
             const uint32_t k = k0 + lane;
@@ -316,12 +342,10 @@ __device__ __forceinline__ void flush_direct(UpdQueue &q, const ScanArgs &a, boo
                 if (!ABL(6)) __builtin_nontemporal_store(rec, out + (size_t)sub * cap_w + slot);
             }
         }
-        const uint32_t rem = n - nl;                                 // < 16 <= nl: the two ranges below do not overlap
-        const uint32_t mv = buf[lane < rem ? nl + lane : 0u];
-        if (lane < rem) buf[lane] = mv;
-        if (sub) { q.base1 = base + nl; q.n1 = rem; } else { q.base0 = base + nl; q.n = rem; }
+        if (sub) { q.base1 = base + nl; q.n1 = n - nl; } else { q.base0 = base + nl; q.n = n - nl; }
     }
 }
+__device__ __forceinline__ void flush_direct(UpdQueue &q, const ScanArgs &a, FlushWhy why) { flush_direct(q, a, why, flush_args(a)); }
 
 // direct mode: the lanes with `hit` append the record of (read rd, genome index gd), t = 1.  All 64 lanes call.
 // The callers have taken the lanes whose gd fails genome_ok out of `hit` (checked()): every record stored is a cell of the table.
@@ -332,14 +356,16 @@ __device__ __forceinline__ void put_rec(UpdQueue &q, const ScanArgs &a, bool hit
     if (!q.two()) {
         const uint64_t m = __ballot(hit);
         const uint32_t tot = (uint32_t)__popcll(m);
-        while (q.n + tot > q.cap) flush_direct(q, a, false);
+        // ends after one call: a room flush leaves q.n <= ROOM_LEFT and tot <= 64, ROOM_LEFT + 64 <= q.cap (static_assert above)
+        while (q.n + tot > q.cap) flush_direct(q, a, FLUSH_ROOM);
         if (hit) q.qr[q.n + rank_in(m)] = rec;
         q.n += tot;
     } else {
         const bool hi = rec_sub2(rd, gd, q.sub_rb, q.sub_gb) != 0u;               // cell >= 2^32
         const uint64_t m1 = __ballot(hit && hi), m0 = __ballot(hit && !hi);
         const uint32_t t0 = (uint32_t)__popcll(m0), t1 = (uint32_t)__popcll(m1);
-        while (q.n + t0 > q.cap || q.n1 + t1 > q.cap) flush_direct(q, a, false);
+        // ends after one call: a room flush leaves q.n and q.n1 <= ROOM_LEFT, and t0 + t1 <= 64
+        while (q.n + t0 > q.cap || q.n1 + t1 > q.cap) flush_direct(q, a, FLUSH_ROOM);
         if (hit) { if (hi) q.qg[q.n1 + rank_in(m1)] = rec; else q.qr[q.n + rank_in(m0)] = rec; }
         q.n += t0; q.n1 += t1;
     }
@@ -423,7 +449,7 @@ __device__ __forceinline__ void drain_bin(UpdQueue &q, const ScanArgs &a, bool f
 __device__ __forceinline__ void drain(UpdQueue &q, const ScanArgs &a)
 {
     if (ABL(13)) { q.n = 0; q.n1 = 0; return; }            // (timing experiments: what ALL of the drains' work costs -- the entries are thrown away)
-    if (q.direct) { flush_direct(q, a, false); return; }
+    if (q.direct) { flush_direct(q, a, FLUSH_ROOM); return; }          // (a scorer's `while (no room) drain`: never the window top's form, which may leave 63)
     if (q.async) { if (q.binned) drain_bin(q, a, false, false); else drain_async(q, a); return; }     // both flags are compile-time constants of the kernel
 #ifdef LIME_PHASE_TIMING
     const uint64_t t0 = __builtin_readcyclecounter();
@@ -805,6 +831,8 @@ __device__ __forceinline__ uint32_t score_small3(LDS &L, const WgTables &T, UpdQ
         const uint32_t hp = halves == 1u ? hits : (half ? hits & 12u : hits & 3u);
         const uint32_t nhp = (uint32_t)__popc(hp);
         const uint32_t incl = halves == 1u ? incl_all : wave_incl_scan(nhp), total = halves == 1u ? total_all : rl32(incl, 63);
+        // direct mode: ends after one call -- drain() is a room flush, which leaves qu.n <= 15 whatever the window's top left waiting (up to 63),
+        // and total <= 256 with total + 30 <= cap (one half) or total <= 128 (two halves; 15 + 128 <= QCAP_SCAN_SHORT): static_asserts at flush_direct
         while (qu.n + total > qu.cap) drain(qu, a);
         const uint32_t slot0 = qu.n + incl - nhp;
 #pragma unroll
@@ -1215,6 +1243,11 @@ __global__ __launch_bounds__((ScanCfg<EBWT, BIN>::wg)) __attribute__((amdgpu_wav
         const uint32_t own_lim = (uint32_t)(n_own_ > lo ? (n_own_ - lo < WIN ? n_own_ - lo : (uint64_t)WIN) : 0ull);
         const uint64_t lim64 = (EBWT ? cold(a) : a).n_avail - lo;             // valid positions of the window + read-ahead: [0, lim)
         const uint32_t lim = (uint32_t)(lim64 < WPOS ? lim64 : (uint64_t)WPOS);
+        // the kernel arguments of the flush behind the staging: their scalar loads go out here and are back when the ~160 vector instructions
+        // of the staging are through (read inside the flush they were waited for with no window load in flight: 12 us of configs[2]'s scan,
+        // profiles/r07_flush_ab.txt; the registers cost no further spill)
+        FlushK fk = {};
+        if (BIN == 2 && MODE == 0) fk = flush_args(a);
         // ---- stage the window in LDS and build the masks.  Loads are lane-strided (register j of lane l =
         // position 64 j + l: every load instruction reads 64 consecutive elements -- a lane reading its own 16
         // positions would touch 64 cache lines per instruction), so mask word j is the wave ballot of the
@@ -1266,7 +1299,7 @@ __global__ __launch_bounds__((ScanCfg<EBWT, BIN>::wg)) __attribute__((amdgpu_wav
         // stores issued from the scoring rounds).  Issued here they are older than the loads and long done by then.
         if (MODE == 0 && !ABL(8)) {
             if (ABL(13)) { qu.n = 0; qu.n1 = 0; } else
-            if (BIN == 2) flush_direct(qu, a, false); else
+            if (BIN == 2) flush_direct(qu, a, FLUSH_TOP, fk); else                  // whole batches of flush_gran records; the rest waits for the next window
             { report_bad(qu, a); if (binned) drain_bin(qu, a); else drain(qu, a); }
             asm volatile("" ::: "memory");                    // the loads below stay below
         }
@@ -1473,7 +1506,7 @@ __global__ __launch_bounds__((ScanCfg<EBWT, BIN>::wg)) __attribute__((amdgpu_wav
     }
     if (MODE == 0) {
         if (n_dup) acc_upd += dup_flush<EBWT>(L, n_dup, a, T, qu);
-        if (BIN == 2) flush_direct(qu, a, true);                               // the last, partial lines too
+        if (BIN == 2) flush_direct(qu, a, FLUSH_FINAL);                        // everything that waits, the partial lines too
         else {
         report_bad(qu, a);
         do drain(qu, a); while (qu.n != 0u || __ballot(qu.f_pend != 0u));      // until every update has landed

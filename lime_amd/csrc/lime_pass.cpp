@@ -64,6 +64,7 @@ static ScanArgs base_args(lime_ctx *c, const uint32_t *lcp, const uint32_t *da, 
     a.ablate = c->ablate;
     a.dense_min = c->dense_min;
     a.no_direct = c->no_direct ? 1u : 0u;
+    a.flush_gran = c->flush_gran;
     return a;
 }
 
