@@ -267,6 +267,22 @@ struct DevBuf {
     }
 };
 
+// The scratch of a pass over `count` items in one block: n_arr arrays of count + 1 32-bit words, each rounded up to 256 bytes, then one
+// 256-byte cell (an error word, a few counters), then rocPRIM's temporary of tmp_bytes
+struct WordScratch {
+    DevBuf buf;
+    size_t stride = 0, n_arr = 0, tmp_bytes = 0;         // stride: the bytes of one array
+    static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
+    int alloc(size_t arrays, size_t count, size_t tmp)
+    {
+        n_arr = arrays; stride = up((count + 1) * 4); tmp_bytes = tmp;
+        return buf.alloc(n_arr * stride + 256 + up(tmp_bytes));
+    }
+    uint32_t *words(size_t i) const { return reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(buf.p) + i * stride); }
+    void *cell() const { return words(n_arr); }
+    void *tmp() const { return static_cast<uint8_t *>(cell()) + 256; }
+};
+
 // lime_api.cpp
 int flags_to_rc(uint32_t flags);
 int timing_mark(lime_ctx *c, hipStream_t st);

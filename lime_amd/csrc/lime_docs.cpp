@@ -70,26 +70,22 @@ int lime_host::docs_parse_fasta_dev(lime_ctx *c, const char *who, const uint8_t 
 {
     const uint32_t nb = (uint32_t)((n + LIME_FASTA_BLOCK - 1) / LIME_FASTA_BLOCK);
     uint32_t totals[2] = {0, 0};                         // kept bytes, header starts
-    DevBuf scratch;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t words = up(((size_t)nb + 1) * 4);
-    uint32_t *last_lf = nullptr, *cum_lf = nullptr, *cnt = nullptr, *off_keep = nullptr, *off_hdr = nullptr, *first_hdr = nullptr;
+    WordScratch scratch;
+    uint32_t *cum_lf = nullptr, *off_keep = nullptr, *off_hdr = nullptr, *first_hdr = nullptr;
     if (nb) {
         size_t t_max = 0, t_sum = 0;
         HIP_TRY(idx_scan_max(nullptr, &t_max, nullptr, nullptr, nb, st));
         HIP_TRY(idx_scan_sum(nullptr, &t_sum, nullptr, nullptr, (size_t)nb + 1, false, st));
         size_t tmp_bytes = std::max(t_max, t_sum);
-        int rc = scratch.alloc(6 * words + 256 + up(tmp_bytes));
+        int rc = scratch.alloc(6, nb, tmp_bytes);
         if (rc) return fail(rc, "%s: no device memory for the parse of %llu bytes: %s", who, (unsigned long long)n, lime_last_error());
-        uint8_t *at = static_cast<uint8_t *>(scratch.p);
-        auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
-        last_lf = (uint32_t *)take(words); cum_lf = (uint32_t *)take(words);
-        cnt = (uint32_t *)take(2 * words);               // kept bytes, then header starts: each with a 0 behind the last block's
-        off_keep = (uint32_t *)take(words); off_hdr = (uint32_t *)take(words);
-        first_hdr = (uint32_t *)take(256);
-        void *tmp = take(up(tmp_bytes));
-        uint32_t *cnt_keep = cnt, *cnt_hdr = cnt + words / 4;
-        HIP_TRY(hipMemsetAsync(cnt, 0, 2 * words, st));
+        uint32_t *last_lf = scratch.words(0);
+        cum_lf = scratch.words(1);
+        uint32_t *cnt_keep = scratch.words(2), *cnt_hdr = scratch.words(3);  // kept bytes, then header starts: each with a 0 behind the last block's
+        off_keep = scratch.words(4); off_hdr = scratch.words(5);
+        first_hdr = (uint32_t *)scratch.cell();
+        void *tmp = scratch.tmp();
+        HIP_TRY(hipMemsetAsync(cnt_keep, 0, 2 * scratch.stride, st));
         HIP_TRY(hipMemsetAsync(first_hdr, 0xFF, 4, st));
         fa_launch_lines(d_bytes, n, nb, last_lf, first_hdr, st);
         HIP_TRY(hipGetLastError());
@@ -127,24 +123,21 @@ int lime_host::docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t 
     const uint32_t nb = (uint32_t)((n + LIME_FASTA_BLOCK - 1) / LIME_FASTA_BLOCK);
     uint32_t n_keep = 0, n_lines = 0;
     uint64_t err_word = ~0ull;                           // line * 4 + reason of the lowest offence
-    DevBuf scratch;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t words = up(((size_t)nb + 1) * 4);
+    WordScratch scratch;
     uint32_t *line0 = nullptr, *off_keep = nullptr, *off_diff = nullptr;
     uint64_t *err = nullptr;
     if (nb) {
         size_t tmp_bytes = 0;
         HIP_TRY(idx_scan_sum(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)nb + 1, false, st));
-        int rc = scratch.alloc(6 * words + 256 + up(tmp_bytes));
+        int rc = scratch.alloc(6, nb, tmp_bytes);
         if (rc) return fail(rc, "%s: no device memory for the parse of %llu bytes: %s", who, (unsigned long long)n, lime_last_error());
-        uint8_t *at = static_cast<uint8_t *>(scratch.p);
-        auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
-        uint32_t *cnt = (uint32_t *)take(3 * words);     // '\n', kept bytes, kept minus quality bytes: each with a 0 behind the last block's
-        line0 = (uint32_t *)take(words); off_keep = (uint32_t *)take(words); off_diff = (uint32_t *)take(words);
-        err = (uint64_t *)take(256);                     // the error word, then n_lines
-        void *tmp = take(up(tmp_bytes));
-        uint32_t *cnt_lf = cnt, *cnt_keep = cnt + words / 4, *cnt_diff = cnt + 2 * (words / 4), *d_lines = (uint32_t *)(err + 1);
-        HIP_TRY(hipMemsetAsync(cnt, 0, 3 * words, st));
+        // '\n', kept bytes, kept minus quality bytes: each with a 0 behind the last block's
+        uint32_t *cnt_lf = scratch.words(0), *cnt_keep = scratch.words(1), *cnt_diff = scratch.words(2);
+        line0 = scratch.words(3); off_keep = scratch.words(4); off_diff = scratch.words(5);
+        err = (uint64_t *)scratch.cell();                // the error word, then n_lines
+        uint32_t *d_lines = (uint32_t *)(err + 1);
+        void *tmp = scratch.tmp();
+        HIP_TRY(hipMemsetAsync(cnt_lf, 0, 3 * scratch.stride, st));
         HIP_TRY(hipMemsetAsync(err, 0xFF, 8, st));
         fq_launch_lines(d_bytes, n, nb, cnt_lf, st);
         HIP_TRY(hipGetLastError());
@@ -382,30 +375,23 @@ extern "C" int lime_docs_get_qual(const lime_docs *d, uint8_t *qual)
 // Scratch: 12 bytes per read (lo, length, new offset) + rocPRIM's + two counters, given back before either returns.  The new lengths' total
 // sizes the handle: two synchronisations, like the parse
 namespace {
-struct TrimScratch {                                     // what a bounds kernel fills and trim_finish reads
-    DevBuf buf;
-    uint32_t *lo32 = nullptr, *len32 = nullptr, *new_off = nullptr;
-    uint64_t *d_counts = nullptr;
-    void *tmp = nullptr;
-    size_t tmp_bytes = 0;
+struct TrimScratch : WordScratch {                       // what a bounds kernel fills and trim_finish reads
+    uint32_t *lo32() const { return words(0); }
+    uint32_t *len32() const { return words(1); }
+    uint32_t *new_off() const { return words(2); }
+    uint64_t *d_counts() const { return (uint64_t *)cell(); }
 };
 }
 
 // nd >= 1 reads: the arrays, with the 0 behind the last read's length and the counters cleared
 static int trim_begin(const char *who, uint32_t nd, hipStream_t st, TrimScratch &ts)
 {
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t words = up(((size_t)nd + 1) * 4);
-    HIP_TRY(idx_scan_sum(nullptr, &ts.tmp_bytes, nullptr, nullptr, (size_t)nd + 1, false, st));
-    int rc = ts.buf.alloc(3 * words + 256 + up(ts.tmp_bytes));
+    size_t tmp_bytes = 0;
+    HIP_TRY(idx_scan_sum(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)nd + 1, false, st));
+    int rc = ts.alloc(3, nd, tmp_bytes);
     if (rc) return fail(rc, "%s: no device memory for the trim of %u reads: %s", who, nd, lime_last_error());
-    uint8_t *at = static_cast<uint8_t *>(ts.buf.p);
-    auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
-    ts.lo32 = (uint32_t *)take(words); ts.len32 = (uint32_t *)take(words); ts.new_off = (uint32_t *)take(words);
-    ts.d_counts = (uint64_t *)take(256);
-    ts.tmp = take(up(ts.tmp_bytes));
-    HIP_TRY(hipMemsetAsync(ts.len32 + nd, 0, 4, st));    // (the 0 behind the last read's length: the sum's last entry is the total)
-    HIP_TRY(hipMemsetAsync(ts.d_counts, 0, 16, st));
+    HIP_TRY(hipMemsetAsync(ts.len32() + nd, 0, 4, st));  // (the 0 behind the last read's length: the sum's last entry is the total)
+    HIP_TRY(hipMemsetAsync(ts.d_counts(), 0, 16, st));
     return LIME_OK;
 }
 
@@ -418,15 +404,15 @@ static int trim_finish(lime_ctx *c, const char *who, const lime_docs *docs, Trim
     uint64_t counts[2] = {0, 0};
     if (nd) {
         HIP_TRY(hipGetLastError());
-        HIP_TRY(idx_scan_sum(ts.tmp, &ts.tmp_bytes, ts.len32, ts.new_off, (size_t)nd + 1, false, st));
-        HIP_TRY(hipMemcpyAsync(&n_out, ts.new_off + nd, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(counts, ts.d_counts, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(idx_scan_sum(ts.tmp(), &ts.tmp_bytes, ts.len32(), ts.new_off(), (size_t)nd + 1, false, st));
+        HIP_TRY(hipMemcpyAsync(&n_out, ts.new_off() + nd, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(counts, ts.d_counts(), 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));               // (the total sizes the handle)
     }
     DocsGuard dg;
     int rc = docs_new(c, who, nd, n_out, dg); if (rc) return rc;
     if (nd) {
-        fqt_launch_copy(docs->text.p, docs->doc_off.p, nd, ts.lo32, ts.len32, ts.new_off, dg.d->text.p, dg.d->doc_off.p, st);
+        fqt_launch_copy(docs->text.p, docs->doc_off.p, nd, ts.lo32(), ts.len32(), ts.new_off(), dg.d->text.p, dg.d->doc_off.p, st);
         HIP_TRY(hipGetLastError());
     } else {
         HIP_TRY(hipMemsetAsync(dg.d->doc_off.p, 0, 8, st));
@@ -445,7 +431,7 @@ int lime_host::docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *doc
     TrimScratch ts;
     if (nd) {
         int rc = trim_begin(who, nd, st, ts); if (rc) return rc;
-        fqt_launch_bounds(docs->qual.p, docs->doc_off.p, nd, q5, q3, ts.lo32, ts.len32, ts.d_counts, st);
+        fqt_launch_bounds(docs->qual.p, docs->doc_off.p, nd, q5, q3, ts.lo32(), ts.len32(), ts.d_counts(), st);
     }
     return trim_finish(c, who, docs, ts, st, out, info);
 }
@@ -473,7 +459,7 @@ int lime_host::docs_adapter_impl(lime_ctx *c, const char *who, const lime_docs *
     TrimScratch ts;
     if (nd) {
         int rc = trim_begin(who, nd, st, ts); if (rc) return rc;
-        ad_launch_bounds(docs->text.p, docs->doc_off.p, nd, masks, m, min_overlap, max_err_pct, ts.lo32, ts.len32, ts.d_counts, st);
+        ad_launch_bounds(docs->text.p, docs->doc_off.p, nd, masks, m, min_overlap, max_err_pct, ts.lo32(), ts.len32(), ts.d_counts(), st);
     }
     return trim_finish(c, who, docs, ts, st, out, info);
 }

@@ -22,6 +22,8 @@
 // The line-first byte of line 4k is record start k whatever the block: no count of record starts crosses blocks (document k's entry is
 // written by the lane that holds that byte, at index ln / 4).  Passes 2 and 3 build the same masks (block_marks): 3 reads per input
 // byte and 1 write per kept byte, which are fewer than half of the bytes.
+// block_marks, with the rule above in code, is lime_fastq_marks.h's (the quality pass of lime_fqtrim_kernel.hip takes its mask from it too); the block
+// geometry (BY_*), load_piece, the per-byte masks, the sum over the waves (add_waves) and the write-out (store_staged) are lime_bytes.h's.
 // wave64.  The only cross-lane operations are the DPP prefix sum of lime_wave.h, in wave-uniform control flow (every lane of a
 // workgroup runs every block of its stride loop; a lane past the end holds no bytes).  No inline assembly here, plain vector stores.
 // No byte outside [0, n) is loaded: a 16-byte load is issued only where all 16 bytes are inside, the byte in front of a lane's piece
@@ -31,138 +33,42 @@
 #include "lime_hip.h"
 #include "lime_index.h"
 #include "lime_wave.h"
+#include "lime_bytes.h"
+#include "lime_fastq_marks.h"
 
 namespace lime {
 
 namespace {
 
-constexpr int FQ_WG = 256;
-constexpr uint32_t FQ_LANE = 16;                 // bytes one lane handles per block
-constexpr uint32_t FQ_WAVES = FQ_WG / 64;
-static_assert(LIME_FASTA_BLOCK == FQ_WG * FQ_LANE, "a workgroup pass is one block");
-constexpr uint32_t FQ_BLOCKS = 8192;             // grids are capped and every kernel strides
-
-// the lane's piece [pos, pos + len) of b[0 .. n): bytes past len read as 0 (lime_fasta_kernel.hip's, restated: that file stays as it is)
-__device__ __forceinline__ uint32_t load_piece(const uint8_t *b, uint64_t n, uint64_t pos, uint32_t w[4])
-{
-    w[0] = w[1] = w[2] = w[3] = 0u;
-    if (pos >= n) return 0u;
-    if (pos + FQ_LANE <= n) {
-        uint4 v;
-        __builtin_memcpy(&v, b + pos, 16);                                  // (the input may sit at any alignment)
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        return FQ_LANE;
-    }
-    const uint32_t len = (uint32_t)(n - pos);
-#pragma unroll
-    for (uint32_t j = 0; j < FQ_LANE; ++j)
-        if (j < len) w[j >> 2] |= (uint32_t)b[pos + j] << ((j & 3u) * 8u);
-    return len;
-}
-
-struct Piece {
-    uint32_t w[4];                               // the bytes
-    uint32_t len;
-    uint32_t nl, cr, at, plus;                   // bit j: byte j is '\n', '\r', '@', '+'
-    uint32_t lf;                                 // bit j: byte j is line-first
-};
-
-__device__ __forceinline__ Piece read_piece(const uint8_t *b, uint64_t n, uint64_t pos)
-{
-    Piece p;
-    p.len = load_piece(b, n, pos, p.w);
-    p.nl = p.cr = p.at = p.plus = 0u;
-#pragma unroll
-    for (uint32_t j = 0; j < FQ_LANE; ++j) {
-        const uint32_t ch = (p.w[j >> 2] >> ((j & 3u) * 8u)) & 255u;
-        p.nl |= (uint32_t)(ch == '\n') << j;
-        p.cr |= (uint32_t)(ch == '\r') << j;
-        p.at |= (uint32_t)(ch == '@') << j;
-        p.plus |= (uint32_t)(ch == '+') << j;
-    }
-    const uint32_t in = (1u << p.len) - 1u;                                // (len <= 16)
-    p.nl &= in; p.cr &= in; p.at &= in; p.plus &= in;
-    uint32_t first = 0u;                         // byte 0 of the input reads nothing in front of it
-    if (p.len) first = pos == 0 ? 1u : (uint32_t)(b[pos - 1] == '\n');
-    p.lf = ((p.nl << 1) | first) & in;
-    return p;
-}
-
 // ---- pass 1 ----
-__global__ void __launch_bounds__(FQ_WG) k_fq_lines(const uint8_t *b, uint64_t n, uint32_t n_blocks, uint32_t *cnt_lf)
+__global__ void __launch_bounds__(BY_WG) k_fq_lines(const uint8_t *b, uint64_t n, uint32_t n_blocks, uint32_t *cnt_lf)
 {
-    __shared__ uint32_t s_sum[FQ_WAVES];
+    __shared__ uint32_t s_sum[BY_WAVES];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-        const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * FQ_LANE;
+        const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * BY_LANE;
         uint32_t w[4];
         const uint32_t len = load_piece(b, n, pos, w);
         uint32_t nl = 0u;
 #pragma unroll
-        for (uint32_t j = 0; j < FQ_LANE; ++j) nl += (uint32_t)(j < len && ((w[j >> 2] >> ((j & 3u) * 8u)) & 255u) == '\n');
+        for (uint32_t j = 0; j < BY_LANE; ++j) nl += (uint32_t)(j < len && byte_of(w, j) == '\n');
         const uint32_t incl = wave_incl_scan(nl);
         if (lane == 63u) s_sum[wave] = incl;
         __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t t = 0u;
-            for (uint32_t k = 0; k < FQ_WAVES; ++k) t += s_sum[k];
-            cnt_lf[blk] = t;
-        }
+        if (threadIdx.x == 0) cnt_lf[blk] = add_waves(s_sum, BY_WAVES);
         __syncthreads();
     }
 }
 
-// ---- passes 2 and 3: the masks of a block ----
-struct Marks {
-    uint32_t keep, qual;                         // bit j: byte j of the lane's piece is kept, is a quality byte
-    uint32_t rs;                                 // a record start: the line-first byte of a line 4k
-    uint32_t bad, bad1;                          // a line-first byte that breaks reason 0 or 1; of those, the ones that break reason 1
-    uint32_t end;                                // a record's end
-    uint32_t ln0;                                // ln of the piece's first byte
-};
-
-// the line number of byte j of a piece, counted from 1
-__device__ __forceinline__ uint64_t line_of(const Piece &p, const Marks &m, uint32_t j) { return (uint64_t)m.ln0 + (uint32_t)__builtin_popcount(p.nl & ((1u << j) - 1u)) + 1u; }
-
-// line0: the exclusive sum of pass 1's counts (line0[k] = ln of block k's first byte).  One __syncthreads inside; s_lf is read before the
-// caller's next one, so a caller with a barrier of its own per block may come straight back.
-__device__ __forceinline__ Marks block_marks(const uint8_t *b, uint64_t n, uint32_t blk, const uint32_t *line0, uint32_t *s_lf, Piece &p)
-{
-    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
-    const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * FQ_LANE;
-    p = read_piece(b, n, pos);
-    const uint32_t mine = (uint32_t)__builtin_popcount(p.nl), incl = wave_incl_scan(mine);
-    if (lane == 63u) s_lf[wave] = incl;
-    __syncthreads();
-    Marks m;
-    m.ln0 = line0[blk] + incl - mine;
-    for (uint32_t k = 0; k < wave; ++k) m.ln0 += s_lf[k];
-    uint32_t is0 = 0u, is1 = 0u, is2 = 0u, is3 = 0u, c = m.ln0 & 3u;       // bit j: ln(byte j) % 4 is 0, 1, 2, 3
-#pragma unroll
-    for (uint32_t j = 0; j < FQ_LANE; ++j) {
-        is0 |= (uint32_t)(c == 0u) << j; is1 |= (uint32_t)(c == 1u) << j;
-        is2 |= (uint32_t)(c == 2u) << j; is3 |= (uint32_t)(c == 3u) << j;
-        c = (c + ((p.nl >> j) & 1u)) & 3u;
-    }
-    const uint32_t in = (1u << p.len) - 1u, sym = in & ~p.nl & ~p.cr;
-    m.keep = is1 & sym;
-    m.qual = is3 & sym;
-    m.rs = p.lf & is0;
-    m.bad1 = p.lf & is2 & ~p.plus;
-    m.bad = (p.lf & is0 & ~p.at) | m.bad1;
-    const uint32_t last = p.len && pos + p.len == n ? 1u << (p.len - 1u) : 0u;   // the last input byte
-    m.end = is3 & (p.nl | last);
-    return m;
-}
-
+// ---- passes 2 and 3: the masks of a block are block_marks of lime_fastq_marks.h ----
 // kept bytes in the low half, quality bytes in the high half: a block has at most 4096 of each
 __device__ __forceinline__ uint32_t packed_counts(const Marks &m) { return (uint32_t)__builtin_popcount(m.keep) | ((uint32_t)__builtin_popcount(m.qual) << 16); }
 
 // *err = min(itself, line * 4 + reason) over reasons 0, 1 and 3; *n_lines is written
-__global__ void __launch_bounds__(FQ_WG) k_fq_count(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, uint32_t *cnt_keep, uint32_t *cnt_diff,
+__global__ void __launch_bounds__(BY_WG) k_fq_count(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, uint32_t *cnt_keep, uint32_t *cnt_diff,
                                                     unsigned long long *err, uint32_t *n_lines)
 {
-    __shared__ uint32_t s_lf[FQ_WAVES], s_sum[FQ_WAVES];
+    __shared__ uint32_t s_lf[BY_WAVES], s_sum[BY_WAVES];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
         Piece p;
@@ -173,16 +79,15 @@ __global__ void __launch_bounds__(FQ_WG) k_fq_count(const uint8_t *b, uint64_t n
             const uint32_t j = (uint32_t)__builtin_ctz(m.bad);
             atomicMin(err, line_of(p, m, j) * 4u + ((m.bad1 >> j) & 1u));
         }
-        const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * FQ_LANE;
+        const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * BY_LANE;
         if (p.len && pos + p.len == n) {         // the lane of the last input byte: the total of pass 1 stands behind the last block's entry
             const uint32_t lines = line0[n_blocks] + (((p.nl >> (p.len - 1u)) & 1u) ^ 1u);
             *n_lines = lines;
             if (lines & 3u) atomicMin(err, (unsigned long long)lines * 4u + 3u);
         }
-        __syncthreads();
+        __syncthreads();                         // (the only one of its own: block_marks' stands between this block's reads of s_sum and the next one's post)
         if (threadIdx.x == 0) {
-            uint32_t t = 0u;
-            for (uint32_t k = 0; k < FQ_WAVES; ++k) t += s_sum[k];
+            const uint32_t t = add_waves(s_sum, BY_WAVES);
             cnt_keep[blk] = t & 0xFFFFu;
             cnt_diff[blk] = (t & 0xFFFFu) - (t >> 16);
         }
@@ -190,10 +95,10 @@ __global__ void __launch_bounds__(FQ_WG) k_fq_count(const uint8_t *b, uint64_t n
 }
 
 // off_keep / off_diff: the exclusive sums of pass 2's counts, n_blocks + 1 entries (the last one the total); n_docs = n_lines / 4
-__global__ void __launch_bounds__(FQ_WG) k_fq_write(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep,
+__global__ void __launch_bounds__(BY_WG) k_fq_write(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep,
                                                     const uint32_t *off_diff, uint32_t n_docs, uint8_t *text, uint64_t *doc_off, unsigned long long *err)
 {
-    __shared__ uint32_t s_lf[FQ_WAVES], s_sum[FQ_WAVES];
+    __shared__ uint32_t s_lf[BY_WAVES], s_sum[BY_WAVES];
     __shared__ uint4 s_stage[LIME_FASTA_BLOCK / 16 + 1];                    // the block's kept bytes, placed as in `text` modulo 16
     uint8_t *stage = reinterpret_cast<uint8_t *>(s_stage);
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
@@ -203,14 +108,12 @@ __global__ void __launch_bounds__(FQ_WG) k_fq_write(const uint8_t *b, uint64_t n
         const uint32_t mine = packed_counts(m), incl = wave_incl_scan(mine);
         if (lane == 63u) s_sum[wave] = incl;
         __syncthreads();
-        uint32_t before = incl - mine;           // kept bytes | quality bytes of the block in front of this piece
-        for (uint32_t k = 0; k < wave; ++k) before += s_sum[k];
-        uint32_t total = 0u;
-        for (uint32_t k = 0; k < FQ_WAVES; ++k) total += s_sum[k];
+        // kept bytes | quality bytes of the block in front of this piece, and of the block
+        const uint32_t before = add_waves(s_sum, wave, incl - mine), total = add_waves(s_sum, BY_WAVES);
         const uint32_t base = off_keep[blk], shift = base & 15u, n_keep = total & 0xFFFFu;
         uint32_t at = shift + (before & 0xFFFFu);
 #pragma unroll
-        for (uint32_t j = 0; j < FQ_LANE; ++j)
+        for (uint32_t j = 0; j < BY_LANE; ++j)
             if ((m.keep >> j) & 1u) stage[at++] = (uint8_t)(p.w[j >> 2] >> ((j & 3u) * 8u));
         for (uint32_t rs = m.rs; rs; rs &= rs - 1u) {
             const uint32_t j = (uint32_t)__builtin_ctz(rs);
@@ -227,14 +130,7 @@ __global__ void __launch_bounds__(FQ_WG) k_fq_write(const uint8_t *b, uint64_t n
             }
         }
         __syncthreads();
-        // stage[shift .. shift + n_keep) goes to text[base ..): 16-byte pieces that are whole, bytes at the two ends
-        uint8_t *dst = text + (base - shift);                              // 16-byte aligned, like text itself
-        for (uint32_t c = threadIdx.x; c < LIME_FASTA_BLOCK / 16 + 1; c += FQ_WG) {
-            const uint32_t lo = c * 16u < shift ? shift : c * 16u, hi = c * 16u + 16u > shift + n_keep ? shift + n_keep : c * 16u + 16u;
-            if (lo >= hi) continue;
-            if (hi - lo == 16u) *reinterpret_cast<uint4 *>(dst + c * 16u) = s_stage[c];
-            else for (uint32_t k = lo; k < hi; ++k) dst[k] = stage[k];
-        }
+        store_staged(s_stage, text + (base - shift), shift, n_keep);       // stage[shift .. shift + n_keep) to text[base ..); text is 16-byte aligned
         if (blk == n_blocks - 1u && threadIdx.x == 0) doc_off[n_docs] = off_keep[n_blocks];
         __syncthreads();
     }
@@ -244,22 +140,20 @@ __global__ void __launch_bounds__(FQ_WG) k_fq_write(const uint8_t *b, uint64_t n
 
 void fq_launch_lines(const uint8_t *b, uint64_t n, uint32_t n_blocks, uint32_t *cnt_lf, hipStream_t st)
 {
-    if (n_blocks) k_fq_lines<<<n_blocks < FQ_BLOCKS ? n_blocks : FQ_BLOCKS, FQ_WG, 0, st>>>(b, n, n_blocks, cnt_lf);
+    if (n_blocks) k_fq_lines<<<by_grid(n_blocks), BY_WG, 0, st>>>(b, n, n_blocks, cnt_lf);
 }
 
 void fq_launch_count(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, uint32_t *cnt_keep, uint32_t *cnt_diff, uint64_t *err,
                      uint32_t *n_lines, hipStream_t st)
 {
-    if (n_blocks)
-        k_fq_count<<<n_blocks < FQ_BLOCKS ? n_blocks : FQ_BLOCKS, FQ_WG, 0, st>>>(b, n, n_blocks, line0, cnt_keep, cnt_diff, (unsigned long long *)err, n_lines);
+    if (n_blocks) k_fq_count<<<by_grid(n_blocks), BY_WG, 0, st>>>(b, n, n_blocks, line0, cnt_keep, cnt_diff, (unsigned long long *)err, n_lines);
 }
 
 void fq_launch_write(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep, const uint32_t *off_diff,
                      uint32_t n_docs, uint8_t *text, uint64_t *doc_off, uint64_t *err, hipStream_t st)
 {
     if (n_blocks)
-        k_fq_write<<<n_blocks < FQ_BLOCKS ? n_blocks : FQ_BLOCKS, FQ_WG, 0, st>>>(b, n, n_blocks, line0, off_keep, off_diff, n_docs, text, doc_off,
-                                                                                 (unsigned long long *)err);
+        k_fq_write<<<by_grid(n_blocks), BY_WG, 0, st>>>(b, n, n_blocks, line0, off_keep, off_diff, n_docs, text, doc_off, (unsigned long long *)err);
 }
 
 } // namespace lime

@@ -1,8 +1,8 @@
 // lime_fqtrim_kernel.hip -- the quality bytes of four-line FASTQ kept next to the sequences, and the reads cut at both ends by the BWA /
 // cutadapt quality rule on the device (lime_docs.cpp sequences the passes; include/lime_hip.h states the rule and what
 // lime_quality_trim, the oracle, returns).
-//   k_fq_qual      the fourth pass of the FASTQ parse (lime_fastq_kernel.hip, whose three kernels stay as they are: its masks are restated
-//                  here): the quality bytes (ln(i) % 4 == 3, neither '\n' nor '\r') in order to qual[0 ..), through LDS with 16-byte
+//   k_fq_qual      the fourth pass of the FASTQ parse (lime_fastq_kernel.hip; the masks are its passes' own, block_marks of
+//                  lime_fastq_marks.h): the quality bytes (ln(i) % 4 == 3, neither '\n' nor '\r') in order to qual[0 ..), through LDS with 16-byte
 //                  stores.  The quality bytes in front of block k are off_keep[k] - off_diff[k] modulo 2^32, exactly: both counts are below
 //                  2^32.  A malformed input may hold more quality bytes than kept bytes: only qual[0 .. cap) is ever written.
 //   k_trim_bounds  per read (lo, hi) by the rule; 16 lanes (one DPP row) on a read, 16 quality bytes a lane, 256 symbols a step, four
@@ -15,6 +15,7 @@
 //                  from a butterfly over the row on (value, t) packed into one word.  Across steps the sum, the minimum, t* and
 //                  "stopped" are carried per row, the sums in 64 bits: a read of 10^7 symbols overflows 32.
 //   k_trim_copy    text[doc_off[r] + lo .. + len) to its new place, the same 16 lanes on a read, and the new doc_off.
+// The block geometry (BY_*), the sum over the waves and the write-out (store_staged) are lime_bytes.h's; row_incl_scan and row_min are lime_wave.h's.
 // wave64.  The cross-lane operations (the DPP row prefix sum, the butterfly, the broadcast of a row's total) sit in wave-uniform control
 // flow: the loop over the reads depends on blockIdx and the kernel's arguments alone, the loop over a read's steps on a wave maximum
 // made scalar, and a row whose read has ended or stopped goes through the steps with nothing to add.  No inline assembly, plain vector
@@ -24,98 +25,37 @@
 #include "lime_hip.h"
 #include "lime_index.h"
 #include "lime_wave.h"
+#include "lime_bytes.h"
+#include "lime_fastq_marks.h"
 
 namespace lime {
 
 namespace {
 
-constexpr int FQ_WG = 256;
-constexpr uint32_t FQ_LANE = 16;                 // bytes one lane handles per block
-constexpr uint32_t FQ_WAVES = FQ_WG / 64;
-static_assert(LIME_FASTA_BLOCK == FQ_WG * FQ_LANE, "a workgroup pass is one block");
-constexpr uint32_t FQ_BLOCKS = 8192;             // grids are capped and every kernel strides
-
-// ---- lime_fastq_kernel.hip's pieces and masks, restated: that file stays as it is ----
-__device__ __forceinline__ uint32_t load_piece(const uint8_t *b, uint64_t n, uint64_t pos, uint32_t w[4])
-{
-    w[0] = w[1] = w[2] = w[3] = 0u;
-    if (pos >= n) return 0u;
-    if (pos + FQ_LANE <= n) {
-        uint4 v;
-        __builtin_memcpy(&v, b + pos, 16);                                  // (the input may sit at any alignment)
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        return FQ_LANE;
-    }
-    const uint32_t len = (uint32_t)(n - pos);
-#pragma unroll
-    for (uint32_t j = 0; j < FQ_LANE; ++j)
-        if (j < len) w[j >> 2] |= (uint32_t)b[pos + j] << ((j & 3u) * 8u);
-    return len;
-}
-
-// the quality bytes of the lane's piece of block blk: bit j of the result, the bytes in w.  line0 as for k_fq_count.  One __syncthreads
-// inside; s_lf is read before the caller's next one.
-__device__ __forceinline__ uint32_t qual_marks(const uint8_t *b, uint64_t n, uint32_t blk, const uint32_t *line0, uint32_t *s_lf, uint32_t w[4])
-{
-    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
-    const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * FQ_LANE;
-    const uint32_t len = load_piece(b, n, pos, w);
-    uint32_t nl = 0u, cr = 0u;
-#pragma unroll
-    for (uint32_t j = 0; j < FQ_LANE; ++j) {
-        const uint32_t ch = (w[j >> 2] >> ((j & 3u) * 8u)) & 255u;
-        nl |= (uint32_t)(ch == '\n') << j;
-        cr |= (uint32_t)(ch == '\r') << j;
-    }
-    const uint32_t in = (1u << len) - 1u;                                   // (len <= 16)
-    nl &= in; cr &= in;
-    const uint32_t mine = (uint32_t)__builtin_popcount(nl), incl = wave_incl_scan(mine);
-    if (lane == 63u) s_lf[wave] = incl;
-    __syncthreads();
-    uint32_t ln0 = line0[blk] + incl - mine;                                // ln of the piece's first byte
-    for (uint32_t k = 0; k < wave; ++k) ln0 += s_lf[k];
-    uint32_t is3 = 0u, c = ln0 & 3u;                                        // bit j: ln(byte j) % 4 is 3
-#pragma unroll
-    for (uint32_t j = 0; j < FQ_LANE; ++j) {
-        is3 |= (uint32_t)(c == 3u) << j;
-        c = (c + ((nl >> j) & 1u)) & 3u;
-    }
-    return is3 & in & ~nl & ~cr;
-}
-
 // off_keep / off_diff: the exclusive sums of k_fq_count's counts.  qual: 16-byte aligned, cap bytes may be written
-__global__ void __launch_bounds__(FQ_WG) k_fq_qual(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep,
+__global__ void __launch_bounds__(BY_WG) k_fq_qual(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep,
                                                    const uint32_t *off_diff, uint8_t *qual, uint64_t cap)
 {
-    __shared__ uint32_t s_lf[FQ_WAVES], s_sum[FQ_WAVES];
+    __shared__ uint32_t s_lf[BY_WAVES], s_sum[BY_WAVES];
     __shared__ uint4 s_stage[LIME_FASTA_BLOCK / 16 + 1];                    // the block's quality bytes, placed as in `qual` modulo 16
     uint8_t *stage = reinterpret_cast<uint8_t *>(s_stage);
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-        uint32_t w[4];
-        const uint32_t q = qual_marks(b, n, blk, line0, s_lf, w);
+        Piece p;
+        const uint32_t q = block_marks(b, n, blk, line0, s_lf, p).qual;
         const uint32_t mine = (uint32_t)__builtin_popcount(q), incl = wave_incl_scan(mine);
         if (lane == 63u) s_sum[wave] = incl;
         __syncthreads();
-        uint32_t before = incl - mine, total = 0u;
-        for (uint32_t k = 0; k < wave; ++k) before += s_sum[k];
-        for (uint32_t k = 0; k < FQ_WAVES; ++k) total += s_sum[k];
+        const uint32_t before = add_waves(s_sum, wave, incl - mine), total = add_waves(s_sum, BY_WAVES);
         const uint32_t base = off_keep[blk] - off_diff[blk], shift = base & 15u;          // the quality bytes in front of the block
         const uint64_t room = (uint64_t)base < cap ? cap - base : 0u;                       // what of qual[base ..) may be written
         const uint32_t n_q = (uint64_t)total < room ? total : (uint32_t)room;
         uint32_t at = shift + before;
 #pragma unroll
-        for (uint32_t j = 0; j < FQ_LANE; ++j)
-            if ((q >> j) & 1u) stage[at++] = (uint8_t)(w[j >> 2] >> ((j & 3u) * 8u));       // (at most 4096 + 15: inside s_stage)
+        for (uint32_t j = 0; j < BY_LANE; ++j)
+            if ((q >> j) & 1u) stage[at++] = (uint8_t)(p.w[j >> 2] >> ((j & 3u) * 8u));     // (at most 4096 + 15: inside s_stage)
         __syncthreads();
-        // stage[shift .. shift + n_q) goes to qual[base ..): 16-byte pieces that are whole, bytes at the two ends
-        uint8_t *dst = qual + ((uint64_t)base - shift);
-        for (uint32_t c = threadIdx.x; c < LIME_FASTA_BLOCK / 16 + 1; c += FQ_WG) {
-            const uint32_t lo = c * 16u < shift ? shift : c * 16u, hi = c * 16u + 16u > shift + n_q ? shift + n_q : c * 16u + 16u;
-            if (lo >= hi) continue;
-            if (hi - lo == 16u) *reinterpret_cast<uint4 *>(dst + c * 16u) = s_stage[c];
-            else for (uint32_t k = lo; k < hi; ++k) dst[k] = stage[k];
-        }
+        store_staged(s_stage, qual + ((uint64_t)base - shift), shift, n_q);                 // stage[shift .. shift + n_q) to qual[base ..)
         __syncthreads();
     }
 }
@@ -123,27 +63,10 @@ __global__ void __launch_bounds__(FQ_WG) k_fq_qual(const uint8_t *b, uint64_t n,
 // ---- the trim ----
 constexpr uint32_t TR_ROW = 16;                  // lanes on a read: a DPP row
 constexpr uint32_t TR_STEP = TR_ROW * 16;        // symbols a row handles per step
-constexpr uint32_t TR_READS = FQ_WG / TR_ROW;    // reads a workgroup handles per trip
+constexpr uint32_t TR_READS = BY_WG / TR_ROW;    // reads a workgroup handles per trip
 constexpr uint32_t TR_BLOCKS = 1536;             // six workgroups a CU: k_trim_bounds' registers admit seven, and a grid of eight runs its last one alone
 constexpr int32_t TR_BIAS = 1 << 20;             // above any sum of a step's 256 values, each in -126 .. 222
 constexpr uint32_t TR_NONE = 0xFFFFFFFFu;
-
-// inclusive prefix sum over the 16 lanes of each DPP row (the first four steps of wave_incl_scan)
-__device__ __forceinline__ uint32_t row_incl_scan(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    return v;
-}
-// the minimum over the 16 lanes of each row, in every lane of it
-__device__ __forceinline__ uint32_t row_min(uint32_t v)
-{
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d); v = o < v ? o : v; }
-    return v;
-}
 
 // One end of one read, all 16 lanes of its row: q[0 .. L) the read's quality bytes, rev: the 3' end.  -> t* or TR_NONE, the same in every
 // lane of the row.  n_steps: wave-uniform, at least ceil(L / TR_STEP) of every row of the wave; cut 0: TR_NONE, nothing is loaded.
@@ -224,7 +147,7 @@ __device__ __forceinline__ uint64_t trim_walk(const uint8_t *q, uint64_t L, uint
 
 // lo32[r], len32[r] of every read (len32[n_docs] stays as the caller zeroed it); counts[0] += reads that changed, counts[1] += reads with
 // symbols that keep none
-__global__ void __launch_bounds__(FQ_WG) k_trim_bounds(const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t q5, uint32_t q3,
+__global__ void __launch_bounds__(BY_WG) k_trim_bounds(const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t q5, uint32_t q3,
                                                        uint32_t *lo32, uint32_t *len32, unsigned long long *counts)
 {
     const uint32_t g = threadIdx.x & (TR_ROW - 1u);
@@ -249,7 +172,7 @@ __global__ void __launch_bounds__(FQ_WG) k_trim_bounds(const uint8_t *qual, cons
 }
 
 // new_off: the exclusive sum of len32 over n_docs + 1 entries.  out (16-byte aligned, new_off[n_docs] bytes) and out_off[n_docs + 1]
-__global__ void __launch_bounds__(FQ_WG) k_trim_copy(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint32_t *lo32, const uint32_t *len32,
+__global__ void __launch_bounds__(BY_WG) k_trim_copy(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint32_t *lo32, const uint32_t *len32,
                                                      const uint32_t *new_off, uint8_t *out, uint64_t *out_off)
 {
     const uint32_t g = threadIdx.x & (TR_ROW - 1u);
@@ -280,21 +203,21 @@ __global__ void __launch_bounds__(FQ_WG) k_trim_copy(const uint8_t *text, const 
 void fqt_launch_qual(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *line0, const uint32_t *off_keep, const uint32_t *off_diff, uint8_t *qual,
                      uint64_t cap, hipStream_t st)
 {
-    if (n_blocks) k_fq_qual<<<n_blocks < FQ_BLOCKS ? n_blocks : FQ_BLOCKS, FQ_WG, 0, st>>>(b, n, n_blocks, line0, off_keep, off_diff, qual, cap);
+    if (n_blocks) k_fq_qual<<<by_grid(n_blocks), BY_WG, 0, st>>>(b, n, n_blocks, line0, off_keep, off_diff, qual, cap);
 }
 
 void fqt_launch_bounds(const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t q5, uint32_t q3, uint32_t *lo32, uint32_t *len32,
                        uint64_t *counts, hipStream_t st)
 {
     const uint32_t nb = (n_docs + TR_READS - 1u) / TR_READS;
-    if (nb) k_trim_bounds<<<nb < TR_BLOCKS ? nb : TR_BLOCKS, FQ_WG, 0, st>>>(qual, doc_off, n_docs, q5, q3, lo32, len32, (unsigned long long *)counts);
+    if (nb) k_trim_bounds<<<nb < TR_BLOCKS ? nb : TR_BLOCKS, BY_WG, 0, st>>>(qual, doc_off, n_docs, q5, q3, lo32, len32, (unsigned long long *)counts);
 }
 
 void fqt_launch_copy(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint32_t *lo32, const uint32_t *len32, const uint32_t *new_off,
                      uint8_t *out, uint64_t *out_off, hipStream_t st)
 {
     const uint32_t nb = (n_docs + TR_READS - 1u) / TR_READS;
-    if (nb) k_trim_copy<<<nb < TR_BLOCKS ? nb : TR_BLOCKS, FQ_WG, 0, st>>>(text, doc_off, n_docs, lo32, len32, new_off, out, out_off);
+    if (nb) k_trim_copy<<<nb < TR_BLOCKS ? nb : TR_BLOCKS, BY_WG, 0, st>>>(text, doc_off, n_docs, lo32, len32, new_off, out, out_off);
 }
 
 } // namespace lime

@@ -30,19 +30,15 @@ static int seq_cut(const char *who, const uint8_t *d_bytes, uint64_t n, int form
     out[0] = out[1] = out[2] = 0;
     if (!n) return LIME_OK;                              // (no byte, no marker, no record)
     const uint32_t nb = (uint32_t)((n + LIME_FASTA_BLOCK - 1) / LIME_FASTA_BLOCK);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t words = up(((size_t)nb + 1) * 4);
     size_t tmp_bytes = 0;
     HIP_TRY(idx_scan_sum(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)nb + 1, false, st));
-    DevBuf scratch;
-    int rc = scratch.alloc(2 * words + 256 + up(tmp_bytes));
+    WordScratch scratch;
+    int rc = scratch.alloc(2, nb, tmp_bytes);
     if (rc) return fail(rc, "%s: no device memory for the cut of %llu bytes: %s", who, (unsigned long long)n, lime_last_error());
-    uint8_t *at = static_cast<uint8_t *>(scratch.p);
-    auto take = [&](size_t b) { uint8_t *p = at; at += b; return p; };
-    uint32_t *cnt = (uint32_t *)take(words), *off = (uint32_t *)take(words);     // the blocks' markers with a 0 behind the last block's; their exclusive sum
-    uint64_t *d_out = (uint64_t *)take(256);
-    void *tmp = take(up(tmp_bytes));
-    HIP_TRY(hipMemsetAsync(cnt, 0, words, st));
+    uint32_t *cnt = scratch.words(0), *off = scratch.words(1);             // the blocks' markers with a 0 behind the last block's; their exclusive sum
+    uint64_t *d_out = (uint64_t *)scratch.cell();
+    void *tmp = scratch.tmp();
+    HIP_TRY(hipMemsetAsync(cnt, 0, scratch.stride, st));
     if (format) fq_launch_lines(d_bytes, n, nb, cnt, st);
     else sc_launch_headers(d_bytes, n, nb, cnt, st);
     HIP_TRY(hipGetLastError());

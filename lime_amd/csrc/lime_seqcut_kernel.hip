@@ -12,6 +12,7 @@
 //   2  k_sc_select  every workgroup computes m and the wanted marker from T; the one block whose range of marker numbers holds it reads
 //                   its bytes again, finds the lane and the bit, and that lane writes the three words.  Where no marker is wanted
 //                   (cut = 0 or n) thread 0 of block 0 writes them.  Exactly one lane of the grid writes.
+// The block geometry (BY_*), load_piece, the line-first mask and the sum over the waves (add_waves) are lime_bytes.h's.
 // wave64.  The only cross-lane operation is the DPP prefix sum of lime_wave.h, in wave-uniform control flow: a workgroup skips a block as
 // a whole (a condition on the block's number and the prefix sums alone), and every lane of it runs the blocks it does not skip; a lane
 // past the end holds no bytes.  No inline assembly here, plain vector stores.  No byte outside [0, n) is loaded: a 16-byte load is issued
@@ -21,80 +22,50 @@
 #include "lime_hip.h"
 #include "lime_index.h"
 #include "lime_wave.h"
+#include "lime_bytes.h"
 
 namespace lime {
 
 namespace {
 
-constexpr int SC_WG = 256;
-constexpr uint32_t SC_LANE = 16;                 // bytes one lane handles per block
-constexpr uint32_t SC_WAVES = SC_WG / 64;
-static_assert(LIME_FASTA_BLOCK == SC_WG * SC_LANE, "a workgroup pass is one block");
-constexpr uint32_t SC_BLOCKS = 8192;             // grids are capped and every kernel strides
-
-// the lane's piece [pos, pos + len) of b[0 .. n): bytes past len read as 0 (lime_fasta_kernel.hip's, restated: that file stays as it is)
-__device__ __forceinline__ uint32_t load_piece(const uint8_t *b, uint64_t n, uint64_t pos, uint32_t w[4])
-{
-    w[0] = w[1] = w[2] = w[3] = 0u;
-    if (pos >= n) return 0u;
-    if (pos + SC_LANE <= n) {
-        uint4 v;
-        __builtin_memcpy(&v, b + pos, 16);                                  // (the input may sit at any alignment)
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        return SC_LANE;
-    }
-    const uint32_t len = (uint32_t)(n - pos);
-#pragma unroll
-    for (uint32_t j = 0; j < SC_LANE; ++j)
-        if (j < len) w[j >> 2] |= (uint32_t)b[pos + j] << ((j & 3u) * 8u);
-    return len;
-}
-
-// bit j: byte j of the lane's piece is a marker of `format` (0 FASTA, 1 FASTQ)
+// bit j: byte j of the lane's piece is a marker of `format` (0 FASTA, 1 FASTQ).  The byte in front of the piece is read for FASTA only.
+// (lime_bytes.h's byte_masks gives the same masks; built on it, these two kernels come out as other code, so the two masks are made here)
 __device__ __forceinline__ uint32_t piece_markers(const uint8_t *b, uint64_t n, uint64_t pos, int format)
 {
     uint32_t w[4];
     const uint32_t len = load_piece(b, n, pos, w);
     uint32_t nl = 0u, gt = 0u;
 #pragma unroll
-    for (uint32_t j = 0; j < SC_LANE; ++j) {
-        const uint32_t ch = (w[j >> 2] >> ((j & 3u) * 8u)) & 255u;
-        nl |= (uint32_t)(ch == '\n') << j;
-        gt |= (uint32_t)(ch == '>') << j;
+    for (uint32_t j = 0; j < BY_LANE; ++j) {
+        nl |= (uint32_t)(byte_of(w, j) == '\n') << j;
+        gt |= (uint32_t)(byte_of(w, j) == '>') << j;
     }
     const uint32_t in = (1u << len) - 1u;                                   // (len <= 16)
     nl &= in; gt &= in;
-    if (format) return nl;
-    uint32_t first = 0u;                         // byte 0 of the window reads nothing in front of it
-    if (len) first = pos == 0 ? 1u : (uint32_t)(b[pos - 1] == '\n');
-    return ((nl << 1) | first) & gt;
+    return format ? nl : line_first(b, pos, len, nl) & gt;
 }
 
 // ---- pass 1, FASTA ----
-__global__ void __launch_bounds__(SC_WG) k_sc_headers(const uint8_t *b, uint64_t n, uint32_t n_blocks, uint32_t *cnt)
+__global__ void __launch_bounds__(BY_WG) k_sc_headers(const uint8_t *b, uint64_t n, uint32_t n_blocks, uint32_t *cnt)
 {
-    __shared__ uint32_t s_sum[SC_WAVES];
+    __shared__ uint32_t s_sum[BY_WAVES];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-        const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * SC_LANE;
+        const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * BY_LANE;
         const uint32_t incl = wave_incl_scan((uint32_t)__builtin_popcount(piece_markers(b, n, pos, 0)));
         if (lane == 63u) s_sum[wave] = incl;
         __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t t = 0u;
-            for (uint32_t k = 0; k < SC_WAVES; ++k) t += s_sum[k];
-            cnt[blk] = t;
-        }
+        if (threadIdx.x == 0) cnt[blk] = add_waves(s_sum, BY_WAVES);
         __syncthreads();
     }
 }
 
 // ---- pass 2 ----
 // off: the exclusive sum of pass 1's counts over n_blocks + 1 entries (off[n_blocks] = T).  n > 0, n_blocks = ceil(n / LIME_FASTA_BLOCK).
-__global__ void __launch_bounds__(SC_WG) k_sc_select(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *off, int format, uint32_t max_reads,
+__global__ void __launch_bounds__(BY_WG) k_sc_select(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *off, int format, uint32_t max_reads,
                                                      int eof, unsigned long long *out)
 {
-    __shared__ uint32_t s_sum[SC_WAVES];
+    __shared__ uint32_t s_sum[BY_WAVES];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     const uint32_t T = (uint32_t)__builtin_amdgcn_readfirstlane((int)off[n_blocks]);
     // m, and the wanted marker (want = 0: none, the cut is `fixed`)
@@ -122,13 +93,12 @@ __global__ void __launch_bounds__(SC_WG) k_sc_select(const uint8_t *b, uint64_t 
         // (the same for every lane of the workgroup, and known to the compiler as such: the skip is a scalar branch)
         const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)off[blk]), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)off[blk + 1u]);
         if (marker < lo || marker >= hi) continue;
-        const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * SC_LANE;
+        const uint64_t pos = (uint64_t)blk * LIME_FASTA_BLOCK + threadIdx.x * BY_LANE;
         const uint32_t mk = piece_markers(b, n, pos, format);
         const uint32_t mine = (uint32_t)__builtin_popcount(mk), incl = wave_incl_scan(mine);
         if (lane == 63u) s_sum[wave] = incl;
         __syncthreads();
-        uint32_t before = lo + incl - mine;      // the number of the piece's first marker
-        for (uint32_t k = 0; k < wave; ++k) before += s_sum[k];
+        const uint32_t before = add_waves(s_sum, wave, lo + incl - mine);   // the number of the piece's first marker
         if (marker >= before && marker < before + mine) {
             uint32_t rest = mk;                  // drop the markers in front of the wanted one: its bit is then the lowest
             for (uint32_t k = before; k < marker; ++k) rest &= rest - 1u;
@@ -144,14 +114,14 @@ __global__ void __launch_bounds__(SC_WG) k_sc_select(const uint8_t *b, uint64_t 
 
 void sc_launch_headers(const uint8_t *b, uint64_t n, uint32_t n_blocks, uint32_t *cnt, hipStream_t st)
 {
-    if (n_blocks) k_sc_headers<<<n_blocks < SC_BLOCKS ? n_blocks : SC_BLOCKS, SC_WG, 0, st>>>(b, n, n_blocks, cnt);
+    if (n_blocks) k_sc_headers<<<by_grid(n_blocks), BY_WG, 0, st>>>(b, n, n_blocks, cnt);
 }
 
 void sc_launch_select(const uint8_t *b, uint64_t n, uint32_t n_blocks, const uint32_t *off, int format, uint32_t max_reads, int eof, uint64_t *out,
                       hipStream_t st)
 {
     if (n_blocks)
-        k_sc_select<<<n_blocks < SC_BLOCKS ? n_blocks : SC_BLOCKS, SC_WG, 0, st>>>(b, n, n_blocks, off, format, max_reads, eof, (unsigned long long *)out);
+        k_sc_select<<<by_grid(n_blocks), BY_WG, 0, st>>>(b, n, n_blocks, off, format, max_reads, eof, (unsigned long long *)out);
 }
 
 } // namespace lime

@@ -1,6 +1,6 @@
 // lime_wave.h -- wave64 and lane primitives of the kernels (gfx950): lane reads and writes, ballot ranks, wave sums and the DPP
 // prefix sum, the may_alias types LDS is read and written through, the kernel-argument re-read (cold) and the exact byte add on the
-// table.  Device code only; shared by the kernel files (lime_kernels.hip, lime_partition.hip, lime_apply.hip).
+// table.  Device code only; shared by lime_kernels.hip, lime_partition.hip, lime_apply.hip, lime_adapter_kernel.hip and lime_bytes.h's users.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,6 +108,27 @@ __device__ __forceinline__ void sim_add(uint8_t *sim, uint64_t cell, uint32_t t)
         if (old == expect) break;
         expect = old;
     }
+}
+
+} // namespace lime
+
+namespace lime {
+
+// inclusive prefix sum over the 16 lanes of each DPP row (the first four steps of wave_incl_scan)
+__device__ __forceinline__ uint32_t row_incl_scan(uint32_t v)
+{
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
+    return v;
+}
+// the minimum over the 16 lanes of each row, in every lane of it
+__device__ __forceinline__ uint32_t row_min(uint32_t v)
+{
+#pragma unroll
+    for (int d = 8; d > 0; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d); v = o < v ? o : v; }
+    return v;
 }
 
 } // namespace lime

@@ -83,5 +83,8 @@ def test_fasta_block_is_the_headers():
     header = open(os.path.join(ROOT, "include", "lime_hip.h")).read()
     m = re.search(r"#define\s+LIME_FASTA_BLOCK\s+(\d+)u", header)
     assert m and int(m.group(1)) == api.FASTA_BLOCK
-    kernel = open(os.path.join(ROOT, "lime_amd", "csrc", "lime_fasta_kernel.hip")).read()
-    assert "static_assert(LIME_FASTA_BLOCK == FA_WG * FA_LANE" in kernel
+    csrc = os.path.join(ROOT, "lime_amd", "csrc")
+    shared, kernel = open(os.path.join(csrc, "lime_bytes.h")).read(), open(os.path.join(csrc, "lime_fasta_kernel.hip")).read()
+    assert shared.count("static_assert(LIME_FASTA_BLOCK == BY_WG * BY_LANE") == 1 and len(re.findall(r"static_assert\(\s*LIME_FASTA_BLOCK", shared)) == 1
+    assert '#include "lime_bytes.h"' in kernel and "LIME_FASTA_BLOCK ==" not in kernel
+    assert not re.search(r"\b\w*(WG|LANE)\s*=[^=]", kernel)           # no workgroup size or bytes per lane of its own: lime_bytes.h's

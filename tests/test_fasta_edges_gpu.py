@@ -101,7 +101,7 @@ def test_parser_views_at_every_offset(ctx, tmp_path):
 
 
 def test_parser_past_the_grid_cap(ctx):
-    """The launchers of lime_fasta_kernel.hip cap their grids at FA_BLOCKS = 8192 workgroups, one block of FASTA_BLOCK bytes per trip; whoever
+    """The launchers of lime_fasta_kernel.hip cap their grids at BY_BLOCKS = 8192 workgroups (lime_bytes.h), one block of FASTA_BLOCK bytes per trip; whoever
     changes that changes this.  4 480 000 records '>r' / 'ACGTACGTACG' of 15 bytes are 16 407 blocks: a third trip.  doc_off[k] = 11 k."""
     import torch
     from lime_amd import api

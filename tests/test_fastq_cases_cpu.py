@@ -81,8 +81,11 @@ def test_symbols_exist():
         assert hasattr(api, n), n
     for n in ("docs_from_fastq", "docs_from_fastq_bytes", "docs_from_fastq_bytes_dev", "docs_from_file"):
         assert hasattr(api.Context, n), n
-    kernel = open(os.path.join(ROOT, "lime_amd", "csrc", "lime_fastq_kernel.hip")).read()
-    assert "static_assert(LIME_FASTA_BLOCK == FQ_WG * FQ_LANE" in kernel
+    csrc = os.path.join(ROOT, "lime_amd", "csrc")
+    shared, kernel = open(os.path.join(csrc, "lime_bytes.h")).read(), open(os.path.join(csrc, "lime_fastq_kernel.hip")).read()
+    assert shared.count("static_assert(LIME_FASTA_BLOCK == BY_WG * BY_LANE") == 1 and len(re.findall(r"static_assert\(\s*LIME_FASTA_BLOCK", shared)) == 1
+    assert '#include "lime_bytes.h"' in kernel and "LIME_FASTA_BLOCK ==" not in kernel
+    assert not re.search(r"\b\w*(WG|LANE)\s*=[^=]", kernel)           # no workgroup size or bytes per lane of its own: lime_bytes.h's
 
 
 def test_seq_format(tmp_path):

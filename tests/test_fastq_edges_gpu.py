@@ -149,7 +149,7 @@ def test_views_at_every_offset(ctx, tmp_path):
 
 
 def test_past_the_grid_cap(ctx):
-    """The launchers of lime_fastq_kernel.hip cap their grids at FQ_BLOCKS = 8192 workgroups, one block of FASTA_BLOCK bytes per trip; whoever
+    """The launchers of lime_fastq_kernel.hip cap their grids at BY_BLOCKS = 8192 workgroups (lime_bytes.h), one block of FASTA_BLOCK bytes per trip; whoever
     changes that changes this.  4 200 100 records of 16 bytes are 16 407 blocks: a third trip.  doc_off[k] = 4 k.  Then one quality byte of a
     record in block 16 390, which the third trip handles, becomes a CR: its line, reason 2."""
     import torch

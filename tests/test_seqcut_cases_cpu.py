@@ -169,8 +169,12 @@ def test_symbols_exist():
     for n in ("seq_reader", "seq_reader_bytes", "seq_cut_dev", "classify_sample_stream"):
         assert hasattr(api.Context, n), n
     assert hasattr(api, "ClassificationWriter") and hasattr(api.SeqReader, "next") and hasattr(api.SeqReader, "__iter__")
-    kernel = open(os.path.join(ROOT, "lime_amd", "csrc", "lime_seqcut_kernel.hip")).read()
-    assert "static_assert(LIME_FASTA_BLOCK == SC_WG * SC_LANE" in kernel and "asm" not in kernel
+    csrc = os.path.join(ROOT, "lime_amd", "csrc")
+    shared, kernel = open(os.path.join(csrc, "lime_bytes.h")).read(), open(os.path.join(csrc, "lime_seqcut_kernel.hip")).read()
+    assert shared.count("static_assert(LIME_FASTA_BLOCK == BY_WG * BY_LANE") == 1 and len(re.findall(r"static_assert\(\s*LIME_FASTA_BLOCK", shared)) == 1
+    assert '#include "lime_bytes.h"' in kernel and "LIME_FASTA_BLOCK ==" not in kernel
+    assert not re.search(r"\b\w*(WG|LANE)\s*=[^=]", kernel)           # no workgroup size or bytes per lane of its own: lime_bytes.h's
+    assert "asm" not in kernel and "asm" not in shared
     make = open(os.path.join(ROOT, "lime_amd", "csrc", "Makefile")).read()
     assert "lime_seqcut_kernel.hip -o $$d/lime_seqcut.s" in make and "seqcut_kres.txt" in make
 
