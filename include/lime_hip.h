@@ -574,6 +574,34 @@ int lime_quality_trim(const uint8_t *text, const uint8_t *qual, const uint64_t *
  * max_err_pct above 50, doc_off that does not start at 0 or decreases. */
 int lime_adapter_trim(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint8_t *adapter, uint32_t m, uint32_t min_overlap,
                       uint32_t max_err_pct, uint8_t **out_text, uint64_t **out_doc_off, lime_trim_info_t *info);
+/* The read filter: poly-X tails, a length cap, and reads dropped for their length, their N's or their complexity (what fastp and cutadapt
+ * do behind the trims).  Integers only.  class(byte) is A, C, G or T after folding with & 0xDF (acgt are taken as ACGT); every other byte
+ * -- N, IUPAC codes, anything -- is the one class "other".  The read is s[0 .. L).  The steps, in this order:
+ *   1. Poly-X tail.  polyx_mask: bit 0 is A, bit 1 C, bit 2 G, bit 3 T; 0 switches the step off.  polyx_min T, 1 .. 255 (LiME_fasta's
+ *      default: 10).  For a base X of the mask and a tail length t, 1 <= t <= L: mm_X(t) = the number of j in [L - t, L) with
+ *      class(s[j]) != X.  t is admissible for X when t >= T, class(s[L - t]) = X and 8 * mm_X(t) <= t: one mismatch per eight symbols, and
+ *      the tail begins with X.  t* = the LARGEST admissible t over every X of the mask, each X on its own; 0 without one.  hi = L - t*.
+ *      Admissibility is not monotone in t: the rule takes the largest t, not the first run.
+ *   2. Cap.  max_len K, 0 for none: hi = min(hi, K).
+ *   3. Filters on the kept s[0 .. n), n = hi; the first that fails empties the read, and the read is counted under that reason alone.  A
+ *      read that came in empty (L = 0) is counted nowhere.
+ *        short           n < min_len (0: off).
+ *        many N          the number of j < n with class(s[j]) = other exceeds max_n (LIME_FILTER_OFF: no limit).
+ *        low complexity  min_complexity C, 0 .. 100 percent, 0 for off: with d = the number of j in [0, n - 1) with
+ *                        class(s[j]) != class(s[j + 1]), the read fails when n >= 2 and 100 * d < C * (n - 1); n < 2 passes (fastp's
+ *                        measure, taken on classes).
+ * Read indices never change, as for both trims: an emptied read is an empty document and no read is dropped.
+ * lime_filter_info_t: n_reads; n_polyx, the reads with t* > 0; n_capped, the reads that step 2 shortened; the reads each filter emptied;
+ * the symbols before and after.
+ * lime_read_filter is the loop form in plain host code, the oracle of lime_docs_filter_dev: text / doc_off[n_docs + 1] as the readers give
+ * them; *out_text (at least one byte) and *out_doc_off[n_docs + 1] are library-owned (lime_free); info may be NULL.  LIME_ERR_ARG with a
+ * text: a NULL array, polyx_mask above 15, polyx_min of 0 or above 255 while the mask is set, min_complexity above 100, every field at
+ * its off value (nothing asked), doc_off that does not start at 0 or decreases. */
+typedef struct { uint32_t polyx_mask, polyx_min, max_len, min_len, max_n, min_complexity; } lime_filter_t;
+#define LIME_FILTER_OFF 0xFFFFFFFFu   /* max_n: no limit */
+typedef struct { uint64_t n_reads, n_polyx, n_capped, n_short, n_many_n, n_low_complexity, symbols_in, symbols_out; } lime_filter_info_t;
+int lime_read_filter(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const lime_filter_t *filter, uint8_t **out_text, uint64_t **out_doc_off,
+                     lime_filter_info_t *info);
 /* *format = 1 (FASTQ) if the file's first byte is '@', else 0 (FASTA: an empty file and text in front of the first header included).
  * LIME_ERR_IO when the file cannot be read.  Pure host code. */
 int lime_seq_format(const char *path, int *format);
@@ -692,6 +720,14 @@ int  lime_docs_trim_dev(lime_ctx *ctx, const lime_docs *docs, uint32_t q5, uint3
  * *out is NULL.  Synchronises `stream`. */
 int  lime_docs_trim_adapter_dev(lime_ctx *ctx, const lime_docs *docs, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct,
                                 void *stream, lime_docs **out, lime_trim_info_t *info);
+/* The documents filtered by the rule at lime_read_filter, on the device: *out = new documents (the caller's; no qualities) whose text and
+ * doc_off are byte for byte lime_read_filter's, *info (may be NULL) its counts.  Any documents are taken, with or without qualities, either
+ * trim's output included.  k_filter_bounds (lime_filter_kernel.hip) finds what every read keeps -- one wave on a read, 64 symbols a word,
+ * four class ballots a word: the tail walked from the last word down, the N's and the equal neighbours counted by set bits -- and the
+ * prefix sum and k_trim_copy of lime_docs_trim_dev follow.  Device memory next to the two handles: 12 bytes per read + the prefix sum's,
+ * given back before the call returns.  LIME_ERR_ARG with a text, before any launch: a NULL argument, documents of another context, and
+ * lime_read_filter's refusals of the parameters.  On every error nothing stays allocated and *out is NULL.  Synchronises `stream`. */
+int  lime_docs_filter_dev(lime_ctx *ctx, const lime_docs *docs, const lime_filter_t *filter, void *stream, lime_docs **out, lime_filter_info_t *info);
 /* lime_docs_from_fastq or lime_docs_from_fasta, by lime_seq_format(path): the one place a file's format is decided */
 int  lime_docs_from_file(lime_ctx *ctx, const char *path, lime_docs **out);
 /* documents that are parsed already (copied); doc_off is checked on the device by lime_build_index's rules: LIME_ERR_ARG */
@@ -806,6 +842,12 @@ int  lime_seq_reader_trim_info(const lime_seq_reader *r, lime_trim_info_t *info)
  * handed out so far (zeros without set_adapter); symbols_in counts what the adapter trim was given, the quality trim's output included. */
 int  lime_seq_reader_set_adapter(lime_seq_reader *r, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct);
 int  lime_seq_reader_adapter_info(const lime_seq_reader *r, lime_trim_info_t *info);
+/* set_filter: from here on every batch is handed out filtered (lime_docs_filter_dev), a FASTA reader's too: third, behind the quality trim
+ * and the adapter trim where those are set.  LIME_ERR_ARG with a text: lime_read_filter's refusals of the parameters, a reader whose
+ * lime_seq_reader_next has been called.  filter_info: the sums over the batches handed out so far (zeros without set_filter); symbols_in
+ * counts what the filter was given, the trims' output included. */
+int  lime_seq_reader_set_filter(lime_seq_reader *r, const lime_filter_t *filter);
+int  lime_seq_reader_filter_info(const lime_seq_reader *r, lime_filter_info_t *info);
 void lime_seq_reader_close(lime_seq_reader *r);
 
 /* lime_classify_sample_dev batch by batch: per batch, batch_reads (>= 1) records from each of the n_mates readers, one unchanged

@@ -38,6 +38,19 @@ class TrimInfo(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_changed", C.c_uint64), ("n_empty", C.c_uint64), ("symbols_in", C.c_uint64), ("symbols_out", C.c_uint64)]
 
 
+FILTER_OFF = 0xFFFFFFFF                      # LIME_FILTER_OFF: lime_filter_t.max_n without a limit
+
+
+class Filter(C.Structure):                   # lime_filter_t
+    _fields_ = [("polyx_mask", C.c_uint32), ("polyx_min", C.c_uint32), ("max_len", C.c_uint32), ("min_len", C.c_uint32), ("max_n", C.c_uint32),
+                ("min_complexity", C.c_uint32)]
+
+
+class FilterInfo(C.Structure):               # lime_filter_info_t
+    _fields_ = [("n_reads", C.c_uint64), ("n_polyx", C.c_uint64), ("n_capped", C.c_uint64), ("n_short", C.c_uint64), ("n_many_n", C.c_uint64),
+                ("n_low_complexity", C.c_uint64), ("symbols_in", C.c_uint64), ("symbols_out", C.c_uint64)]
+
+
 class LimeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"lime error {code}: {msg}")
@@ -170,6 +183,10 @@ SYMBOLS = {
     "lime_docs_trim_adapter_dev": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _pp, C.POINTER(TrimInfo)]),
     "lime_seq_reader_set_adapter": (_i, [_vp, _vp, _u32, _u32, _u32]),
     "lime_seq_reader_adapter_info": (_i, [_vp, C.POINTER(TrimInfo)]),
+    "lime_read_filter": (_i, [_vp, _vp, _u32, C.POINTER(Filter), _pp, _pp, C.POINTER(FilterInfo)]),
+    "lime_docs_filter_dev": (_i, [_vp, _vp, C.POINTER(Filter), _vp, _pp, C.POINTER(FilterInfo)]),
+    "lime_seq_reader_set_filter": (_i, [_vp, C.POINTER(Filter)]),
+    "lime_seq_reader_filter_info": (_i, [_vp, C.POINTER(FilterInfo)]),
     "lime_docs_from_file": (_i, [_vp, C.c_char_p, _pp]),
     "lime_docs_from_arrays_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _pp]),
     "lime_docs_revcomp": (_i, [_vp, _vp, _vp, _pp]),

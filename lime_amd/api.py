@@ -505,6 +505,16 @@ class Context:
         check(self.lib.lime_docs_trim_adapter_dev(self.h, docs.h, a, len(a), int(min_overlap), int(max_err_pct), stream, C.byref(h), C.byref(ti)))
         return self._docs_of(h), _trim_info(ti)
 
+    def docs_filter(self, docs, polyx=None, polyx_min=10, max_len=0, min_len=0, max_n=None, min_complexity=0, stream=None):
+        """any Docs through the read filter (lime_docs_filter_dev; the rule is at lime_read_filter in include/lime_hip.h): polyx, the bases whose
+        tails are cut ("G", "GA", or the mask), of polyx_min symbols or more; max_len, the cap; then reads shorter than min_len, with more than
+        max_n N's (None: no limit) or below min_complexity percent are emptied -> (Docs without qualities, info: dict of n_reads, n_polyx,
+        n_capped, n_short, n_many_n, n_low_complexity, symbols_in, symbols_out)"""
+        f = _filter_of(polyx, polyx_min, max_len, min_len, max_n, min_complexity)
+        h, fi = C.c_void_p(), _lib.FilterInfo()
+        check(self.lib.lime_docs_filter_dev(self.h, docs.h, C.byref(f), stream, C.byref(h), C.byref(fi)))
+        return self._docs_of(h), _filter_info(fi)
+
     def docs_from_file(self, path):
         """a FASTA or FASTQ file, by seq_format(path) -> Docs"""
         h = C.c_void_p()
@@ -623,6 +633,31 @@ def _trim_info(ti):
     return {k: int(getattr(ti, k)) for k, _ in _lib.TrimInfo._fields_}
 
 
+def _filter_info(fi):
+    return {k: int(getattr(fi, k)) for k, _ in _lib.FilterInfo._fields_}
+
+
+def polyx_mask(polyx):
+    """None, "", "G", "GA", b"ga" or the mask itself -> lime_filter_t.polyx_mask: bit 0 is A, bit 1 C, bit 2 G, bit 3 T"""
+    if polyx is None:
+        return 0
+    if isinstance(polyx, (int, np.integer)):
+        return int(polyx)
+    mask = 0
+    for ch in (polyx.decode("latin-1") if isinstance(polyx, (bytes, bytearray)) else polyx).upper():
+        if ch not in "ACGT":
+            raise ValueError("the poly-X bases are of A, C, G and T")
+        mask |= 1 << "ACGT".index(ch)
+    return mask
+
+
+def _filter_of(polyx, polyx_min, max_len, min_len, max_n, min_complexity):
+    vals = (polyx_mask(polyx), int(polyx_min), int(max_len), int(min_len), _lib.FILTER_OFF if max_n is None else int(max_n), int(min_complexity))
+    if any(not 0 <= v <= 0xFFFFFFFF for v in vals):
+        raise ValueError("the filter's parameters are unsigned 32-bit numbers")
+    return _lib.Filter(*vals)
+
+
 def _adapter_bytes(adapter):
     return adapter.encode("latin-1") if isinstance(adapter, str) else bytes(adapter)
 
@@ -636,6 +671,21 @@ def _adapters(trim_adapter, n_reads):
     if len(ad) == 2 and n_reads != 2:
         raise ValueError("trim_adapter: a second adapter needs a second reads file")
     return ad * 2 if len(ad) == 1 else ad
+
+
+def _polyx_arg(trim_polyx):
+    """None, "G", "GA,12" or (BASES, T) -> (mask, T), as `--trim-polyx` reads them (T defaults to 10)"""
+    if trim_polyx is None:
+        return 0, 10
+    if isinstance(trim_polyx, bytes):
+        trim_polyx = trim_polyx.decode("latin-1")
+    parts = trim_polyx.split(",") if isinstance(trim_polyx, str) else list(trim_polyx)
+    if len(parts) not in (1, 2) or not parts[0]:
+        raise ValueError("trim_polyx is BASES or (BASES, T): BASES of A, C, G and T, T 1 .. 255")
+    mask, t = polyx_mask(parts[0]), int(parts[1]) if len(parts) == 2 else 10
+    if not 1 <= mask <= 15 or not 1 <= t <= 255:
+        raise ValueError("trim_polyx is BASES or (BASES, T): BASES of A, C, G and T, T 1 .. 255")
+    return mask, t
 
 
 def _trim_cutoffs(trim_qual):
@@ -690,6 +740,18 @@ class SeqReader:
         ti = _lib.TrimInfo()
         check(self.ctx.lib.lime_seq_reader_adapter_info(self.h, C.byref(ti)))
         return _trim_info(ti)
+
+    def set_filter(self, polyx=None, polyx_min=10, max_len=0, min_len=0, max_n=None, min_complexity=0):
+        """every batch from here on is handed out filtered, behind the quality trim and the adapter trim where those are set
+        (lime_seq_reader_set_filter: before the first next; FASTA or FASTQ; the parameters as Context.docs_filter takes them)"""
+        f = _filter_of(polyx, polyx_min, max_len, min_len, max_n, min_complexity)
+        check(self.ctx.lib.lime_seq_reader_set_filter(self.h, C.byref(f)))
+
+    def filter_info(self):
+        """the filter's counts summed over the batches handed out so far -> dict as Context.docs_filter gives"""
+        fi = _lib.FilterInfo()
+        check(self.ctx.lib.lime_seq_reader_filter_info(self.h, C.byref(fi)))
+        return _filter_info(fi)
 
     def trim_info(self):
         """the trim's counts summed over the batches handed out so far -> dict as Context.docs_trim gives"""
@@ -1089,6 +1151,21 @@ def adapter_trim(text, doc_off, adapter, min_overlap=3, max_err_pct=10):
     return new_text, new_off, _trim_info(ti)
 
 
+def read_filter(text, doc_off, polyx=None, polyx_min=10, max_len=0, min_len=0, max_n=None, min_complexity=0):
+    """the read filter's rule in plain host code (lime_read_filter; the parameters as Context.docs_filter takes them) -> (text, doc_off, info dict)"""
+    lib = _lib.load()
+    t = np.ascontiguousarray(text, dtype=np.uint8); off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    f = _filter_of(polyx, polyx_min, max_len, min_len, max_n, min_complexity)
+    pt, po, fi = C.c_void_p(), C.c_void_p(), _lib.FilterInfo()
+    check(lib.lime_read_filter(t.ctypes.data if len(t) else None, off.ctypes.data, len(off) - 1, C.byref(f), C.byref(pt), C.byref(po), C.byref(fi)))
+    try:
+        new_off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(len(off),)).copy()
+        new_text = np.frombuffer(C.string_at(pt, int(new_off[-1])), dtype=np.uint8).copy()
+    finally:
+        lib.lime_free(pt); lib.lime_free(po)
+    return new_text, new_off, _filter_info(fi)
+
+
 def seq_format(path):
     """"fastq" if the file's first byte is '@', else "fasta" (lime_seq_format)"""
     f = C.c_int(0)
@@ -1177,7 +1254,7 @@ def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, thread
 
 def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16, beta=0.25, rank=1, trlcp=0, ebwt=True, higher=False, binary=True,
                ctx=None, batch_reads=0, window_bytes=0, trim_qual=None, trim_adapter=None,
-               adapter_overlap=3, adapter_error=10):
+               adapter_overlap=3, adapter_error=10, trim_polyx=None, max_len=0, min_len=0, max_n=None, min_complexity=0):
     """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen (L | auto) --out output
     [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta (read_len="auto": every read by its own length): the files are parsed on the device (each reads file
     FASTA or four-line FASTQ, by its first byte; refs FASTA), the
@@ -1188,6 +1265,9 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     trim_adapter: `--trim-adapter`, SEQ or (SEQ, SEQ2) (SEQ2 for the second reads file), with adapter_overlap and adapter_error
     (`--adapter-overlap`, `--adapter-error`): the reads, FASTA or FASTQ, are cut where the 3' adapter begins, behind the quality trim;
     read_len must be "auto".
+    trim_polyx, max_len, min_len, max_n, min_complexity: `--trim-polyx BASES[,T]` ("G", "GA,12" or (BASES, T)), `--max-len`, `--min-len`,
+    `--max-n`, `--min-complexity`: the read filter (Context.docs_filter), behind both trims, each mate on its own.  trim_polyx and max_len
+    change lengths and need read_len="auto"; the other three only empty reads and are taken with a fixed read_len too.
     -> counts {C, U, A, H}"""
     reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
     if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
@@ -1205,6 +1285,14 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
             raise ValueError("LiME_fasta: trim_adapter needs read_len=\"auto\": a fixed norm does not fit trimmed reads")
         if not 1 <= int(adapter_overlap) <= min(len(a) for a in adapters) or not 0 <= int(adapter_error) <= 50:
             raise ValueError("LiME_fasta: adapter_overlap is 1 .. the adapter's length, adapter_error 0 .. 50")
+    flt = None
+    if trim_polyx is not None or max_len or min_len or max_n is not None or min_complexity:
+        px, px_min = _polyx_arg(trim_polyx)
+        if (px or max_len) and read_len != "auto":
+            raise ValueError("LiME_fasta: trim_polyx and max_len need read_len=\"auto\": a fixed norm does not fit shortened reads")
+        if not 0 <= int(min_complexity) <= 100 or int(max_len) < 0 or int(min_len) < 0 or (max_n is not None and int(max_n) < 0):
+            raise ValueError("LiME_fasta: min_complexity is 0 .. 100 percent; max_len, min_len and max_n are not negative")
+        flt = dict(polyx=px, polyx_min=px_min, max_len=max_len, min_len=min_len, max_n=max_n, min_complexity=min_complexity)
     norm = NORM_PER_READ if read_len == "auto" else ((int(read_len) & 0xFF) + 1 - int(alpha)) & 0xFFFFFFFF     # (`--readlen auto`)
     own = ctx is None
     ctx = ctx or Context()
@@ -1229,6 +1317,13 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
                     m.set_adapter(adapters[k], adapter_overlap, adapter_error)
                 else:
                     mates[k] = ctx.docs_trim_adapter(m, adapters[k], adapter_overlap, adapter_error)[0]
+                    m.close()
+        if flt is not None:
+            for k, m in enumerate(mates):
+                if batch_reads:
+                    m.set_filter(**flt)
+                else:
+                    mates[k] = ctx.docs_filter(m, **flt)[0]
                     m.close()
         if refs is not None:
             g = ctx.docs_from_fasta(refs)

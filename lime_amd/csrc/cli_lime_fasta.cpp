@@ -2,6 +2,7 @@
 //   LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
 //              [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]
 //              [--trim-adapter SEQ[,SEQ2] [--adapter-overlap O] [--adapter-error E]]
+//              [--trim-polyx BASES[,T]] [--max-len K] [--min-len M] [--max-n K] [--min-complexity C]
 // Each reads file is FASTA or four-line FASTQ, decided by its first byte ('@': FASTQ; lime_docs_from_file), the mates each on their own;
 // --refs is FASTA.  The files' bytes go to the device as they are and are parsed there; per collection (reads_1, its reverse
 // complements, reads_2, its reverse complements: the script's `seqtk seq -r`) the reads are merged into the genome index, scanned and
@@ -33,6 +34,14 @@
 // kit differ); one SEQ serves every mate.  FASTA and FASTQ reads files are taken; --readlen must be auto, for --trim-qual's reason.  With
 // --trim-qual every read is cut by quality first and at its adapter second.  The rest is as for --trim-qual: each mate on its own, the
 // reverse complements from the trimmed reads, an emptied read stays in its place, one line of counts per reads file.
+// --trim-polyx BASES[,T], --max-len K, --min-len M, --max-n K, --min-complexity C: the read filter, by the rule at lime_read_filter in
+// include/lime_hip.h, on the device, behind both trims.  --trim-polyx G (or GA,12): the longest tail of at least T symbols (default 10) of one
+// of BASES, with at most one other symbol per eight, is cut: the poly-G tails of two-colour instruments.  --max-len K: what remains is cut
+// to K symbols; --max-len 255 is how a file with longer reads runs under --readlen auto.  Then a read of fewer than M symbols, with more than
+// K symbols that are no base (N), or with fewer than C percent of its neighbouring symbols different (fastp's complexity) is emptied and
+// stays in its place as an empty read (verdict U).  --trim-polyx and --max-len change lengths and need --readlen auto, for --trim-qual's
+// reason; the other three only empty reads and are taken with a fixed --readlen L too.  Each mate on its own, the reverse complements from
+// the filtered reads, one line of counts per reads file.
 // The defaults are the script's constants (LiME_paired.sh:21-23); norm = readLen + 1 - alpha (ClusterBWT_DA.cpp:555).  The reference's
 // compile-time switches are environment variables, as for the other drop-ins: LIME_EBWT (default 1), LIME_BIN (default 1), LIME_HIGHER (0).
 #include <string.h>
@@ -84,6 +93,45 @@ static void print_adapter(const char *file, const std::string &ad, unsigned over
               << t.n_empty << " emptied, " << t.symbols_in << " symbols before, " << t.symbols_out << " after." << std::endl;
 }
 
+// digits only, at most nine of them -> *v
+static bool parse_u32(const char *s, unsigned *v)
+{
+    unsigned x = 0;
+    int digits = 0;
+    for (; *s; ++s) {
+        if (*s < '0' || *s > '9' || digits == 9) return false;
+        x = x * 10 + (unsigned)(*s - '0'); ++digits;
+    }
+    *v = x;
+    return digits > 0;
+}
+
+// "BASES" or "BASES,T": BASES 1 or more of ACGTacgt, T 1 .. 255 (default 10)
+static bool parse_polyx(const char *s, lime_filter_t *f)
+{
+    unsigned mask = 0, t = 10;
+    const char *comma = strchr(s, ',');
+    for (const char *p = s; *p && p != comma; ++p) {
+        const char *at = static_cast<const char *>(memchr("ACGT", *p & 0xDF, 4));
+        if (!at) return false;
+        mask |= 1u << (at - "ACGT");
+    }
+    if (!mask || (comma && (!parse_u32(comma + 1, &t) || !t || t > 255))) return false;
+    f->polyx_mask = mask; f->polyx_min = t;
+    return true;
+}
+
+static void print_filter(const char *file, const lime_filter_t &f, const lime_filter_info_t &t)
+{
+    std::string bases;
+    for (int b = 0; b < 4; ++b) if (f.polyx_mask >> b & 1u) bases += "ACGT"[b];
+    std::cout << file << ": read filter (poly-X " << (bases.empty() ? "-" : bases) << "," << (f.polyx_mask ? f.polyx_min : 0) << ", max-len " << f.max_len << ", min-len " << f.min_len << ", max-n ";
+    if (f.max_n == LIME_FILTER_OFF) std::cout << "-"; else std::cout << f.max_n;
+    std::cout << ", min-complexity " << f.min_complexity << "%): " << t.n_polyx << " of " << t.n_reads << " reads with a poly-X tail, " << t.n_capped << " capped, " << t.n_short
+              << " short, " << t.n_many_n << " with many N, " << t.n_low_complexity << " of low complexity, " << t.symbols_in << " symbols before, " << t.symbols_out
+              << " after." << std::endl;
+}
+
 static int env_flag(const char *name, int dflt)
 {
     const char *s = getenv(name);
@@ -126,6 +174,8 @@ int main(int argc, char **argv)
     int n_adapters = 0;
     unsigned ad_overlap = 3, ad_err = 10;
     bool have_ad_opt = false;
+    lime_filter_t flt = {0, 0, 0, 0, LIME_FILTER_OFF, 0};      // --trim-polyx, --max-len, --min-len, --max-n, --min-complexity
+    bool filter = false;
     unsigned long long window_bytes = 0;
     bool batched = false, have_window = false;
     float beta = 0.25f;
@@ -151,6 +201,13 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--trim-adapter")) { if (more && parse_adapters(argv[i + 1], adapters, &n_adapters)) ++i; else bad = true; }
         else if (!strcmp(argv[i], "--adapter-overlap")) { if (more && sscanf(argv[i + 1], "%u", &ad_overlap) == 1 && ad_overlap) { ++i; have_ad_opt = true; } else bad = true; }
         else if (!strcmp(argv[i], "--adapter-error")) { if (more && sscanf(argv[i + 1], "%u", &ad_err) == 1 && ad_err <= 50) { ++i; have_ad_opt = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--trim-polyx")) { if (more && parse_polyx(argv[i + 1], &flt)) { ++i; filter = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--max-len")) { if (more && parse_u32(argv[i + 1], &flt.max_len) && flt.max_len) { ++i; filter = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--min-len")) { if (more && parse_u32(argv[i + 1], &flt.min_len) && flt.min_len) { ++i; filter = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--max-n")) { if (more && parse_u32(argv[i + 1], &flt.max_n)) { ++i; filter = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--min-complexity")) {
+            if (more && parse_u32(argv[i + 1], &flt.min_complexity) && flt.min_complexity && flt.min_complexity <= 100) { ++i; filter = true; } else bad = true;
+        }
         else if (!strcmp(argv[i], "--window-bytes")) { if (more && sscanf(argv[i + 1], "%llu", &window_bytes) == 1 && window_bytes) { ++i; have_window = true; } else bad = true; }
         else reads.push_back(argv[i]);
     }
@@ -159,6 +216,7 @@ int main(int argc, char **argv)
     const bool cut_adapter = n_adapters > 0;
     if (cut_adapter && !len_auto) bad = true;      // (the same)
     if (have_ad_opt && !cut_adapter) bad = true;
+    if ((flt.polyx_mask || flt.max_len) && !len_auto) bad = true;          // (the same; the three filters only empty reads)
     if (n_adapters == 2 && reads.size() != 2) bad = true;
     for (int k = 0; k < n_adapters; ++k) if (ad_overlap > adapters[k].size()) bad = true;
     if (n_adapters == 1) adapters[1] = adapters[0];
@@ -167,6 +225,7 @@ int main(int argc, char **argv)
         std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx [--gidx next.gidx ...]) --lineage LineageFile --readlen (L | auto) --out output\n"
                   << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]\n"
                   << "           [--trim-adapter SEQ[,SEQ2] [--adapter-overlap 3] [--adapter-error 10]]\n"
+                  << "           [--trim-polyx BASES[,10]] [--max-len K] [--min-len M] [--max-n K] [--min-complexity C]\n"
                   << "  classifies the reads of one sample (one file: single-end, two: paired-end) against the genomes of refs.fasta, or of an\n"
                   << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  A reads file is FASTA or\n"
                   << "  four-line FASTQ, by its first byte ('@': FASTQ), each mate on its own; refs.fasta is FASTA.  --trlcp k: lcp values\n"
@@ -185,6 +244,12 @@ int main(int argc, char **argv)
                   << "  leftmost match of at least --adapter-overlap O symbols (1 .. the adapter's length) with at most --adapter-error E percent\n"
                   << "  of them wrong (0 .. 50), on the device; SEQ,SEQ2: SEQ2 for reads_2.  FASTA or FASTQ; --readlen must be auto; behind\n"
                   << "  --trim-qual where both are given; one line of counts per reads file.\n"
+                  << "  --trim-polyx BASES[,T]: the longest tail of at least T symbols (1 .. 255, default 10) of one of BASES (of ACGT; G for the\n"
+                  << "  poly-G tails of two-colour instruments) with at most one other symbol per eight is cut; --max-len K: what remains is cut to K\n"
+                  << "  symbols (--max-len 255: how a file with longer reads runs).  Both need --readlen auto.  --min-len M, --max-n K,\n"
+                  << "  --min-complexity C (1 .. 100): a read of fewer than M symbols, with more than K symbols that are no base, or with fewer than C\n"
+                  << "  percent of its neighbouring symbols different is emptied (verdict U); also with --readlen L.  On the device, behind the\n"
+                  << "  trims; FASTA or FASTQ; one line of counts per reads file.\n"
                   << "  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
@@ -234,6 +299,7 @@ int main(int argc, char **argv)
         if (cut_adapter && lime_seq_reader_set_adapter(readers[m], (const uint8_t *)adapters[m].data(), (uint32_t)adapters[m].size(), ad_overlap, ad_err) != LIME_OK) {
             std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1;
         }
+        if (filter && lime_seq_reader_set_filter(readers[m], &flt) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
     }
     for (uint32_t m = 0; m < n_mates && !batched; ++m) {
         int rc;
@@ -253,6 +319,14 @@ int main(int argc, char **argv)
             rc = lime_docs_trim_adapter_dev(ctx, whole, (const uint8_t *)adapters[m].data(), (uint32_t)adapters[m].size(), ad_overlap, ad_err, nullptr, &mates[m], &ti);
             lime_docs_free(whole);
             if (rc == LIME_OK) print_adapter(reads[m], adapters[m], ad_overlap, ad_err, ti);
+        }
+        if (rc == LIME_OK && filter) {             // what the trims left, filtered
+            lime_docs *whole = mates[m];
+            lime_filter_info_t fi;
+            mates[m] = nullptr;
+            rc = lime_docs_filter_dev(ctx, whole, &flt, nullptr, &mates[m], &fi);
+            lime_docs_free(whole);
+            if (rc == LIME_OK) print_filter(reads[m], flt, fi);
         }
         if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
     }
@@ -317,6 +391,11 @@ int main(int argc, char **argv)
             lime_trim_info_t ti;
             lime_seq_reader_adapter_info(readers[m], &ti);
             print_adapter(reads[m], adapters[m], ad_overlap, ad_err, ti);
+        }
+        for (uint32_t m = 0; m < n_mates && filter; ++m) {
+            lime_filter_info_t fi;
+            lime_seq_reader_filter_info(readers[m], &fi);
+            print_filter(reads[m], flt, fi);
         }
         clk.mark("batches: reads, collections, classification");
         if (lime_classification_writer_close(sink.w, 1) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }

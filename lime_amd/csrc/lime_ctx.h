@@ -243,6 +243,8 @@ struct __attribute__((visibility("hidden"))) lime_seq_reader {
     lime_trim_info_t trimmed = {0, 0, 0, 0, 0};            // summed over the batches handed out
     bool adapter = false; uint64_t ad_masks[4] = {0, 0, 0, 0}; uint32_t ad_m = 0, ad_overlap = 0, ad_err = 0;     // lime_seq_reader_set_adapter: every
     lime_trim_info_t ad_trimmed = {0, 0, 0, 0, 0};         // batch is cut at its reads' adapters (behind the quality trim, where both are set)
+    bool filter = false; lime_filter_t fl = {0, 0, 0, 0, LIME_FILTER_OFF, 0};      // lime_seq_reader_set_filter: every batch is filtered, behind the trims
+    lime_filter_info_t filtered = {0, 0, 0, 0, 0, 0, 0, 0};
     ~lime_seq_reader();
 };
 
@@ -316,6 +318,10 @@ int docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t
 int adapter_masks(const char *who, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct, uint64_t masks[4]);
 int docs_adapter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const uint64_t masks[4], uint32_t m, uint32_t min_overlap, uint32_t max_err_pct,
                       hipStream_t st, lime_docs **out, lime_trim_info_t *info);
+// lime_host.cpp: the filter's refusals of its parameters (LIME_ERR_ARG with a text); lime_docs.cpp: lime_docs_filter_dev without its
+// argument checks
+int filter_check(const char *who, const lime_filter_t *f);
+int docs_filter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const lime_filter_t *f, hipStream_t st, lime_docs **out, lime_filter_info_t *info);
 // lime_docs.cpp: the genome side's refusals of the sample calls, with one index or with shards (the read sets' own come between the two)
 int sample_check_shards(const char *who, lime_ctx *c, uint32_t n_shards, const lime_gindex *const *shards);
 int sample_check_rules(const char *who, uint32_t n_shards, const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha,

@@ -1,6 +1,6 @@
 // lime_docs.cpp -- document collections that stay in HBM (lime_docs: made from the raw bytes of a FASTA or FASTQ file by the kernels of
 // lime_fasta_kernel.hip / lime_fastq_kernel.hip, or copied from parsed arrays), their reverse complements, FASTQ reads with their quality strings and
-// the quality trim (lime_fqtrim_kernel.hip), the adapter trim (lime_adapter_kernel.hip), and a whole sample from documents to verdicts
+// the quality trim (lime_fqtrim_kernel.hip), the adapter trim (lime_adapter_kernel.hip), the read filter (lime_filter_kernel.hip), and a whole sample from documents to verdicts
 // (lime_classify_sample_dev: per collection the merge into the genome index, the scan and clusterChoose, then Classify over the lists).
 // include/lime_hip.h states the contract.
 #include <hip/hip_runtime.h>
@@ -372,8 +372,8 @@ extern "C" int lime_docs_get_qual(const lime_docs *d, uint8_t *qual)
 }
 
 // ---- the quality trim (lime_fqtrim_kernel.hip: k_trim_bounds, k_trim_copy) and the adapter trim (lime_adapter_kernel.hip: k_adapter_bounds) ----
-// Scratch: 12 bytes per read (lo, length, new offset) + rocPRIM's + two counters, given back before either returns.  The new lengths' total
-// sizes the handle: two synchronisations, like the parse
+// Scratch: 12 bytes per read (lo, length, new offset) + rocPRIM's + the counter cell (two counters for a trim, five for the read filter
+// further down), given back before either returns.  The new lengths' total sizes the handle: two synchronisations, like the parse
 namespace {
 struct TrimScratch : WordScratch {                       // what a bounds kernel fills and trim_finish reads
     uint32_t *lo32() const { return words(0); }
@@ -383,30 +383,31 @@ struct TrimScratch : WordScratch {                       // what a bounds kernel
 };
 }
 
-// nd >= 1 reads: the arrays, with the 0 behind the last read's length and the counters cleared
-static int trim_begin(const char *who, uint32_t nd, hipStream_t st, TrimScratch &ts)
+// nd >= 1 reads: the arrays, with the 0 behind the last read's length and the n_counts counters cleared
+static int trim_begin(const char *who, uint32_t nd, hipStream_t st, TrimScratch &ts, uint32_t n_counts = 2)
 {
     size_t tmp_bytes = 0;
     HIP_TRY(idx_scan_sum(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)nd + 1, false, st));
     int rc = ts.alloc(3, nd, tmp_bytes);
     if (rc) return fail(rc, "%s: no device memory for the trim of %u reads: %s", who, nd, lime_last_error());
     HIP_TRY(hipMemsetAsync(ts.len32() + nd, 0, 4, st));  // (the 0 behind the last read's length: the sum's last entry is the total)
-    HIP_TRY(hipMemsetAsync(ts.d_counts(), 0, 16, st));
+    HIP_TRY(hipMemsetAsync(ts.d_counts(), 0, 8 * n_counts, st));
     return LIME_OK;
 }
 
-// behind a bounds kernel's launch (none for no reads): the prefix sum, the total, the handle, the copy and the counts
-static int trim_finish(lime_ctx *c, const char *who, const lime_docs *docs, TrimScratch &ts, hipStream_t st, lime_docs **out, lime_trim_info_t *info)
+// behind a bounds kernel's launch (none for no reads): the prefix sum, the total, the handle and the copy; -> counts[0 .. n_counts) as the
+// kernel left them in the counter cell (zeros for no reads) and *symbols_out
+static int trim_finish_counts(lime_ctx *c, const char *who, const lime_docs *docs, TrimScratch &ts, hipStream_t st, lime_docs **out, uint64_t *counts,
+                              uint32_t n_counts, uint64_t *symbols_out)
 {
     const uint32_t nd = docs->n_docs;
-    lime_trim_info_t ti = {nd, 0, 0, docs->n_text, 0};
     uint32_t n_out = 0;
-    uint64_t counts[2] = {0, 0};
+    memset(counts, 0, 8 * n_counts);
     if (nd) {
         HIP_TRY(hipGetLastError());
         HIP_TRY(idx_scan_sum(ts.tmp(), &ts.tmp_bytes, ts.len32(), ts.new_off(), (size_t)nd + 1, false, st));
         HIP_TRY(hipMemcpyAsync(&n_out, ts.new_off() + nd, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(counts, ts.d_counts(), 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(counts, ts.d_counts(), 8 * n_counts, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));               // (the total sizes the handle)
     }
     DocsGuard dg;
@@ -418,9 +419,19 @@ static int trim_finish(lime_ctx *c, const char *who, const lime_docs *docs, Trim
         HIP_TRY(hipMemsetAsync(dg.d->doc_off.p, 0, 8, st));
     }
     HIP_TRY(hipStreamSynchronize(st));                   // (the scratch goes back when the caller returns)
-    ti.n_changed = counts[0]; ti.n_empty = counts[1]; ti.symbols_out = n_out;
-    if (info) *info = ti;
+    *symbols_out = n_out;
     *out = dg.take();
+    return LIME_OK;
+}
+
+// the same for the two trims, whose kernels count the reads changed and the reads emptied
+static int trim_finish(lime_ctx *c, const char *who, const lime_docs *docs, TrimScratch &ts, hipStream_t st, lime_docs **out, lime_trim_info_t *info)
+{
+    lime_trim_info_t ti = {docs->n_docs, 0, 0, docs->n_text, 0};
+    uint64_t counts[2];
+    int rc = trim_finish_counts(c, who, docs, ts, st, out, counts, 2, &ti.symbols_out); if (rc) return rc;
+    ti.n_changed = counts[0]; ti.n_empty = counts[1];
+    if (info) *info = ti;
     return LIME_OK;
 }
 
@@ -476,6 +487,36 @@ extern "C" int lime_docs_trim_adapter_dev(lime_ctx *c, const lime_docs *docs, co
     int rc = adapter_masks(who, adapter, m, min_overlap, max_err_pct, masks); if (rc) return rc;
     if ((rc = check_ctx(c, who))) return rc;
     return docs_adapter_impl(c, who, docs, masks, m, min_overlap, max_err_pct, (hipStream_t)stream, out, info);
+}
+
+// ---- the read filter (lime_filter_kernel.hip: k_filter_bounds), through the trims' prefix sum and copy ----
+int lime_host::docs_filter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const lime_filter_t *f, hipStream_t st, lime_docs **out,
+                                lime_filter_info_t *info)
+{
+    const uint32_t nd = docs->n_docs;
+    TrimScratch ts;
+    if (nd) {
+        int rc = trim_begin(who, nd, st, ts, 5); if (rc) return rc;
+        fl_launch_bounds(docs->text.p, docs->doc_off.p, nd, f, ts.lo32(), ts.len32(), ts.d_counts(), st);
+    }
+    lime_filter_info_t fi = {nd, 0, 0, 0, 0, 0, docs->n_text, 0};
+    uint64_t counts[5];
+    int rc = trim_finish_counts(c, who, docs, ts, st, out, counts, 5, &fi.symbols_out); if (rc) return rc;
+    fi.n_polyx = counts[0]; fi.n_capped = counts[1]; fi.n_short = counts[2]; fi.n_many_n = counts[3]; fi.n_low_complexity = counts[4];
+    if (info) *info = fi;
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_filter_dev(lime_ctx *c, const lime_docs *docs, const lime_filter_t *f, void *stream, lime_docs **out, lime_filter_info_t *info)
+{
+    const char *who = "lime_docs_filter_dev";
+    if (info) memset(info, 0, sizeof *info);
+    if (out) *out = nullptr;
+    if (!c || !docs || !f || !out) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (docs->ctx != c) return fail(LIME_ERR_ARG, "%s: the documents belong to another context", who);
+    int rc = filter_check(who, f); if (rc) return rc;
+    if ((rc = check_ctx(c, who))) return rc;
+    return docs_filter_impl(c, who, docs, f, (hipStream_t)stream, out, info);
 }
 
 extern "C" int lime_docs_trim_dev(lime_ctx *c, const lime_docs *docs, uint32_t q5, uint32_t q3, void *stream, lime_docs **out, lime_trim_info_t *info)

@@ -9,6 +9,7 @@
 
 namespace lime_host __attribute__((visibility("hidden"))) {
 int fail(int code, const char *fmt, ...);                 // lime_api.cpp: sets what lime_last_error() returns
+int filter_check(const char *who, const lime_filter_t *f);        // below; lime_ctx.h declares it for the device side
 }
 
 namespace {
@@ -449,6 +450,82 @@ extern "C" int lime_adapter_trim(const uint8_t *text, const uint64_t *doc_off, u
     memcpy(o, off.data(), off.size() * 8);
     *out_text = t; *out_doc_off = o;
     if (info) *info = ti;
+    return LIME_OK;
+}
+
+// ---- the read filter: the loop form of the rule (include/lime_hip.h), the oracle of lime_docs_filter_dev -------------------------
+// the refusals of the parameters, shared with lime_docs_filter_dev and lime_seq_reader_set_filter
+int lime_host::filter_check(const char *who, const lime_filter_t *f)
+{
+    if (!f) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (f->polyx_mask > 15) return fail(LIME_ERR_ARG, "%s: a poly-X mask of %u; bits 0 .. 3 are A, C, G and T", who, f->polyx_mask);
+    if (f->polyx_mask && (!f->polyx_min || f->polyx_min > 255))
+        return fail(LIME_ERR_ARG, "%s: a shortest poly-X tail of %u symbols; it is 1 .. 255", who, f->polyx_min);
+    if (f->min_complexity > 100) return fail(LIME_ERR_ARG, "%s: a complexity of %u percent; it is 0 .. 100", who, f->min_complexity);
+    if (!f->polyx_mask && !f->max_len && !f->min_len && f->max_n == LIME_FILTER_OFF && !f->min_complexity)
+        return fail(LIME_ERR_ARG, "%s: nothing asked: no poly-X base, no length cap, no shortest length, no N limit and no complexity", who);
+    return LIME_OK;
+}
+
+namespace {
+inline uint32_t class_of(uint8_t b)                       // 0 .. 3: A C G T; 4: other
+{
+    switch (b & 0xDF) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; default: return 4; }
+}
+}
+
+extern "C" int lime_read_filter(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const lime_filter_t *f, uint8_t **out_text,
+                                uint64_t **out_doc_off, lime_filter_info_t *info)
+{
+    const char *who = "lime_read_filter";
+    if (out_text) *out_text = nullptr;
+    if (out_doc_off) *out_doc_off = nullptr;
+    if (info) memset(info, 0, sizeof *info);
+    if (!doc_off || !f || !out_text || !out_doc_off) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    int rc = lime_host::filter_check(who, f); if (rc) return rc;
+    if (doc_off[0] != 0) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off does not start at 0", who);
+    for (uint32_t r = 0; r < n_docs; ++r)
+        if (doc_off[r + 1] < doc_off[r]) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off decreases at read %u", who, r);
+    if (doc_off[n_docs] && !text) return lime_host::fail(LIME_ERR_ARG, "%s: NULL array", who);
+    std::vector<uint8_t> sym;
+    std::vector<uint64_t> off;
+    off.reserve((size_t)n_docs + 1);
+    lime_filter_info_t fi = {n_docs, 0, 0, 0, 0, 0, doc_off[n_docs], 0};
+    for (uint32_t r = 0; r < n_docs; ++r) {
+        const uint64_t a = doc_off[r], L = doc_off[r + 1] - a;
+        const uint8_t *s = text + a;
+        off.push_back(sym.size());
+        if (!L) continue;                                // (counted nowhere)
+        uint64_t best = 0;                               // t*
+        for (uint32_t X = 0; X < 4; ++X) {
+            if (!(f->polyx_mask >> X & 1u)) continue;
+            uint64_t mm = 0;
+            for (uint64_t t = 1; t <= L; ++t) {
+                const bool is_x = class_of(s[L - t]) == X;
+                mm += !is_x;
+                if (is_x && t >= f->polyx_min && 8 * mm <= t && t > best) best = t;
+            }
+        }
+        uint64_t n = L - best;
+        fi.n_polyx += best != 0;
+        if (f->max_len && n > f->max_len) { n = f->max_len; ++fi.n_capped; }
+        if (n < f->min_len) { ++fi.n_short; continue; }
+        uint64_t n_other = 0, d = 0;
+        for (uint64_t j = 0; j < n; ++j) n_other += class_of(s[j]) == 4;
+        for (uint64_t j = 0; j + 1 < n; ++j) d += class_of(s[j]) != class_of(s[j + 1]);
+        if (f->max_n != LIME_FILTER_OFF && n_other > f->max_n) { ++fi.n_many_n; continue; }
+        if (n >= 2 && 100 * d < (uint64_t)f->min_complexity * (n - 1)) { ++fi.n_low_complexity; continue; }
+        sym.insert(sym.end(), s, s + n);
+    }
+    off.push_back(sym.size());
+    fi.symbols_out = sym.size();
+    uint8_t *t = static_cast<uint8_t *>(malloc(sym.size() ? sym.size() : 1));
+    uint64_t *o = static_cast<uint64_t *>(malloc(off.size() * 8));
+    if (!t || !o) { free(t); free(o); return lime_host::fail(LIME_ERR_NOMEM, "%s: out of host memory", who); }
+    if (!sym.empty()) memcpy(t, sym.data(), sym.size());
+    memcpy(o, off.data(), off.size() * 8);
+    *out_text = t; *out_doc_off = o;
+    if (info) *info = fi;
     return LIME_OK;
 }
 

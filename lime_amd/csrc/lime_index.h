@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "lime_hip.h"                                    // (lime_filter_t)
 
 namespace lime {
 
@@ -121,6 +122,13 @@ void fqt_launch_copy(const uint8_t *text, const uint64_t *doc_off, uint32_t n_do
 // 1 <= min_overlap <= m <= 64, max_err_pct <= 50
 void ad_launch_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const uint64_t masks[4], uint32_t m, uint32_t min_overlap,
                       uint32_t max_err_pct, uint32_t *lo32, uint32_t *len32, uint64_t *counts, hipStream_t st);
+
+// ---- lime_filter_kernel.hip: what the read filter keeps of every read (lime_docs.cpp) ----
+// lo32[r] = 0, len32[r] = what the rule (include/lime_hip.h: lime_read_filter) keeps of read r, in fqt_launch_bounds' conventions, so that
+// the prefix sum and fqt_launch_copy follow unchanged.  counts[0 .. 5) += the reads with a poly-X tail, the reads the cap shortened, the
+// reads emptied as short, for their N's, for their complexity.  *f as lime_read_filter accepts it
+void fl_launch_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const lime_filter_t *f, uint32_t *lo32, uint32_t *len32, uint64_t *counts,
+                      hipStream_t st);
 
 // ---- lime_seqcut_kernel.hip: where a window of a reads file is cut into whole records (lime_reader.cpp) ----
 // The same blocks; the markers and the rule are at the head of the kernel file.  cnt[k] = the line-first '>' of block k (FASTQ counts

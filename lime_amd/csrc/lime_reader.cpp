@@ -249,6 +249,17 @@ static int reader_next(lime_seq_reader *r, const char *who, uint32_t max_reads, 
             r->ad_trimmed.n_reads += ti.n_reads; r->ad_trimmed.n_changed += ti.n_changed; r->ad_trimmed.n_empty += ti.n_empty;
             r->ad_trimmed.symbols_in += ti.symbols_in; r->ad_trimmed.symbols_out += ti.symbols_out;
         }
+        if (r->filter) {                                 // third: what the trims left, filtered
+            lime_docs *t = nullptr;
+            lime_filter_info_t fi;
+            rc = docs_filter_impl(r->ctx, who, d, &r->fl, nullptr, &t, &fi);
+            lime_docs_free(d);
+            if (rc) return rc;
+            d = t;
+            lime_filter_info_t &s = r->filtered;
+            s.n_reads += fi.n_reads; s.n_polyx += fi.n_polyx; s.n_capped += fi.n_capped; s.n_short += fi.n_short; s.n_many_n += fi.n_many_n;
+            s.n_low_complexity += fi.n_low_complexity; s.symbols_in += fi.symbols_in; s.symbols_out += fi.symbols_out;
+        }
         uint32_t nd = 0;
         lime_docs_info(d, &nd, nullptr);
         if (r->n_records + nd > 0xFFFFFFFFull) {
@@ -313,6 +324,23 @@ extern "C" int lime_seq_reader_adapter_info(const lime_seq_reader *r, lime_trim_
 {
     if (!r || !info) return fail(LIME_ERR_ARG, "lime_seq_reader_adapter_info: NULL argument");
     *info = r->ad_trimmed;
+    return LIME_OK;
+}
+
+extern "C" int lime_seq_reader_set_filter(lime_seq_reader *r, const lime_filter_t *filter)
+{
+    const char *who = "lime_seq_reader_set_filter";
+    if (!r) return fail(LIME_ERR_ARG, "%s: the reader is NULL", who);
+    int rc = filter_check(who, filter); if (rc) return rc;
+    if (r->asked) return fail(LIME_ERR_ARG, "%s: the reader has handed out records already; the filter is set before the first lime_seq_reader_next", who);
+    r->filter = true; r->fl = *filter;
+    return LIME_OK;
+}
+
+extern "C" int lime_seq_reader_filter_info(const lime_seq_reader *r, lime_filter_info_t *info)
+{
+    if (!r || !info) return fail(LIME_ERR_ARG, "lime_seq_reader_filter_info: NULL argument");
+    *info = r->filtered;
     return LIME_OK;
 }
 
