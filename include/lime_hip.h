@@ -602,6 +602,33 @@ typedef struct { uint32_t polyx_mask, polyx_min, max_len, min_len, max_n, min_co
 typedef struct { uint64_t n_reads, n_polyx, n_capped, n_short, n_many_n, n_low_complexity, symbols_in, symbols_out; } lime_filter_info_t;
 int lime_read_filter(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const lime_filter_t *filter, uint8_t **out_text, uint64_t **out_doc_off,
                      lime_filter_info_t *info);
+/* The overlap cut: adapter read-through found from the two mates of a pair alone, with no adapter sequence given (what fastp does for
+ * paired data).  When the fragment (insert) is shorter than a read, both mates run through it into the adapter, and the first I symbols of
+ * mate 1 are the reverse complement of the first I symbols of mate 2.  Integers only, on the strings as given.  Mates a[0 .. La) and
+ * b[0 .. Lb) of pair r; min_overlap O >= 1 (LiME_fasta's default: 30); max_err_pct E, whole percent, 0 <= E <= 50 (default: 10).
+ *   class(byte) is A, C, G or T after folding with & 0xDF (acgt are taken as ACGT); every other byte -- N, IUPAC codes, anything -- has no
+ *   class and agrees with nothing, not even with itself.  comp swaps A / T and C / G.
+ *   For a candidate insert length I the places are the j in [max(0, I - Lb), min(La, I)); n(I) = min(La, I) - max(0, I - Lb) is their
+ *   number.  Place j agrees when a[j] has a class and class(a[j]) = comp(class(b[I - 1 - j])).  mis(I) = n(I) - the agreeing places.
+ *   I is admissible when n(I) >= O and mis(I) <= (n(I) * E) / 100 by integer division.
+ *   I* = the LARGEST admissible I in [O, La + Lb - O]: largest, not first-found and not best-scoring, so that it cuts least and a pair of
+ *   low complexity with many admissible I is decided the same way everywhere.  Without one the pair is unchanged and insert[r] = 0.
+ *   Mate 1 keeps a[0 .. min(La, I*)), mate 2 keeps b[0 .. min(Lb, I*)).  I* >= max(La, Lb) is an ordinary overlap of a long fragment: it
+ *   cuts nothing and is still reported in insert[r].
+ * Hence nothing is ever cut below O symbols and no read is emptied; an empty mate gives no overlap; read indices never change.
+ * The rule is symmetric in the mates.  It runs LAST, behind each mate's quality trim, adapter trim and filter: it is the only stage that
+ * needs both mates, and every per-mate stage makes the comparison cleaner.  So --min-len judges a read before this cut (the floor behind
+ * it is O), and a 5' quality cut (Q5) moves a read's anchor: such a pair is judged on the strings as they are and usually has no overlap.
+ * lime_overlap_info_t: n_pairs; n_overlap, the pairs with an I*; n_cut, the pairs of which a mate got shorter; the symbols of both mates
+ * before and after.
+ * lime_pair_overlap_trim is the loop form in plain host code, the oracle of lime_docs_trim_overlap_dev: two collections of n_docs reads
+ * each; the four outputs as lime_adapter_trim's; *insert (may be NULL: not wanted) = I* per pair, n_docs words (at least one),
+ * library-owned (lime_free); info may be NULL.  LIME_ERR_ARG with a text: a NULL array, min_overlap of 0, max_err_pct above 50, a doc_off
+ * that does not start at 0 or decreases. */
+typedef struct { uint64_t n_pairs, n_overlap, n_cut, symbols_in, symbols_out; } lime_overlap_info_t;
+int lime_pair_overlap_trim(const uint8_t *text1, const uint64_t *doc_off1, const uint8_t *text2, const uint64_t *doc_off2, uint32_t n_docs,
+                           uint32_t min_overlap, uint32_t max_err_pct, uint8_t **out_text1, uint64_t **out_doc_off1, uint8_t **out_text2,
+                           uint64_t **out_doc_off2, uint32_t **insert, lime_overlap_info_t *info);
 /* *format = 1 (FASTQ) if the file's first byte is '@', else 0 (FASTA: an empty file and text in front of the first header included).
  * LIME_ERR_IO when the file cannot be read.  Pure host code. */
 int lime_seq_format(const char *path, int *format);
@@ -728,6 +755,18 @@ int  lime_docs_trim_adapter_dev(lime_ctx *ctx, const lime_docs *docs, const uint
  * given back before the call returns.  LIME_ERR_ARG with a text, before any launch: a NULL argument, documents of another context, and
  * lime_read_filter's refusals of the parameters.  On every error nothing stays allocated and *out is NULL.  Synchronises `stream`. */
 int  lime_docs_filter_dev(lime_ctx *ctx, const lime_docs *docs, const lime_filter_t *filter, void *stream, lime_docs **out, lime_filter_info_t *info);
+/* The two mates' documents cut by the rule at lime_pair_overlap_trim, on the device: *out1, *out2 = new documents (the caller's; no
+ * qualities) whose texts and doc_off are byte for byte the oracle's, d_insert (device memory, n_docs words, may be NULL) its insert[],
+ * *info (may be NULL) its counts.  Any documents are taken, as for the other trims; input qualities are dropped.  k_overlap_bounds
+ * (lime_overlap_kernel.hip) finds I* of every pair -- one wave on a pair; mate 1 as four class ballots per 64 symbols, mate 2 as those of
+ * its reverse complement, read backwards in place; a lane takes one candidate I, 64 candidates a step from the largest down, the agreeing
+ * places counted as set bits of (a funnel-shifted window of one read's words) & (the other's) -- and per mate the prefix sum and
+ * k_trim_copy of lime_docs_trim_dev follow.  The cost is quadratic in the read length.  Device memory next to the four handles: 24 bytes
+ * per pair + the prefix sums', given back before the call returns.  LIME_ERR_ARG with a text, before any launch: a NULL argument, documents
+ * of another context, collections of different n_docs, min_overlap of 0, max_err_pct above 50.  On every error nothing stays allocated
+ * and *out1, *out2 are NULL.  Synchronises `stream`. */
+int  lime_docs_trim_overlap_dev(lime_ctx *ctx, const lime_docs *docs1, const lime_docs *docs2, uint32_t min_overlap, uint32_t max_err_pct,
+                                uint32_t *d_insert, void *stream, lime_docs **out1, lime_docs **out2, lime_overlap_info_t *info);
 /* lime_docs_from_fastq or lime_docs_from_fasta, by lime_seq_format(path): the one place a file's format is decided */
 int  lime_docs_from_file(lime_ctx *ctx, const char *path, lime_docs **out);
 /* documents that are parsed already (copied); doc_off is checked on the device by lime_build_index's rules: LIME_ERR_ARG */
@@ -848,6 +887,20 @@ int  lime_seq_reader_adapter_info(const lime_seq_reader *r, lime_trim_info_t *in
  * counts what the filter was given, the trims' output included. */
 int  lime_seq_reader_set_filter(lime_seq_reader *r, const lime_filter_t *filter);
 int  lime_seq_reader_filter_info(const lime_seq_reader *r, lime_filter_info_t *info);
+/* set_overlap: links two readers of one ctx, the two mates' files, so that lime_seq_reader_next_pair hands out their batches cut by the
+ * rule at lime_pair_overlap_trim.  The cut needs both mates of a batch, so it cannot sit in one reader's next: lime_seq_reader_next on a
+ * linked reader alone hands out the UNCUT batch (each mate's own stages applied).  LIME_ERR_ARG with a text: a NULL reader, one reader
+ * given twice, readers of different contexts, min_overlap of 0, max_err_pct above 50, a reader whose lime_seq_reader_next has been
+ * called, a reader that is linked already.  Closing a linked reader unlinks the other.
+ * next_pair: a batch of max_reads records from each reader, each through its own stages (quality trim, adapter trim, filter), then the
+ * pair cut LAST (lime_docs_trim_overlap_dev).  *docs1 = *docs2 = NULL with LIME_OK: the end of both files.  LIME_ERR_ARG with a text:
+ * readers that are not linked to each other, batches of different record counts (one file has ended before the other; both batches are
+ * dropped).  The batches, concatenated, are the whole files' documents cut as one pair of collections.
+ * overlap_info: the sums over the batches next_pair handed out so far, from either reader of the link (zeros without one). */
+int  lime_seq_reader_set_overlap(lime_seq_reader *r1, lime_seq_reader *r2, uint32_t min_overlap, uint32_t max_err_pct);
+int  lime_seq_reader_next_pair(lime_seq_reader *r1, lime_seq_reader *r2, uint32_t max_reads, lime_docs **docs1, lime_docs **docs2,
+                               uint64_t *first_record);
+int  lime_seq_reader_overlap_info(const lime_seq_reader *r, lime_overlap_info_t *info);
 void lime_seq_reader_close(lime_seq_reader *r);
 
 /* lime_classify_sample_dev batch by batch: per batch, batch_reads (>= 1) records from each of the n_mates readers, one unchanged
@@ -857,6 +910,8 @@ void lime_seq_reader_close(lime_seq_reader *r);
  * and max_len is that of the batch's part of a cluster; they are not the whole sample's numbers.  A cluster longer than
  * LIME_MAX_CLUSTER in the whole sample may be shorter in every batch: batching can succeed where the whole run is LIME_ERR_MAXLEN,
  * never the reverse.
+ * Two readers that lime_seq_reader_set_overlap linked to each other are read with lime_seq_reader_next_pair: every batch is cut at the
+ * mates' overlap before it is classified.  A reader linked to one that is not in the call is refused.
  * LIME_ERR_ARG before any read: lime_classify_sample_dev's argument refusals, a NULL reader or one of another context, batch_reads = 0.
  * A mate that ends before the other: LIME_ERR_ARG, "the read sets hold different numbers of reads" with both record counts (the longer
  * file is read to its end for it); no read at all: LIME_ERR_ARG.  A reader's refusal ends the call with it.  A non-zero return of the

@@ -51,6 +51,10 @@ class FilterInfo(C.Structure):               # lime_filter_info_t
                 ("n_low_complexity", C.c_uint64), ("symbols_in", C.c_uint64), ("symbols_out", C.c_uint64)]
 
 
+class OverlapInfo(C.Structure):              # lime_overlap_info_t
+    _fields_ = [("n_pairs", C.c_uint64), ("n_overlap", C.c_uint64), ("n_cut", C.c_uint64), ("symbols_in", C.c_uint64), ("symbols_out", C.c_uint64)]
+
+
 class LimeError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"lime error {code}: {msg}")
@@ -187,6 +191,11 @@ SYMBOLS = {
     "lime_docs_filter_dev": (_i, [_vp, _vp, C.POINTER(Filter), _vp, _pp, C.POINTER(FilterInfo)]),
     "lime_seq_reader_set_filter": (_i, [_vp, C.POINTER(Filter)]),
     "lime_seq_reader_filter_info": (_i, [_vp, C.POINTER(FilterInfo)]),
+    "lime_pair_overlap_trim": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _pp, _pp, _pp, _pp, _pp, C.POINTER(OverlapInfo)]),
+    "lime_docs_trim_overlap_dev": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _pp, _pp, C.POINTER(OverlapInfo)]),
+    "lime_seq_reader_set_overlap": (_i, [_vp, _vp, _u32, _u32]),
+    "lime_seq_reader_next_pair": (_i, [_vp, _vp, _u32, _pp, _pp, _pu64]),
+    "lime_seq_reader_overlap_info": (_i, [_vp, C.POINTER(OverlapInfo)]),
     "lime_docs_from_file": (_i, [_vp, C.c_char_p, _pp]),
     "lime_docs_from_arrays_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _vp, _pp]),
     "lime_docs_revcomp": (_i, [_vp, _vp, _vp, _pp]),

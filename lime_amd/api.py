@@ -515,6 +515,24 @@ class Context:
         check(self.lib.lime_docs_filter_dev(self.h, docs.h, C.byref(f), stream, C.byref(h), C.byref(fi)))
         return self._docs_of(h), _filter_info(fi)
 
+    def docs_trim_overlap(self, d1, d2, min_overlap=30, max_err_pct=10, want_insert=False, stream=None):
+        """the two mates' Docs cut at the mates' overlap: adapter read-through found with no adapter given (lime_docs_trim_overlap_dev; the rule
+        is at lime_pair_overlap_trim in include/lime_hip.h).  It is the last stage: give it what each mate's trims and filter left
+        -> (Docs, Docs, info: dict of n_pairs, n_overlap, n_cut, symbols_in, symbols_out), and with want_insert also insert: numpy uint32 per
+        pair, I* or 0"""
+        h1, h2, oi = C.c_void_p(), C.c_void_p(), _lib.OverlapInfo()
+        ins = None
+        if want_insert:
+            import torch
+            n = d1.info()[0]
+            ins = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")      # (torch's current device: the ctx's, as for docs_norms)
+        check(self.lib.lime_docs_trim_overlap_dev(self.h, d1.h, d2.h, int(min_overlap), int(max_err_pct), _ptr(ins), stream, C.byref(h1), C.byref(h2),
+                                                  C.byref(oi)))
+        out = (self._docs_of(h1), self._docs_of(h2), _overlap_info(oi))
+        if want_insert:
+            out += (ins[:n].cpu().numpy().view(np.uint32),)
+        return out
+
     def docs_from_file(self, path):
         """a FASTA or FASTQ file, by seq_format(path) -> Docs"""
         h = C.c_void_p()
@@ -631,6 +649,22 @@ class Context:
 
 def _trim_info(ti):
     return {k: int(getattr(ti, k)) for k, _ in _lib.TrimInfo._fields_}
+
+
+def _overlap_info(oi):
+    return {k: int(getattr(oi, k)) for k, _ in _lib.OverlapInfo._fields_}
+
+
+def _overlap_arg(trim_overlap):
+    """O, "O", "O,E" or (O, E) -> (O, E), as `--trim-overlap` reads them (E defaults to 10)"""
+    if isinstance(trim_overlap, bytes):
+        trim_overlap = trim_overlap.decode("latin-1")
+    if isinstance(trim_overlap, str):
+        trim_overlap = [int(x) for x in trim_overlap.split(",")]
+    v = [int(trim_overlap)] if isinstance(trim_overlap, (int, np.integer)) else [int(x) for x in trim_overlap]
+    if len(v) not in (1, 2) or v[0] < 1 or not 0 <= (v[1] if len(v) == 2 else 10) <= 50:
+        raise ValueError("trim_overlap is O or (O, E): O 1 or more, E 0 .. 50")
+    return v[0], (v[1] if len(v) == 2 else 10)
 
 
 def _filter_info(fi):
@@ -752,6 +786,26 @@ class SeqReader:
         fi = _lib.FilterInfo()
         check(self.ctx.lib.lime_seq_reader_filter_info(self.h, C.byref(fi)))
         return _filter_info(fi)
+
+    def set_overlap(self, other, min_overlap=30, max_err_pct=10):
+        """links this reader and `other`, the two mates' files, so that next_pair hands out their batches cut at the mates' overlap
+        (lime_seq_reader_set_overlap: before the first next of either).  next() on a linked reader alone hands out the UNCUT batch"""
+        check(self.ctx.lib.lime_seq_reader_set_overlap(self.h, other.h, int(min_overlap), int(max_err_pct)))
+
+    def next_pair(self, other, max_reads):
+        """the next max_reads records of this reader and of `other`, each through its own stages, then cut at the mates' overlap, last
+        (lime_seq_reader_next_pair) -> (Docs, Docs, number of the first record), or None at the end of both files"""
+        d1, d2, first = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        check(self.ctx.lib.lime_seq_reader_next_pair(self.h, other.h, int(max_reads), C.byref(d1), C.byref(d2), C.byref(first)))
+        if not d1:
+            return None
+        return self.ctx._docs_of(d1), self.ctx._docs_of(d2), int(first.value)
+
+    def overlap_info(self):
+        """the overlap cut's counts summed over the batches next_pair handed out so far -> dict as Context.docs_trim_overlap gives"""
+        oi = _lib.OverlapInfo()
+        check(self.ctx.lib.lime_seq_reader_overlap_info(self.h, C.byref(oi)))
+        return _overlap_info(oi)
 
     def trim_info(self):
         """the trim's counts summed over the batches handed out so far -> dict as Context.docs_trim gives"""
@@ -1151,6 +1205,29 @@ def adapter_trim(text, doc_off, adapter, min_overlap=3, max_err_pct=10):
     return new_text, new_off, _trim_info(ti)
 
 
+def overlap_trim(text1, doc_off1, text2, doc_off2, min_overlap=30, max_err_pct=10):
+    """the overlap cut's rule in plain host code (lime_pair_overlap_trim) -> (text1, doc_off1, text2, doc_off2, insert uint32 per pair, info dict)"""
+    lib = _lib.load()
+    t1 = np.ascontiguousarray(text1, dtype=np.uint8); o1 = np.ascontiguousarray(doc_off1, dtype=np.uint64)
+    t2 = np.ascontiguousarray(text2, dtype=np.uint8); o2 = np.ascontiguousarray(doc_off2, dtype=np.uint64)
+    if len(o1) != len(o2):
+        raise ValueError("overlap_trim: the mates hold different numbers of reads")
+    p1, q1, p2, q2, pi, oi = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), _lib.OverlapInfo()
+    check(lib.lime_pair_overlap_trim(t1.ctypes.data if len(t1) else None, o1.ctypes.data, t2.ctypes.data if len(t2) else None, o2.ctypes.data, len(o1) - 1,
+                                     int(min_overlap), int(max_err_pct), C.byref(p1), C.byref(q1), C.byref(p2), C.byref(q2), C.byref(pi), C.byref(oi)))
+    try:
+        n = len(o1) - 1
+        n1 = np.ctypeslib.as_array(C.cast(q1, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        n2 = np.ctypeslib.as_array(C.cast(q2, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        x1 = np.frombuffer(C.string_at(p1, int(n1[-1])), dtype=np.uint8).copy()
+        x2 = np.frombuffer(C.string_at(p2, int(n2[-1])), dtype=np.uint8).copy()
+        ins = np.frombuffer(C.string_at(pi, 4 * n), dtype=np.uint32).copy()
+    finally:
+        for p in (p1, q1, p2, q2, pi):
+            lib.lime_free(p)
+    return x1, n1, x2, n2, ins, _overlap_info(oi)
+
+
 def read_filter(text, doc_off, polyx=None, polyx_min=10, max_len=0, min_len=0, max_n=None, min_complexity=0):
     """the read filter's rule in plain host code (lime_read_filter; the parameters as Context.docs_filter takes them) -> (text, doc_off, info dict)"""
     lib = _lib.load()
@@ -1254,7 +1331,7 @@ def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, thread
 
 def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16, beta=0.25, rank=1, trlcp=0, ebwt=True, higher=False, binary=True,
                ctx=None, batch_reads=0, window_bytes=0, trim_qual=None, trim_adapter=None,
-               adapter_overlap=3, adapter_error=10, trim_polyx=None, max_len=0, min_len=0, max_n=None, min_complexity=0):
+               adapter_overlap=3, adapter_error=10, trim_polyx=None, max_len=0, min_len=0, max_n=None, min_complexity=0, trim_overlap=None):
     """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen (L | auto) --out output
     [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta (read_len="auto": every read by its own length): the files are parsed on the device (each reads file
     FASTA or four-line FASTQ, by its first byte; refs FASTA), the
@@ -1268,6 +1345,8 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     trim_polyx, max_len, min_len, max_n, min_complexity: `--trim-polyx BASES[,T]` ("G", "GA,12" or (BASES, T)), `--max-len`, `--min-len`,
     `--max-n`, `--min-complexity`: the read filter (Context.docs_filter), behind both trims, each mate on its own.  trim_polyx and max_len
     change lengths and need read_len="auto"; the other three only empty reads and are taken with a fixed read_len too.
+    trim_overlap: `--trim-overlap O[,E]`, O or (O, E): adapter read-through cut from the two mates' overlap, with no adapter given
+    (Context.docs_trim_overlap), last, behind each mate's trims and filter; it needs two reads files and read_len="auto".
     -> counts {C, U, A, H}"""
     reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
     if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
@@ -1293,6 +1372,10 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
         if not 0 <= int(min_complexity) <= 100 or int(max_len) < 0 or int(min_len) < 0 or (max_n is not None and int(max_n) < 0):
             raise ValueError("LiME_fasta: min_complexity is 0 .. 100 percent; max_len, min_len and max_n are not negative")
         flt = dict(polyx=px, polyx_min=px_min, max_len=max_len, min_len=min_len, max_n=max_n, min_complexity=min_complexity)
+    if trim_overlap is not None:
+        ov = _overlap_arg(trim_overlap)
+        if read_len != "auto" or len(reads) != 2:
+            raise ValueError("LiME_fasta: trim_overlap needs two reads files and read_len=\"auto\": a fixed norm does not fit trimmed reads")
     norm = NORM_PER_READ if read_len == "auto" else ((int(read_len) & 0xFF) + 1 - int(alpha)) & 0xFFFFFFFF     # (`--readlen auto`)
     own = ctx is None
     ctx = ctx or Context()
@@ -1324,6 +1407,14 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
                     m.set_filter(**flt)
                 else:
                     mates[k] = ctx.docs_filter(m, **flt)[0]
+                    m.close()
+        if trim_overlap is not None:                                # last: the one stage that needs both mates
+            if batch_reads:
+                mates[0].set_overlap(mates[1], *ov)
+            else:
+                whole = mates
+                mates = list(ctx.docs_trim_overlap(whole[0], whole[1], *ov)[:2])
+                for m in whole:
                     m.close()
         if refs is not None:
             g = ctx.docs_from_fasta(refs)

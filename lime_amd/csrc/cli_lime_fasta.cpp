@@ -2,7 +2,7 @@
 //   LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen L --out output
 //              [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]
 //              [--trim-adapter SEQ[,SEQ2] [--adapter-overlap O] [--adapter-error E]]
-//              [--trim-polyx BASES[,T]] [--max-len K] [--min-len M] [--max-n K] [--min-complexity C]
+//              [--trim-polyx BASES[,T]] [--max-len K] [--min-len M] [--max-n K] [--min-complexity C] [--trim-overlap O[,E]]
 // Each reads file is FASTA or four-line FASTQ, decided by its first byte ('@': FASTQ; lime_docs_from_file), the mates each on their own;
 // --refs is FASTA.  The files' bytes go to the device as they are and are parsed there; per collection (reads_1, its reverse
 // complements, reads_2, its reverse complements: the script's `seqtk seq -r`) the reads are merged into the genome index, scanned and
@@ -42,6 +42,14 @@
 // stays in its place as an empty read (verdict U).  --trim-polyx and --max-len change lengths and need --readlen auto, for --trim-qual's
 // reason; the other three only empty reads and are taken with a fixed --readlen L too.  Each mate on its own, the reverse complements from
 // the filtered reads, one line of counts per reads file.
+// --trim-overlap O[,E]: adapter read-through cut from the two mates' overlap, with no adapter sequence given, by the rule at
+// lime_pair_overlap_trim in include/lime_hip.h, on the device: the largest insert length I at which the first I symbols of one mate are the
+// reverse complement of the first I symbols of the other, over at least O places (default 30) with at most E percent of them wrong (0 .. 50,
+// default 10); both mates keep their first I symbols.  It needs two reads files and --readlen auto (for --trim-qual's reason); FASTA or
+// FASTQ.  It runs LAST, behind each mate's quality trim, adapter trim and filter: it is the only stage that needs both mates.  So --min-len
+// judges a read before this cut (the floor behind it is O), and a 5' quality cut (--trim-qual Q5,Q3) moves a read's anchor: such a pair is
+// judged on the strings as they are and usually has no overlap.  The reverse complements are made from the cut reads.  One line of counts
+// for the pair: the pairs with an overlap, the pairs cut, the symbols before and after.
 // The defaults are the script's constants (LiME_paired.sh:21-23); norm = readLen + 1 - alpha (ClusterBWT_DA.cpp:555).  The reference's
 // compile-time switches are environment variables, as for the other drop-ins: LIME_EBWT (default 1), LIME_BIN (default 1), LIME_HIGHER (0).
 #include <string.h>
@@ -132,6 +140,22 @@ static void print_filter(const char *file, const lime_filter_t &f, const lime_fi
               << " after." << std::endl;
 }
 
+// "O" or "O,E": O >= 1, E 0 .. 50 (default 10)
+static bool parse_overlap(const char *s, unsigned *o, unsigned *e)
+{
+    const char *comma = strchr(s, ',');
+    const std::string first = comma ? std::string(s, comma) : std::string(s);
+    if (!parse_u32(first.c_str(), o) || !*o) return false;
+    if (comma && (!parse_u32(comma + 1, e) || *e > 50)) return false;
+    return true;
+}
+
+static void print_overlap(const char *file1, const char *file2, unsigned overlap, unsigned err, const lime_overlap_info_t &t)
+{
+    std::cout << file1 << " + " << file2 << ": overlap trim (overlap " << overlap << ", error " << err << "%): " << t.n_overlap << " of " << t.n_pairs
+              << " pairs with an overlap, " << t.n_cut << " cut, " << t.symbols_in << " symbols before, " << t.symbols_out << " after." << std::endl;
+}
+
 static int env_flag(const char *name, int dflt)
 {
     const char *s = getenv(name);
@@ -176,6 +200,8 @@ int main(int argc, char **argv)
     bool have_ad_opt = false;
     lime_filter_t flt = {0, 0, 0, 0, LIME_FILTER_OFF, 0};      // --trim-polyx, --max-len, --min-len, --max-n, --min-complexity
     bool filter = false;
+    unsigned ov_overlap = 30, ov_err = 10;     // --trim-overlap
+    bool cut_overlap = false;
     unsigned long long window_bytes = 0;
     bool batched = false, have_window = false;
     float beta = 0.25f;
@@ -208,6 +234,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--min-complexity")) {
             if (more && parse_u32(argv[i + 1], &flt.min_complexity) && flt.min_complexity && flt.min_complexity <= 100) { ++i; filter = true; } else bad = true;
         }
+        else if (!strcmp(argv[i], "--trim-overlap")) { if (more && parse_overlap(argv[i + 1], &ov_overlap, &ov_err)) { ++i; cut_overlap = true; } else bad = true; }
         else if (!strcmp(argv[i], "--window-bytes")) { if (more && sscanf(argv[i + 1], "%llu", &window_bytes) == 1 && window_bytes) { ++i; have_window = true; } else bad = true; }
         else reads.push_back(argv[i]);
     }
@@ -217,6 +244,7 @@ int main(int argc, char **argv)
     if (cut_adapter && !len_auto) bad = true;      // (the same)
     if (have_ad_opt && !cut_adapter) bad = true;
     if ((flt.polyx_mask || flt.max_len) && !len_auto) bad = true;          // (the same; the three filters only empty reads)
+    if (cut_overlap && (!len_auto || reads.size() != 2)) bad = true;       // (the same; and a pair is two files)
     if (n_adapters == 2 && reads.size() != 2) bad = true;
     for (int k = 0; k < n_adapters; ++k) if (ad_overlap > adapters[k].size()) bad = true;
     if (n_adapters == 1) adapters[1] = adapters[0];
@@ -225,7 +253,7 @@ int main(int argc, char **argv)
         std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx [--gidx next.gidx ...]) --lineage LineageFile --readlen (L | auto) --out output\n"
                   << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]\n"
                   << "           [--trim-adapter SEQ[,SEQ2] [--adapter-overlap 3] [--adapter-error 10]]\n"
-                  << "           [--trim-polyx BASES[,10]] [--max-len K] [--min-len M] [--max-n K] [--min-complexity C]\n"
+                  << "           [--trim-polyx BASES[,10]] [--max-len K] [--min-len M] [--max-n K] [--min-complexity C] [--trim-overlap O[,E]]\n"
                   << "  classifies the reads of one sample (one file: single-end, two: paired-end) against the genomes of refs.fasta, or of an\n"
                   << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  A reads file is FASTA or\n"
                   << "  four-line FASTQ, by its first byte ('@': FASTQ), each mate on its own; refs.fasta is FASTA.  --trlcp k: lcp values\n"
@@ -250,6 +278,11 @@ int main(int argc, char **argv)
                   << "  --min-complexity C (1 .. 100): a read of fewer than M symbols, with more than K symbols that are no base, or with fewer than C\n"
                   << "  percent of its neighbouring symbols different is emptied (verdict U); also with --readlen L.  On the device, behind the\n"
                   << "  trims; FASTA or FASTQ; one line of counts per reads file.\n"
+                  << "  --trim-overlap O[,E]: adapter read-through cut from the mates' overlap, no adapter given: the largest insert length I at which\n"
+                  << "  the first I symbols of one mate are the reverse complement of the other's, over at least O places (30) with at most E percent\n"
+                  << "  of them wrong (0 .. 50, default 10); both mates keep I symbols.  Two reads files and --readlen auto; FASTA or FASTQ.  It runs\n"
+                  << "  last, behind each mate's trims and filter: --min-len judges a read before this cut (the floor behind it is O), and a 5'\n"
+                  << "  quality cut moves a read's anchor, so such a pair usually has no overlap.  One line of counts for the pair.\n"
                   << "  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
@@ -301,6 +334,9 @@ int main(int argc, char **argv)
         }
         if (filter && lime_seq_reader_set_filter(readers[m], &flt) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
     }
+    if (batched && cut_overlap && lime_seq_reader_set_overlap(readers[0], readers[1], ov_overlap, ov_err) != LIME_OK) {
+        std::cerr << "Error reading " << reads[0] << ": " << lime_last_error() << std::endl; return 1;
+    }
     for (uint32_t m = 0; m < n_mates && !batched; ++m) {
         int rc;
         if (trim) {                                // the raw reads with their qualities, then the trimmed reads alone
@@ -329,6 +365,15 @@ int main(int argc, char **argv)
             if (rc == LIME_OK) print_filter(reads[m], flt, fi);
         }
         if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
+    }
+    if (!batched && cut_overlap) {                 // last: what each mate's stages left, cut at the mates' overlap
+        lime_docs *whole[2] = {mates[0], mates[1]};
+        lime_overlap_info_t oi;
+        mates[0] = mates[1] = nullptr;
+        const int rc = lime_docs_trim_overlap_dev(ctx, whole[0], whole[1], ov_overlap, ov_err, nullptr, nullptr, &mates[0], &mates[1], &oi);
+        lime_docs_free(whole[0]); lime_docs_free(whole[1]);
+        if (rc != LIME_OK) { std::cerr << "Error reading " << reads[0] << ": " << lime_last_error() << std::endl; return 1; }
+        print_overlap(reads[0], reads[1], ov_overlap, ov_err, oi);
     }
     if (!batched) { uint32_t nd = 0; lime_docs_info(mates[0], &nd, nullptr); numReads = nd; }
     clk.mark(batched ? "readers" : "reads (parsed on the device)");
@@ -396,6 +441,11 @@ int main(int argc, char **argv)
             lime_filter_info_t fi;
             lime_seq_reader_filter_info(readers[m], &fi);
             print_filter(reads[m], flt, fi);
+        }
+        if (cut_overlap) {
+            lime_overlap_info_t oi;
+            lime_seq_reader_overlap_info(readers[0], &oi);
+            print_overlap(reads[0], reads[1], ov_overlap, ov_err, oi);
         }
         clk.mark("batches: reads, collections, classification");
         if (lime_classification_writer_close(sink.w, 1) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }

@@ -245,6 +245,8 @@ struct __attribute__((visibility("hidden"))) lime_seq_reader {
     lime_trim_info_t ad_trimmed = {0, 0, 0, 0, 0};         // batch is cut at its reads' adapters (behind the quality trim, where both are set)
     bool filter = false; lime_filter_t fl = {0, 0, 0, 0, LIME_FILTER_OFF, 0};      // lime_seq_reader_set_filter: every batch is filtered, behind the trims
     lime_filter_info_t filtered = {0, 0, 0, 0, 0, 0, 0, 0};
+    lime_seq_reader *mate = nullptr; uint32_t ov_overlap = 0, ov_err = 0;       // lime_seq_reader_set_overlap: the other mate's reader; next_pair cuts
+    lime_overlap_info_t overlapped = {0, 0, 0, 0, 0};      // every batch of the two at the mates' overlap, last (the sums: kept in both readers)
     ~lime_seq_reader();
 };
 
@@ -322,6 +324,11 @@ int docs_adapter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const
 // argument checks
 int filter_check(const char *who, const lime_filter_t *f);
 int docs_filter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const lime_filter_t *f, hipStream_t st, lime_docs **out, lime_filter_info_t *info);
+// lime_host.cpp: the overlap cut's refusals of its parameters (LIME_ERR_ARG with a text); lime_docs.cpp: lime_docs_trim_overlap_dev without
+// its argument checks
+int overlap_check(const char *who, uint32_t min_overlap, uint32_t max_err_pct);
+int docs_overlap_impl(lime_ctx *c, const char *who, const lime_docs *docs1, const lime_docs *docs2, uint32_t min_overlap, uint32_t max_err_pct,
+                      uint32_t *d_insert, hipStream_t st, lime_docs **out1, lime_docs **out2, lime_overlap_info_t *info);
 // lime_docs.cpp: the genome side's refusals of the sample calls, with one index or with shards (the read sets' own come between the two)
 int sample_check_shards(const char *who, lime_ctx *c, uint32_t n_shards, const lime_gindex *const *shards);
 int sample_check_rules(const char *who, uint32_t n_shards, const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha,

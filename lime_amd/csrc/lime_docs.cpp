@@ -1,6 +1,6 @@
 // lime_docs.cpp -- document collections that stay in HBM (lime_docs: made from the raw bytes of a FASTA or FASTQ file by the kernels of
 // lime_fasta_kernel.hip / lime_fastq_kernel.hip, or copied from parsed arrays), their reverse complements, FASTQ reads with their quality strings and
-// the quality trim (lime_fqtrim_kernel.hip), the adapter trim (lime_adapter_kernel.hip), the read filter (lime_filter_kernel.hip), and a whole sample from documents to verdicts
+// the quality trim (lime_fqtrim_kernel.hip), the adapter trim (lime_adapter_kernel.hip), the read filter (lime_filter_kernel.hip), the overlap cut (lime_overlap_kernel.hip), and a whole sample from documents to verdicts
 // (lime_classify_sample_dev: per collection the merge into the genome index, the scan and clusterChoose, then Classify over the lists).
 // include/lime_hip.h states the contract.
 #include <hip/hip_runtime.h>
@@ -517,6 +517,47 @@ extern "C" int lime_docs_filter_dev(lime_ctx *c, const lime_docs *docs, const li
     int rc = filter_check(who, f); if (rc) return rc;
     if ((rc = check_ctx(c, who))) return rc;
     return docs_filter_impl(c, who, docs, f, (hipStream_t)stream, out, info);
+}
+
+// ---- the overlap cut (lime_overlap_kernel.hip: k_overlap_bounds): one kernel over the pairs, then per mate the trims' prefix sum and copy ----
+// The two counters stand in mate 1's cell; mate 2's cell stays as trim_begin cleared it
+int lime_host::docs_overlap_impl(lime_ctx *c, const char *who, const lime_docs *docs1, const lime_docs *docs2, uint32_t min_overlap, uint32_t max_err_pct,
+                                 uint32_t *d_insert, hipStream_t st, lime_docs **out1, lime_docs **out2, lime_overlap_info_t *info)
+{
+    const uint32_t nd = docs1->n_docs;
+    TrimScratch ts1, ts2;
+    if (nd) {
+        int rc = trim_begin(who, nd, st, ts1); if (rc) return rc;
+        if ((rc = trim_begin(who, nd, st, ts2))) return rc;
+        ov_launch_bounds(docs1->text.p, docs1->doc_off.p, docs2->text.p, docs2->doc_off.p, nd, min_overlap, max_err_pct, ts1.lo32(), ts1.len32(), ts2.lo32(),
+                         ts2.len32(), d_insert, ts1.d_counts(), st);
+    }
+    lime_overlap_info_t oi = {nd, 0, 0, docs1->n_text + docs2->n_text, 0};
+    uint64_t counts[2], none[2], sym1 = 0, sym2 = 0;
+    DocsGuard g1;
+    int rc = trim_finish_counts(c, who, docs1, ts1, st, &g1.d, counts, 2, &sym1); if (rc) return rc;
+    lime_docs *o2 = nullptr;
+    if ((rc = trim_finish_counts(c, who, docs2, ts2, st, &o2, none, 2, &sym2))) return rc;       // (g1 gives mate 1's documents back)
+    oi.n_overlap = counts[0]; oi.n_cut = counts[1]; oi.symbols_out = sym1 + sym2;
+    *out1 = g1.take(); *out2 = o2;
+    if (info) *info = oi;
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_trim_overlap_dev(lime_ctx *c, const lime_docs *docs1, const lime_docs *docs2, uint32_t min_overlap, uint32_t max_err_pct,
+                                          uint32_t *d_insert, void *stream, lime_docs **out1, lime_docs **out2, lime_overlap_info_t *info)
+{
+    const char *who = "lime_docs_trim_overlap_dev";
+    if (info) memset(info, 0, sizeof *info);
+    if (out1) *out1 = nullptr;
+    if (out2) *out2 = nullptr;
+    if (!c || !docs1 || !docs2 || !out1 || !out2) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (docs1->ctx != c || docs2->ctx != c) return fail(LIME_ERR_ARG, "%s: the documents belong to another context", who);
+    if (docs1->n_docs != docs2->n_docs)
+        return fail(LIME_ERR_ARG, "%s: the mates hold different numbers of reads (%u and %u)", who, docs1->n_docs, docs2->n_docs);
+    int rc = overlap_check(who, min_overlap, max_err_pct); if (rc) return rc;
+    if ((rc = check_ctx(c, who))) return rc;
+    return docs_overlap_impl(c, who, docs1, docs2, min_overlap, max_err_pct, d_insert, (hipStream_t)stream, out1, out2, info);
 }
 
 extern "C" int lime_docs_trim_dev(lime_ctx *c, const lime_docs *docs, uint32_t q5, uint32_t q3, void *stream, lime_docs **out, lime_trim_info_t *info)

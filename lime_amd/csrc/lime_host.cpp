@@ -10,6 +10,7 @@
 namespace lime_host __attribute__((visibility("hidden"))) {
 int fail(int code, const char *fmt, ...);                 // lime_api.cpp: sets what lime_last_error() returns
 int filter_check(const char *who, const lime_filter_t *f);        // below; lime_ctx.h declares it for the device side
+int overlap_check(const char *who, uint32_t min_overlap, uint32_t max_err_pct);       // the same
 }
 
 namespace {
@@ -526,6 +527,94 @@ extern "C" int lime_read_filter(const uint8_t *text, const uint64_t *doc_off, ui
     memcpy(o, off.data(), off.size() * 8);
     *out_text = t; *out_doc_off = o;
     if (info) *info = fi;
+    return LIME_OK;
+}
+
+// ---- the overlap cut: the loop form of the rule (include/lime_hip.h), the oracle of lime_docs_trim_overlap_dev -------------------
+int lime_host::overlap_check(const char *who, uint32_t min_overlap, uint32_t max_err_pct)
+{
+    if (!min_overlap) return fail(LIME_ERR_ARG, "%s: a minimum overlap of 0; it is 1 or more", who);
+    if (max_err_pct > 50) return fail(LIME_ERR_ARG, "%s: an error rate of %u percent; it is 0 .. 50", who, max_err_pct);
+    return LIME_OK;
+}
+
+namespace {
+// I* of the mates a[0 .. La), b[0 .. Lb): the largest admissible I in [O, La + Lb - O], 0 without one
+uint64_t overlap_insert(const uint8_t *a, uint64_t La, const uint8_t *b, uint64_t Lb, uint64_t O, uint64_t E)
+{
+    if (La + Lb < 2 * O) return 0;
+    for (uint64_t I = La + Lb - O; I >= O; --I) {
+        const uint64_t j0 = I > Lb ? I - Lb : 0, j1 = La < I ? La : I;
+        if (j1 < j0 + O) continue;                       // n(I) < O (an empty or a short mate)
+        const uint64_t n = j1 - j0;
+        uint64_t same = 0;
+        for (uint64_t j = j0; j < j1; ++j) {
+            const uint32_t ca = class_of(a[j]), cb = class_of(b[I - 1 - j]);
+            same += ca < 4 && cb == 3 - ca;              // (A C G T are 0 1 2 3: the complement is 3 - class)
+        }
+        if (n - same <= (n * E) / 100) return I;
+    }
+    return 0;
+}
+
+template <class T> T *to_malloc(const std::vector<T> &v)         // the vector's copy in a block of at least one byte, NULL without memory
+{
+    T *p = static_cast<T *>(malloc(v.empty() ? 1 : v.size() * sizeof(T)));
+    if (p && !v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
+    return p;
+}
+}
+
+extern "C" int lime_pair_overlap_trim(const uint8_t *text1, const uint64_t *doc_off1, const uint8_t *text2, const uint64_t *doc_off2, uint32_t n_docs,
+                                      uint32_t min_overlap, uint32_t max_err_pct, uint8_t **out_text1, uint64_t **out_doc_off1, uint8_t **out_text2,
+                                      uint64_t **out_doc_off2, uint32_t **insert, lime_overlap_info_t *info)
+{
+    const char *who = "lime_pair_overlap_trim";
+    if (out_text1) *out_text1 = nullptr;
+    if (out_doc_off1) *out_doc_off1 = nullptr;
+    if (out_text2) *out_text2 = nullptr;
+    if (out_doc_off2) *out_doc_off2 = nullptr;
+    if (insert) *insert = nullptr;
+    if (info) memset(info, 0, sizeof *info);
+    if (!doc_off1 || !doc_off2 || !out_text1 || !out_doc_off1 || !out_text2 || !out_doc_off2) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    int rc = lime_host::overlap_check(who, min_overlap, max_err_pct); if (rc) return rc;
+    const uint8_t *text[2] = {text1, text2};
+    const uint64_t *doc_off[2] = {doc_off1, doc_off2};
+    for (int m = 0; m < 2; ++m) {
+        if (doc_off[m][0] != 0) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off of mate %d does not start at 0", who, m + 1);
+        for (uint32_t r = 0; r < n_docs; ++r)
+            if (doc_off[m][r + 1] < doc_off[m][r]) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off of mate %d decreases at read %u", who, m + 1, r);
+        if (doc_off[m][n_docs] && !text[m]) return lime_host::fail(LIME_ERR_ARG, "%s: NULL array", who);
+    }
+    std::vector<uint8_t> sym[2];
+    std::vector<uint64_t> off[2];
+    std::vector<uint32_t> ins;
+    off[0].reserve((size_t)n_docs + 1); off[1].reserve((size_t)n_docs + 1); ins.reserve(n_docs);
+    lime_overlap_info_t oi = {n_docs, 0, 0, doc_off1[n_docs] + doc_off2[n_docs], 0};
+    for (uint32_t r = 0; r < n_docs; ++r) {
+        const uint64_t La = doc_off1[r + 1] - doc_off1[r], Lb = doc_off2[r + 1] - doc_off2[r];
+        const uint8_t *a = text1 + doc_off1[r], *b = text2 + doc_off2[r];
+        const uint64_t I = overlap_insert(a, La, b, Lb, min_overlap, max_err_pct);
+        const uint64_t ka = I && I < La ? I : La, kb = I && I < Lb ? I : Lb;
+        off[0].push_back(sym[0].size()); off[1].push_back(sym[1].size());
+        if (ka) sym[0].insert(sym[0].end(), a, a + ka);
+        if (kb) sym[1].insert(sym[1].end(), b, b + kb);
+        ins.push_back((uint32_t)I);
+        oi.n_overlap += I != 0;
+        oi.n_cut += ka != La || kb != Lb;
+    }
+    off[0].push_back(sym[0].size()); off[1].push_back(sym[1].size());
+    oi.symbols_out = sym[0].size() + sym[1].size();
+    uint8_t *t1 = to_malloc(sym[0]), *t2 = to_malloc(sym[1]);
+    uint64_t *o1 = to_malloc(off[0]), *o2 = to_malloc(off[1]);
+    uint32_t *in = insert ? to_malloc(ins) : nullptr;
+    if (!t1 || !t2 || !o1 || !o2 || (insert && !in)) {
+        free(t1); free(t2); free(o1); free(o2); free(in);
+        return lime_host::fail(LIME_ERR_NOMEM, "%s: out of host memory", who);
+    }
+    *out_text1 = t1; *out_doc_off1 = o1; *out_text2 = t2; *out_doc_off2 = o2;
+    if (insert) *insert = in;
+    if (info) *info = oi;
     return LIME_OK;
 }
 

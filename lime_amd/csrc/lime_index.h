@@ -130,6 +130,14 @@ void ad_launch_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_d
 void fl_launch_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const lime_filter_t *f, uint32_t *lo32, uint32_t *len32, uint64_t *counts,
                       hipStream_t st);
 
+// ---- lime_overlap_kernel.hip: where the two mates of a pair run into the adapter, from their overlap alone (lime_docs.cpp) ----
+// With I* of pair r by the rule (include/lime_hip.h: lime_pair_overlap_trim): lo1[r] = lo2[r] = 0, len1[r] = min(La, I*), len2[r] =
+// min(Lb, I*) (La, Lb without an I*), in fqt_launch_bounds' conventions, so that per mate the prefix sum and fqt_launch_copy follow
+// unchanged; insert32[r] = I* or 0 (insert32 may be NULL).  counts[0] += the pairs with an I*, counts[1] += the pairs of which a mate got
+// shorter.  min_overlap >= 1, max_err_pct <= 50
+void ov_launch_bounds(const uint8_t *text1, const uint64_t *doc_off1, const uint8_t *text2, const uint64_t *doc_off2, uint32_t n_docs, uint32_t min_overlap,
+                      uint32_t max_err_pct, uint32_t *lo1, uint32_t *len1, uint32_t *lo2, uint32_t *len2, uint32_t *insert32, uint64_t *counts, hipStream_t st);
+
 // ---- lime_seqcut_kernel.hip: where a window of a reads file is cut into whole records (lime_reader.cpp) ----
 // The same blocks; the markers and the rule are at the head of the kernel file.  cnt[k] = the line-first '>' of block k (FASTQ counts
 // its markers with fq_launch_lines)

@@ -73,6 +73,7 @@ lime_seq_reader::~lime_seq_reader()
 {
     for (int k = 0; k < 2; ++k) { if (ev[k]) (void)hipEventDestroy(ev[k]); if (pin[k]) (void)hipHostFree(pin[k]); }
     if (f) fclose(f);
+    if (mate) mate->mate = nullptr;                      // (lime_seq_reader_set_overlap: the other reader stays, unlinked)
 }
 
 static void reader_release(lime_seq_reader *r)
@@ -344,6 +345,71 @@ extern "C" int lime_seq_reader_filter_info(const lime_seq_reader *r, lime_filter
     return LIME_OK;
 }
 
+// ---- the overlap cut over two readers' batches (lime_docs_trim_overlap_dev): the one stage that needs both mates ----
+extern "C" int lime_seq_reader_set_overlap(lime_seq_reader *r1, lime_seq_reader *r2, uint32_t min_overlap, uint32_t max_err_pct)
+{
+    const char *who = "lime_seq_reader_set_overlap";
+    if (!r1 || !r2) return fail(LIME_ERR_ARG, "%s: a reader is NULL", who);
+    if (r1 == r2) return fail(LIME_ERR_ARG, "%s: the two mates are one reader", who);
+    if (r1->ctx != r2->ctx) return fail(LIME_ERR_ARG, "%s: the readers belong to different contexts", who);
+    int rc = overlap_check(who, min_overlap, max_err_pct); if (rc) return rc;
+    if (r1->asked || r2->asked)
+        return fail(LIME_ERR_ARG, "%s: a reader has handed out records already; the overlap is set before the first lime_seq_reader_next of either", who);
+    if (r1->mate || r2->mate) return fail(LIME_ERR_ARG, "%s: a reader is linked already", who);
+    r1->mate = r2; r2->mate = r1;
+    r1->ov_overlap = r2->ov_overlap = min_overlap; r1->ov_err = r2->ov_err = max_err_pct;
+    return LIME_OK;
+}
+
+// a batch from each of two linked readers, cut at the mates' overlap.  *uneven: the batches hold different numbers of records (one file has
+// ended before the other); both are dropped, LIME_OK, and the caller words the refusal
+static int next_pair_impl(const char *who, lime_seq_reader *r1, lime_seq_reader *r2, uint32_t max_reads, lime_docs **docs1, lime_docs **docs2,
+                          uint64_t *first_record, bool *uneven, uint32_t got[2])
+{
+    *uneven = false;
+    got[0] = got[1] = 0;
+    DocsPair batch;
+    uint64_t first = 0;
+    int rc;
+    if ((rc = lime_seq_reader_next(r1, max_reads, &batch.d[0], &first))) return rc;
+    if ((rc = lime_seq_reader_next(r2, max_reads, &batch.d[1], nullptr))) return rc;
+    for (int m = 0; m < 2; ++m) if (batch.d[m]) lime_docs_info(batch.d[m], &got[m], nullptr);
+    if (got[0] != got[1]) { *uneven = true; return LIME_OK; }
+    if (!got[0]) return LIME_OK;                         // the end of both files
+    lime_overlap_info_t oi;
+    if ((rc = docs_overlap_impl(r1->ctx, who, batch.d[0], batch.d[1], r1->ov_overlap, r1->ov_err, nullptr, nullptr, docs1, docs2, &oi))) return rc;
+    lime_overlap_info_t &s = r1->overlapped;
+    s.n_pairs += oi.n_pairs; s.n_overlap += oi.n_overlap; s.n_cut += oi.n_cut; s.symbols_in += oi.symbols_in; s.symbols_out += oi.symbols_out;
+    r2->overlapped = s;
+    if (first_record) *first_record = first;
+    return LIME_OK;
+}
+
+extern "C" int lime_seq_reader_next_pair(lime_seq_reader *r1, lime_seq_reader *r2, uint32_t max_reads, lime_docs **docs1, lime_docs **docs2,
+                                         uint64_t *first_record)
+{
+    const char *who = "lime_seq_reader_next_pair";
+    if (docs1) *docs1 = nullptr;
+    if (docs2) *docs2 = nullptr;
+    if (!r1 || !r2 || !docs1 || !docs2) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (r1 == r2 || r1->mate != r2 || r2->mate != r1)
+        return fail(LIME_ERR_ARG, "%s: the readers are not linked to each other (lime_seq_reader_set_overlap)", who);
+    if (!max_reads) return fail(LIME_ERR_ARG, "%s: max_reads is 0", who);
+    bool uneven = false;
+    uint32_t got[2];
+    int rc = next_pair_impl(who, r1, r2, max_reads, docs1, docs2, first_record, &uneven, got); if (rc) return rc;
+    if (uneven)
+        return fail(LIME_ERR_ARG, "%s: the read sets hold different numbers of reads (a batch of %u records in set 0, of %u in set 1)", who, got[0], got[1]);
+    return LIME_OK;
+}
+
+extern "C" int lime_seq_reader_overlap_info(const lime_seq_reader *r, lime_overlap_info_t *info)
+{
+    if (!r || !info) return fail(LIME_ERR_ARG, "lime_seq_reader_overlap_info: NULL argument");
+    *info = r->overlapped;
+    return LIME_OK;
+}
+
 extern "C" int lime_seq_reader_info(const lime_seq_reader *r, int *format, uint64_t *n_records, uint64_t *n_lines, uint64_t *n_bytes, uint64_t *window_bytes)
 {
     if (!r) return fail(LIME_ERR_ARG, "lime_seq_reader_info: the reader is NULL");
@@ -400,6 +466,10 @@ static int sample_stream_impl(const char *who, lime_ctx *c, uint32_t n_mates, li
         if (readers[m]->ctx != c) return fail(LIME_ERR_ARG, "%s: reader %u belongs to another context", who, m);
     }
     if (n_mates == 2 && readers[0] == readers[1]) return fail(LIME_ERR_ARG, "%s: the two read sets are one reader", who);
+    for (uint32_t m = 0; m < n_mates; ++m)
+        if (readers[m]->mate && (n_mates != 2 || readers[m]->mate != readers[1 - m]))
+            return fail(LIME_ERR_ARG, "%s: reader %u is linked to a reader that is not in the call (lime_seq_reader_set_overlap)", who, m);
+    const bool linked = n_mates == 2 && readers[0]->mate == readers[1];       // the batches are cut at the mates' overlap
     uint32_t n_refs = 0, cap = 0;
     if ((rc = sample_check_rules(who, n_shards, shards, tx, alpha, lcp_cap, &n_refs, &cap))) return rc;
     if (!batch_reads) return fail(LIME_ERR_ARG, "%s: batch_reads is 0", who);
@@ -411,11 +481,17 @@ static int sample_stream_impl(const char *who, lime_ctx *c, uint32_t n_mates, li
     for (;;) {
         DocsPair batch;
         uint32_t got[2] = {0, 0};
-        for (uint32_t m = 0; m < n_mates; ++m) {
-            if ((rc = lime_seq_reader_next(readers[m], batch_reads, &batch.d[m], nullptr))) return rc;
-            if (batch.d[m]) lime_docs_info(batch.d[m], &got[m], nullptr);
+        bool uneven = false;
+        if (linked) {
+            if ((rc = next_pair_impl(who, readers[0], readers[1], batch_reads, &batch.d[0], &batch.d[1], nullptr, &uneven, got))) return rc;
+        } else {
+            for (uint32_t m = 0; m < n_mates; ++m) {
+                if ((rc = lime_seq_reader_next(readers[m], batch_reads, &batch.d[m], nullptr))) return rc;
+                if (batch.d[m]) lime_docs_info(batch.d[m], &got[m], nullptr);
+            }
+            uneven = n_mates == 2 && got[0] != got[1];
         }
-        if (n_mates == 2 && got[0] != got[1]) {          // one mate has ended before the other: both counts, from the files' ends
+        if (uneven) {          // one mate has ended before the other: both counts, from the files' ends
             batch.release();
             for (uint32_t m = 0; m < 2; ++m) if ((rc = drain(readers[m], batch_reads))) return rc;
             return fail(LIME_ERR_ARG, "%s: the read sets hold different numbers of reads (%llu in set 0, %llu in set 1)", who,
