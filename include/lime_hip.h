@@ -238,6 +238,25 @@ int lime_apply_records_dev(lime_ctx *ctx, uint32_t n_src, const uint32_t *d_rx, 
                            uint32_t nb, uint32_t bin_shift, const uint64_t *d_bigrecs, uint64_t n_bigrecs,
                            uint64_t cell_lo, uint64_t block_bytes, uint8_t *d_block, void *stream);
 
+/* Test and diagnosis hook, like lime_apply_records_dev for the stage behind it: the FIRST-LEVEL PARTITION of the binned update path alone
+ * (k_bin_rowscan, k_bin_bases, then k_part or k_part_lines -- whichever a pass with this layout would get) on a record pool the caller made.
+ * h_pool: n_prod * prod_waves * n_sub * cap_w host words laid out as the scan lays them: the segment of (wave w, sub-region s) starts at
+ * (w * n_sub + s) * cap_w and holds h_wave_cnt[w * n_sub + s] records; producer p owns the waves p * prod_waves .. + prod_waves - 1.  A pool
+ * record is the cell's low 32 bits, its bin (rec >> bin_shift) + (s << (32 - bin_shift)) (lime_rec_bin).  What a segment holds beyond its
+ * count is never used as a record.
+ * d_out (device, out_words words): the records grouped by bin, each as (rec & ((1 << bin_shift) - 1)) | 1 << bin_shift; bin b's start
+ * goes to h_binbase[b] (n_bins + 1 words: h_binbase[b] = the lower bins' records, h_binbase[n_bins] = all records), and producer p's
+ * records of bin b lie at h_binbase[b] + (the records of b of the producers below p) ..; the order INSIDE one (bin, producer) range is
+ * unspecified.  Words of d_out from h_binbase[n_bins] on are not written.  *kernel: 1 if k_part_lines ran, 0 if k_part.
+ * Honours the ctx options part_lines, force_p64 and p64_test_base (the positions then start at that number; h_binbase is reported without it).
+ * Refused with LIME_ERR_ARG before anything is launched: a NULL pointer, n_prod == 0, prod_waves outside 1 .. 16, n_sub outside 1 .. 8,
+ * cap_w not a multiple of 16 (or prod_waves * n_sub * cap_w beyond 2^32 - 16), a count above cap_w, bin_shift outside 16 .. 25, n_bins
+ * outside 1 .. 3072, a record whose bin is n_bins or more, more records than out_words, d_out not 64-byte aligned.
+ * Uploads the pool into the ctx's own scratch, waits for `stream`, and leaves nothing for lime_get_stats to repeat. */
+int lime_partition_records_dev(lime_ctx *ctx, uint32_t n_prod, uint32_t prod_waves, uint32_t n_sub, uint32_t cap_w, const uint32_t *h_pool,
+                               const uint32_t *h_wave_cnt, uint32_t n_bins, uint32_t bin_shift, uint32_t *d_out, uint64_t out_words,
+                               uint64_t *h_binbase /* n_bins + 1, out */, int *kernel /* out */, void *stream);
+
 /* Runs longer than the halo that cross shard borders: the reference reads on without limit (ClusterLCP.cpp:246-264)
  * and only refuses CLUSTERS longer than LIME_MAX_CLUSTER (ClusterBWT_DA.cpp:558-562).  A shard that ends inside such a
  * run reports it in lime_stats_t.edge (and lime_get_stats returns LIME_ERR_HALO to callers that do not look);

@@ -127,6 +127,7 @@ SYMBOLS = {
     "lime_fused_records_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _u64, _i, _u32, _u32, _u32, _vp]),
     "lime_records_get": (_i, [_vp, _vp, _vp, _vp]),
     "lime_apply_records_dev": (_i, [_vp, _u32, _vp, _vp, _u32, _u32, _vp, _u64, _u64, _u64, _vp, _vp]),
+    "lime_partition_records_dev": (_i, [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _vp, _u64, _vp, C.POINTER(_i), _vp]),
     "lime_comm_exchange_records": (_i, [_vp, _vp, _u32, _u32, _vp, _sz, _pu64, _pu64, _vp]),
     "lime_fused_multi": (_i, [_i, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _pu64, _pu64]),
     "lime_score_choose_multi": (_i, [_i, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _u32, _u32, C.c_float, _vp, _vp, _pp, _pu64]),

@@ -298,6 +298,20 @@ class Context:
         check(self.lib.lime_apply_records_dev(self.h, n_src, _ptr(rx_t), so.ctypes.data, nb, bin_shift, _ptr(bigrecs_t), n_big,
                                               cell_lo, block_bytes, _ptr(block_t), stream))
 
+    def partition_records(self, n_prod, prod_waves, n_sub, cap_w, pool, wave_cnt, n_bins, bin_shift, out_t, out_words=None, stream=None):
+        """test hook (lime_partition_records_dev): the first-level partition alone on a host pool of n_prod * prod_waves * n_sub segments of
+        cap_w words with wave_cnt records each, into the torch device tensor out_t (int32 / uint32 words)
+        -> (numpy bin bases [n_bins + 1], 1 if k_part_lines ran else 0).  Waits for the stream."""
+        import numpy as np
+        pool = np.ascontiguousarray(pool, dtype=np.uint32)
+        wc = np.ascontiguousarray(wave_cnt, dtype=np.uint32)
+        base = np.zeros(n_bins + 1, dtype=np.uint64)
+        kernel = C.c_int(-1)
+        check(self.lib.lime_partition_records_dev(self.h, n_prod, prod_waves, n_sub, cap_w, pool.ctypes.data, wc.ctypes.data, n_bins, bin_shift,
+                                                  _ptr(out_t), out_t.numel() if out_words is None else out_words, base.ctypes.data,
+                                                  C.byref(kernel), stream))
+        return base, int(kernel.value)
+
     def detect_dev(self, lcp_t, da_t, n_own, n_avail, eof, pos_base, n_reads, alpha, stream=None):
         """-> (device pointer of the library-owned record list, n_clusters, max_len); the list stays valid
         until the next detect_dev on this context."""

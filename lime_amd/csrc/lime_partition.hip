@@ -770,34 +770,41 @@ void launch_part(const ScanArgs &a, uint32_t n_prod, const uint64_t *binbase, ui
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_part<PART_WG, BIN_MAX, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BIN_MAX * 16u));
         set.store(true, std::memory_order_relaxed);
     }
-    // whole-line writes (k_part_lines) wherever the bins' line buffers fit the LDS next to the stage; LIME_PART_LINES=0: comparison runs
-    static std::atomic<uint32_t> lines_room[MAX_DEV][2];     // dynamic LDS k_part_lines may ask for on this device (0: not asked yet)
-    const size_t lds_lines = part_lines_lds(a.n_bins, p64);
-    const void *kl = p64 ? reinterpret_cast<const void *>(k_part_lines<true>) : reinterpret_cast<const void *>(k_part_lines<false>);
-    if (lines_ok && a.n_bins <= 3u * PART_WG) {
-        std::atomic<uint32_t> &room = lines_room[cur_device()][p64 ? 1 : 0];
-        uint32_t r = room.load(std::memory_order_relaxed);
-        if (!r) {
-            hipFuncAttributes fa;
-            r = 1u;
-            if (hipFuncGetAttributes(&fa, kl) == hipSuccess && fa.sharedSizeBytes < 160u * 1024u) {
-                const uint32_t dyn = 160u * 1024u - (uint32_t)fa.sharedSizeBytes;
-                if (hipFuncSetAttribute(kl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) == hipSuccess) r = dyn;
-            }
-            (void)hipGetLastError();
-            room.store(r, std::memory_order_relaxed);
-        }
-        // two workgroups per CU must fit (the kernel is a chain of short phases: alone on a CU it is slower than k_part -- configs[2], 1193 bins:
-        // 0.72 against 0.48 ms; N = 1e10, 477 bins, two per CU: 3.8 against 4.2 .. 4.7 ms)
-        const size_t stat = 160u * 1024u - (r > 1u ? r : 0u);               // the kernel's static LDS
-        if (lds_lines <= r && 2u * (lds_lines + stat + 512u) <= 160u * 1024u) {
-            if (p64) hipLaunchKernelGGL(k_part_lines<true>, dim3(n_prod), dim3(PART_WG), lds_lines, st, a, binbase, out);
-            else     hipLaunchKernelGGL(k_part_lines<false>, dim3(n_prod), dim3(PART_WG), lds_lines, st, a, binbase, out);
-            return;
-        }
+    if (part_uses_lines(a.n_bins, p64, lines_ok)) {
+        const size_t lds_lines = part_lines_lds(a.n_bins, p64);
+        if (p64) hipLaunchKernelGGL(k_part_lines<true>, dim3(n_prod), dim3(PART_WG), lds_lines, st, a, binbase, out);
+        else     hipLaunchKernelGGL(k_part_lines<false>, dim3(n_prod), dim3(PART_WG), lds_lines, st, a, binbase, out);
+        return;
     }
     if (p64) hipLaunchKernelGGL((k_part<PART_WG, BIN_MAX, true>), dim3(n_prod), dim3(PART_WG), (size_t)a.n_bins * 16u, st, a, binbase, out);
     else     hipLaunchKernelGGL((k_part<PART_WG, BIN_MAX, false>), dim3(n_prod), dim3(PART_WG), (size_t)a.n_bins * 12u, st, a, binbase, out);
+}
+
+// which of the two first-level kernels launch_part takes on the current device: k_part_lines (true) or k_part (lime_partition_records_dev reports it)
+// (defined behind launch_part: the kernels are instantiated in the order of their first use, and this order keeps the code object what it was)
+// whole-line writes (k_part_lines) wherever the bins' line buffers fit the LDS next to the stage; LIME_PART_LINES=0: comparison runs
+bool part_uses_lines(uint32_t n_bins, bool p64, bool lines_ok)
+{
+    if (!lines_ok || n_bins > 3u * PART_WG) return false;
+    static std::atomic<uint32_t> lines_room[MAX_DEV][2];     // dynamic LDS k_part_lines may ask for on this device (0: not asked yet)
+    const size_t lds_lines = part_lines_lds(n_bins, p64);
+    const void *kl = p64 ? reinterpret_cast<const void *>(k_part_lines<true>) : reinterpret_cast<const void *>(k_part_lines<false>);
+    std::atomic<uint32_t> &room = lines_room[cur_device()][p64 ? 1 : 0];
+    uint32_t r = room.load(std::memory_order_relaxed);
+    if (!r) {
+        hipFuncAttributes fa;
+        r = 1u;
+        if (hipFuncGetAttributes(&fa, kl) == hipSuccess && fa.sharedSizeBytes < 160u * 1024u) {
+            const uint32_t dyn = 160u * 1024u - (uint32_t)fa.sharedSizeBytes;
+            if (hipFuncSetAttribute(kl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) == hipSuccess) r = dyn;
+        }
+        (void)hipGetLastError();
+        room.store(r, std::memory_order_relaxed);
+    }
+    // two workgroups per CU must fit (the kernel is a chain of short phases: alone on a CU it is slower than k_part -- configs[2], 1193 bins:
+    // 0.72 against 0.48 ms; N = 1e10, 477 bins, two per CU: 3.8 against 4.2 .. 4.7 ms)
+    const size_t stat = 160u * 1024u - (r > 1u ? r : 0u);               // the kernel's static LDS
+    return lds_lines <= r && 2u * (lds_lines + stat + 512u) <= 160u * 1024u;
 }
 
 void launch_part2(const uint32_t *recs, const uint64_t *binbase, uint32_t n_bins, uint32_t bin_shift, uint64_t *regbase,

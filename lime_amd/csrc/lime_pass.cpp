@@ -1,6 +1,6 @@
 // lime_pass.cpp -- the passes on device-resident arrays: scratch sizing (ensure_scratch, ensure_binned), the choice of the update path and the bin
 // layout (want_binned, bin_layout_of), the density probe, the kernel sequence of a fused pass (fused_dev_impl), the owner-partitioned record
-// exchange (lime_fused_records_dev, lime_apply_records_dev) and the detect / score / choose / synth entry points that take device pointers.
+// exchange (lime_fused_records_dev, lime_apply_records_dev), the partition stage's test hook (lime_partition_records_dev) and the detect / score / choose / synth entry points that take device pointers.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "lime_device.h"
 #include "lime_ctx.h"
 
 using namespace lime;
@@ -545,6 +546,84 @@ extern "C" int lime_apply_records_dev(lime_ctx *c, uint32_t n_src, const uint32_
     }
     launch_apply_bigrecs(d_bigrecs, n_bigrecs, cell_lo, cell_lo + block_bytes, d_block, st);
     HIP_TRY(hipGetLastError());
+    return LIME_OK;
+}
+
+// ---- test and diagnosis hook: the first-level partition alone on a record pool the caller made ---------------------------------
+// what runs on the stream once the arguments have been checked and the raw counts built; the caller waits for the stream whatever this returns
+// (counts is the caller's vector, and the copies out of it are queued here)
+static int partition_records_run(lime_ctx *c, uint32_t n_prod, uint32_t prod_waves, uint32_t n_sub, uint32_t cap_w, const uint32_t *h_pool,
+                                 const uint32_t *h_wave_cnt, uint32_t n_bins, uint32_t bin_shift, uint32_t *d_out, const std::vector<uint32_t> &counts,
+                                 bool p64, uint64_t *h_binbase, hipStream_t st)
+{
+    int rc;
+    const size_t segs = (size_t)n_prod * prod_waves * n_sub, pool_words = segs * cap_w;
+    if ((rc = c->pool.ensure(pool_words + 16, st, nullptr)) || (rc = ensure_bin_counters(c, segs, counts.size(), st, nullptr))) return rc;
+    if (pool_words) HIP_TRY(hipMemcpyAsync(c->pool.p, h_pool, pool_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->wave_cnt.p, h_wave_cnt, segs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->counts.p, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    ScanArgs a;
+    memset(&a, 0, sizeof a);
+    a.upd_mode = 1; a.pool = c->pool.p; a.cap_w = cap_w; a.n_sub = n_sub; a.wave_cnt = c->wave_cnt.p; a.counts = c->counts.p;
+    a.n_bins = n_bins; a.bin_shift = bin_shift; a.prod_waves = prod_waves;
+    launch_bin_rowscan(c->counts.p, c->totals.p, n_bins, n_prod, st);
+    launch_bin_bases(c->totals.p, c->binbase.p, nullptr, n_bins, st);
+    uint32_t *out = d_out;
+    if (c->p64_test_base) {                               // positions from a base near a multiple of 2^32 on, as in fused_dev_impl
+        launch_add_u64(c->binbase.p, (size_t)n_bins + 1, c->p64_test_base, st);
+        out = d_out - c->p64_test_base;                   // (an address only: the kernels add positions >= the base to it)
+    }
+    launch_part(a, n_prod, c->binbase.p, out, st, p64, c->part_lines != 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_binbase, c->binbase.p, ((size_t)n_bins + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    return LIME_OK;
+}
+
+// The contract is in include/lime_hip.h.  Everything is checked on the host before the first launch: the kernels trust the counts (they
+// index the pool with them) and the records' bins (they index LDS counters with them).
+extern "C" int lime_partition_records_dev(lime_ctx *c, uint32_t n_prod, uint32_t prod_waves, uint32_t n_sub, uint32_t cap_w, const uint32_t *h_pool,
+                                          const uint32_t *h_wave_cnt, uint32_t n_bins, uint32_t bin_shift, uint32_t *d_out, uint64_t out_words,
+                                          uint64_t *h_binbase, int *kernel, void *stream)
+{
+    int rc = check_ctx(c, "lime_partition_records_dev"); if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!h_pool || !h_wave_cnt || !d_out || !h_binbase || !kernel) return fail(LIME_ERR_ARG, "lime_partition_records_dev: NULL argument");
+    if (!n_prod || prod_waves < 1u || prod_waves > 16u || n_sub < 1u || n_sub > MAX_SUB || (cap_w & 15u))
+        return fail(LIME_ERR_ARG, "lime_partition_records_dev: want n_prod >= 1, 1 <= prod_waves <= 16, 1 <= n_sub <= %u, cap_w a multiple of 16", MAX_SUB);
+    if (bin_shift < REGION_SHIFT || bin_shift > BIN_SHIFT_MAX || n_bins < 1u || n_bins > BIN_MAX)
+        return fail(LIME_ERR_ARG, "lime_partition_records_dev: want %u <= bin_shift <= %u and 1 <= n_bins <= %u", REGION_SHIFT, BIN_SHIFT_MAX, BIN_MAX);
+    if (misaligned(d_out, 64)) return fail(LIME_ERR_ARG, "lime_partition_records_dev: d_out must be 64-byte aligned");
+    // (a producer's stream -- its segments, each padded to four records -- is addressed with 32 bits, and so is counts[bin][producer])
+    if ((uint64_t)prod_waves * n_sub * cap_w > 0xFFFFFFF0ull || (uint64_t)n_bins * n_prod > 0xFFFFFFF0ull)
+        return fail(LIME_ERR_ARG, "lime_partition_records_dev: pool too large");
+    const size_t segs = (size_t)n_prod * prod_waves * n_sub;
+    uint64_t total = 0;
+    for (size_t i = 0; i < segs; ++i) {
+        if (h_wave_cnt[i] > cap_w) return fail(LIME_ERR_ARG, "lime_partition_records_dev: segment %zu holds %u records, cap_w is %u", i, h_wave_cnt[i], cap_w);
+        total += h_wave_cnt[i];
+    }
+    if (total > out_words) return fail(LIME_ERR_ARG, "lime_partition_records_dev: %llu records, out_words is %llu", (unsigned long long)total, (unsigned long long)out_words);
+    // 64-bit positions: their high part rides in a record's bits above t through k_part's stage (31 - bin_shift of them)
+    if ((c->p64_test_base + total) >> (32u + 31u - bin_shift)) return fail(LIME_ERR_ARG, "lime_partition_records_dev: positions beyond what bin_shift %u leaves room for", bin_shift);
+    // the raw counts[bin][producer] the scan would have left
+    std::vector<uint32_t> counts((size_t)n_bins * n_prod, 0u);
+    for (size_t i = 0; i < segs; ++i) {
+        const uint32_t sub = (uint32_t)(i % n_sub), p = (uint32_t)(i / ((size_t)prod_waves * n_sub));
+        const uint32_t *seg = h_pool + i * cap_w;
+        for (uint32_t k = 0; k < h_wave_cnt[i]; ++k) {
+            const uint32_t b = rec_bin(seg[k], sub, bin_shift);
+            if (b >= n_bins) return fail(LIME_ERR_ARG, "lime_partition_records_dev: record %u of segment %zu lies in bin %u of %u", k, i, b, n_bins);
+            ++counts[(size_t)b * n_prod + p];
+        }
+    }
+    const bool p64 = c->force_p64 || total >= 0xF0000000ull;
+    *kernel = part_uses_lines(n_bins, p64, c->part_lines != 0) ? 1 : 0;
+    c->last.valid = false;                                // no pass of lime_fused_dev: lime_get_stats has nothing to repeat
+    rc = partition_records_run(c, n_prod, prod_waves, n_sub, cap_w, h_pool, h_wave_cnt, n_bins, bin_shift, d_out, counts, p64, h_binbase, st);
+    const hipError_t e = hipStreamSynchronize(st);        // (also where the run failed half way: its copies read `counts`)
+    if (rc) return rc;
+    HIP_TRY(e);
+    for (uint32_t b = 0; b <= n_bins; ++b) h_binbase[b] -= c->p64_test_base;
     return LIME_OK;
 }
 
