@@ -648,6 +648,36 @@ typedef struct { uint64_t n_pairs, n_overlap, n_cut, symbols_in, symbols_out; } 
 int lime_pair_overlap_trim(const uint8_t *text1, const uint64_t *doc_off1, const uint8_t *text2, const uint64_t *doc_off2, uint32_t n_docs,
                            uint32_t min_overlap, uint32_t max_err_pct, uint8_t **out_text1, uint64_t **out_doc_off1, uint8_t **out_text2,
                            uint64_t **out_doc_off2, uint32_t **insert, lime_overlap_info_t *info);
+/* Per-position read statistics: what the reads look like, cycle by cycle (what fastp and FastQC report before and after filtering).
+ * Integers only.  class(byte) is A, C, G or T after folding with & 0xDF, every other byte is the one class "other": the rule at
+ * lime_read_filter.  Quality bytes are taken raw, with no offset removed (the reader of the tables subtracts 33).
+ * n_pos, 1 .. LIME_QC_MAX_POS, is the number of positions with a row of their own; it need not be a multiple of 64.  The tables are
+ * LIME_QC_WORDS(n_pos) words of uint64_t, in this order:
+ *   row[p][8], p in 0 .. n_pos.  Row p < n_pos counts, over all reads with a symbol at position p: the symbols of class A, C, G, T and
+ *     other (words 0 .. 4); qsum, the sum of the quality bytes at p (5); q20, the quality bytes >= 53 (6); q30, the quality bytes >= 63 (7).
+ *     Row n_pos pools every position >= n_pos with the same eight counters, so that the five class counters summed over all rows are n_text.
+ *   len_hist[n_pos + 1]: a read of length L adds 1 at min(L, n_pos); an empty read is counted at 0.
+ *   gc_hist[101]: a read with acgt >= 1 symbols of a base class, gc of them C or G, adds 1 at (100 * gc) / acgt by integer division; a
+ *     read without a base is counted nowhere.
+ *   mq_hist[256]: a read with L >= 1 and qualities adds 1 at (the sum of its quality bytes) / L by integer division.
+ * Documents without qualities (qual == NULL) leave qsum, q20, q30 and mq_hist untouched.
+ * Every call ADDS to the caller's tables: batches, files and mates sum by calling again; the caller zeroes them.  Every word is exact
+ * for any documents a lime_docs can hold: n_docs <= 2^32 - 1, n_text < 2^32, one document that may be the whole text.
+ * lime_read_qc is the loop form in plain host code, the oracle of lime_docs_qc_dev.  LIME_ERR_ARG with a text: a NULL array (qual may be
+ * NULL), n_pos of 0 or above LIME_QC_MAX_POS, doc_off that does not start at 0 or decreases. */
+#define LIME_QC_MAX_POS 512u
+#define LIME_QC_WORDS(n_pos) (9u * ((n_pos) + 1u) + 101u + 256u)
+int lime_read_qc(const uint8_t *text, const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t n_pos, uint64_t *tables);
+/* The statistics of n_files reads files as JSON, integers only, keys in a fixed order:
+ *   {"lime_qc_report": 1, "positions": P, "files": [{"file": "...", "format": "fasta" | "fastq", "before": {...}, "after": {...}}, ...]}
+ * before[k], after[k]: LIME_QC_WORDS(n_pos) words each, file k as parsed and as it enters classification; formats[k]: 0 FASTA, 1 FASTQ.
+ * A section holds reads, empty, symbols, gc (the C + G symbols), bases {"A": [P + 1 numbers], "C", "G", "T", "other"}, length_hist,
+ * gc_hist; `before` of a FASTQ file then q20, q30 (totals), qual_sum, qual_ge20, qual_ge30 (P + 1 numbers each) and mean_qual_hist
+ * (256).  `after` never holds quality keys: the stages drop the qualities.  The file is written under a temporary name beside `path` and
+ * renamed: a failure leaves no file.  LIME_ERR_ARG with a text: a NULL argument, n_files of 0, n_pos out of range, a format other than
+ * 0 or 1; LIME_ERR_IO with a text when the file cannot be written.  Pure host code. */
+int lime_qc_report_write(const char *path, uint32_t n_files, const char *const *names, const int *formats, uint32_t n_pos,
+                         const uint64_t *const *before, const uint64_t *const *after);
 /* *format = 1 (FASTQ) if the file's first byte is '@', else 0 (FASTA: an empty file and text in front of the first header included).
  * LIME_ERR_IO when the file cannot be read.  Pure host code. */
 int lime_seq_format(const char *path, int *format);
@@ -774,6 +804,14 @@ int  lime_docs_trim_adapter_dev(lime_ctx *ctx, const lime_docs *docs, const uint
  * given back before the call returns.  LIME_ERR_ARG with a text, before any launch: a NULL argument, documents of another context, and
  * lime_read_filter's refusals of the parameters.  On every error nothing stays allocated and *out is NULL.  Synchronises `stream`. */
 int  lime_docs_filter_dev(lime_ctx *ctx, const lime_docs *docs, const lime_filter_t *filter, void *stream, lime_docs **out, lime_filter_info_t *info);
+/* The statistics of the rule at lime_read_qc, on the device: tables (host memory, LIME_QC_WORDS(n_pos) words) += the documents' counts,
+ * every word lime_read_qc's.  Any documents are taken; those with qualities fill the quality counters too.  k_qc_reads
+ * (lime_qc_kernel.hip): one wave on a read, 64 symbols a word; the rows p < n_pos are counted in a per-workgroup table in LDS (32-bit
+ * counters, counter-major), the pooled row (64-bit counters in LDS) and the per-read sums from set bits of ballots; every workgroup
+ * adds its non-zero counters to the 64-bit tables once, at its end.  Device memory next to the handle: the tables, given back before
+ * the call returns.  LIME_ERR_ARG with a text, before any launch: a NULL argument, documents of another context, n_pos of 0 or above
+ * LIME_QC_MAX_POS.  No documents (n_docs = 0) add nothing.  On every error nothing stays allocated.  Synchronises `stream`. */
+int  lime_docs_qc_dev(lime_ctx *ctx, const lime_docs *docs, uint32_t n_pos, void *stream, uint64_t *tables);
 /* The two mates' documents cut by the rule at lime_pair_overlap_trim, on the device: *out1, *out2 = new documents (the caller's; no
  * qualities) whose texts and doc_off are byte for byte the oracle's, d_insert (device memory, n_docs words, may be NULL) its insert[],
  * *info (may be NULL) its counts.  Any documents are taken, as for the other trims; input qualities are dropped.  k_overlap_bounds
@@ -920,6 +958,16 @@ int  lime_seq_reader_set_overlap(lime_seq_reader *r1, lime_seq_reader *r2, uint3
 int  lime_seq_reader_next_pair(lime_seq_reader *r1, lime_seq_reader *r2, uint32_t max_reads, lime_docs **docs1, lime_docs **docs2,
                                uint64_t *first_record);
 int  lime_seq_reader_overlap_info(const lime_seq_reader *r, lime_overlap_info_t *info);
+/* set_qc: from here on every batch adds to two sets of the tables of lime_read_qc (lime_docs_qc_dev), with n_pos rows: RAW (which = 0),
+ * the batch as parsed -- a FASTQ reader then parses with qualities even without set_trim, and drops them behind this pass -- and OUT
+ * (which = 1), the batch as handed out: by lime_seq_reader_next behind the reader's own stages, by lime_seq_reader_next_pair behind the
+ * overlap cut (its inner next adds nothing: a batch is counted once).  The text and doc_off handed out, and whether the documents carry
+ * qualities, are what they are without set_qc.  LIME_ERR_ARG with a text: a NULL reader, n_pos of 0 or above LIME_QC_MAX_POS, a reader
+ * whose lime_seq_reader_next has been called.
+ * qc: tables[0 .. LIME_QC_WORDS(n_pos)) = the sums over the batches so far (overwritten).  Without set_qc n_pos counts as 1 and the
+ * LIME_QC_WORDS(1) words are zeros.  LIME_ERR_ARG with a text: a NULL argument, which above 1. */
+int  lime_seq_reader_set_qc(lime_seq_reader *r, uint32_t n_pos);
+int  lime_seq_reader_qc(const lime_seq_reader *r, int which, uint64_t *tables);
 void lime_seq_reader_close(lime_seq_reader *r);
 
 /* lime_classify_sample_dev batch by batch: per batch, batch_reads (>= 1) records from each of the n_mates readers, one unchanged

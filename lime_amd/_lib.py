@@ -38,6 +38,7 @@ class TrimInfo(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_changed", C.c_uint64), ("n_empty", C.c_uint64), ("symbols_in", C.c_uint64), ("symbols_out", C.c_uint64)]
 
 
+QC_MAX_POS = 512                             # LIME_QC_MAX_POS: the most positions with a row of their own in the tables of lime_read_qc
 FILTER_OFF = 0xFFFFFFFF                      # LIME_FILTER_OFF: lime_filter_t.max_n without a limit
 
 
@@ -192,6 +193,11 @@ SYMBOLS = {
     "lime_docs_filter_dev": (_i, [_vp, _vp, C.POINTER(Filter), _vp, _pp, C.POINTER(FilterInfo)]),
     "lime_seq_reader_set_filter": (_i, [_vp, C.POINTER(Filter)]),
     "lime_seq_reader_filter_info": (_i, [_vp, C.POINTER(FilterInfo)]),
+    "lime_read_qc": (_i, [_vp, _vp, _vp, _u32, _u32, _vp]),
+    "lime_docs_qc_dev": (_i, [_vp, _vp, _u32, _vp, _vp]),
+    "lime_seq_reader_set_qc": (_i, [_vp, _u32]),
+    "lime_seq_reader_qc": (_i, [_vp, _i, _vp]),
+    "lime_qc_report_write": (_i, [C.c_char_p, _u32, _vp, _vp, _u32, _vp, _vp]),
     "lime_pair_overlap_trim": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _pp, _pp, _pp, _pp, _pp, C.POINTER(OverlapInfo)]),
     "lime_docs_trim_overlap_dev": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _pp, _pp, C.POINTER(OverlapInfo)]),
     "lime_seq_reader_set_overlap": (_i, [_vp, _vp, _u32, _u32]),

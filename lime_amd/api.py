@@ -529,6 +529,13 @@ class Context:
         check(self.lib.lime_docs_filter_dev(self.h, docs.h, C.byref(f), stream, C.byref(h), C.byref(fi)))
         return self._docs_of(h), _filter_info(fi)
 
+    def docs_qc(self, docs, n_pos=256, tables=None, stream=None):
+        """the per-position statistics of any Docs (lime_docs_qc_dev; the rule is at lime_read_qc in include/lime_hip.h): tables, the flat
+        uint64 array of qc_words(n_pos) words that the counts are ADDED to (None: fresh zeros) -> the tables split as read_qc gives them"""
+        t = _qc_tables(n_pos, tables)
+        check(self.lib.lime_docs_qc_dev(self.h, docs.h, int(n_pos), stream, t.ctypes.data))
+        return qc_split(t, n_pos)
+
     def docs_trim_overlap(self, d1, d2, min_overlap=30, max_err_pct=10, want_insert=False, stream=None):
         """the two mates' Docs cut at the mates' overlap: adapter read-through found with no adapter given (lime_docs_trim_overlap_dev; the rule
         is at lime_pair_overlap_trim in include/lime_hip.h).  It is the last stage: give it what each mate's trims and filter left
@@ -800,6 +807,21 @@ class SeqReader:
         fi = _lib.FilterInfo()
         check(self.ctx.lib.lime_seq_reader_filter_info(self.h, C.byref(fi)))
         return _filter_info(fi)
+
+    def set_qc(self, n_pos=256):
+        """every batch from here on adds to the reader's two sets of statistics with n_pos rows: the batch as parsed and as handed out
+        (lime_seq_reader_set_qc: before the first next; FASTA or FASTQ)"""
+        check(self.ctx.lib.lime_seq_reader_set_qc(self.h, int(n_pos)))
+        self._qc_pos = int(n_pos)
+
+    def qc(self, which):
+        """the statistics summed over the batches so far, which = 0 or "raw": as parsed, 1 or "out": as handed out (lime_seq_reader_qc)
+        -> the tables split as read_qc gives them; without set_qc zeros with one row"""
+        which = {"raw": 0, "out": 1}.get(which, which)
+        n_pos = getattr(self, "_qc_pos", 1)
+        t = np.zeros(qc_words(n_pos), dtype=np.uint64)
+        check(self.ctx.lib.lime_seq_reader_qc(self.h, int(which), t.ctypes.data))
+        return qc_split(t, n_pos)
 
     def set_overlap(self, other, min_overlap=30, max_err_pct=10):
         """links this reader and `other`, the two mates' files, so that next_pair hands out their batches cut at the mates' overlap
@@ -1257,6 +1279,63 @@ def read_filter(text, doc_off, polyx=None, polyx_min=10, max_len=0, min_len=0, m
     return new_text, new_off, _filter_info(fi)
 
 
+def qc_words(n_pos):
+    """LIME_QC_WORDS(n_pos): the uint64 words of the tables of read_qc"""
+    return 9 * (int(n_pos) + 1) + 101 + 256
+
+
+def _qc_tables(n_pos, tables):
+    if not 1 <= int(n_pos) <= _lib.QC_MAX_POS:
+        raise ValueError(f"n_pos is 1 .. {_lib.QC_MAX_POS}")
+    if tables is None:
+        return np.zeros(qc_words(n_pos), dtype=np.uint64)
+    if not (isinstance(tables, np.ndarray) and tables.dtype == np.uint64 and tables.flags.c_contiguous and tables.shape == (qc_words(n_pos),)):
+        raise ValueError("tables is a contiguous uint64 array of qc_words(n_pos) words")
+    return tables
+
+
+def qc_split(tables, n_pos):
+    """the flat tables -> dict of views: rows (n_pos + 1, 8) [A, C, G, T, other, qsum, q20, q30], len_hist (n_pos + 1), gc_hist (101), mq_hist (256),
+    and tables, the flat array itself"""
+    n = int(n_pos) + 1
+    return {"rows": tables[:8 * n].reshape(n, 8), "len_hist": tables[8 * n:9 * n], "gc_hist": tables[9 * n:9 * n + 101], "mq_hist": tables[9 * n + 101:],
+            "tables": tables}
+
+
+def read_qc(text, doc_off, n_pos=256, qual=None, tables=None):
+    """the per-position statistics' rule in plain host code (lime_read_qc; the oracle of Context.docs_qc): qual, the quality bytes laid out like
+    text, or None; tables as Context.docs_qc takes them (the counts are ADDED) -> dict as qc_split gives"""
+    lib = _lib.load()
+    t = np.ascontiguousarray(text, dtype=np.uint8); off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    q = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)
+    if q is not None and len(q) != len(t):
+        raise ValueError("read_qc: qual is laid out like text")
+    out = _qc_tables(n_pos, tables)
+    if q is not None and not len(q):
+        q = np.zeros(1, dtype=np.uint8)             # (no symbol, but qualities: not NULL)
+    check(lib.lime_read_qc(t.ctypes.data if len(t) else None, None if q is None else q.ctypes.data, off.ctypes.data, len(off) - 1, int(n_pos),
+                           out.ctypes.data))
+    return qc_split(out, n_pos)
+
+
+def qc_report_write(path, names, formats, n_pos, before, after):
+    """the statistics of the reads files `names` as JSON (lime_qc_report_write): formats, "fasta" / "fastq" (or 0 / 1) per file; before, after:
+    per file the tables (the flat array, or the dict that read_qc / Context.docs_qc give)"""
+    k = len(names)
+    if not (len(formats) == len(before) == len(after) == k):
+        raise ValueError("qc_report_write: one format and two sets of tables per file")
+    flat = [[np.ascontiguousarray(x["tables"] if isinstance(x, dict) else x, dtype=np.uint64) for x in side] for side in (before, after)]
+    for side in flat:
+        for x in side:
+            if x.shape != (qc_words(n_pos),):
+                raise ValueError("qc_report_write: tables of qc_words(n_pos) words")
+    nm = (C.c_char_p * max(k, 1))(*[os.fsencode(n) for n in names])
+    fm = (C.c_int * max(k, 1))(*[_format_of(f) for f in formats])
+    pb = (C.c_void_p * max(k, 1))(*[x.ctypes.data for x in flat[0]])
+    pa = (C.c_void_p * max(k, 1))(*[x.ctypes.data for x in flat[1]])
+    check(_lib.load().lime_qc_report_write(os.fsencode(path), k, nm, fm, int(n_pos), pb, pa))
+
+
 def seq_format(path):
     """"fastq" if the file's first byte is '@', else "fasta" (lime_seq_format)"""
     f = C.c_int(0)
@@ -1345,7 +1424,8 @@ def lime_paired(files, output, num_reads, num_genomes, lineage, read_len, thread
 
 def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16, beta=0.25, rank=1, trlcp=0, ebwt=True, higher=False, binary=True,
                ctx=None, batch_reads=0, window_bytes=0, trim_qual=None, trim_adapter=None,
-               adapter_overlap=3, adapter_error=10, trim_polyx=None, max_len=0, min_len=0, max_n=None, min_complexity=0, trim_overlap=None):
+               adapter_overlap=3, adapter_error=10, trim_polyx=None, max_len=0, min_len=0, max_n=None, min_complexity=0, trim_overlap=None,
+               qc_report=None, qc_positions=None):
     """`LiME_fasta reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx) --lineage LineageFile --readlen (L | auto) --out output
     [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k]`, like lime_amd/bin/LiME_fasta (read_len="auto": every read by its own length): the files are parsed on the device (each reads file
     FASTA or four-line FASTQ, by its first byte; refs FASTA), the
@@ -1361,10 +1441,19 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     change lengths and need read_len="auto"; the other three only empty reads and are taken with a fixed read_len too.
     trim_overlap: `--trim-overlap O[,E]`, O or (O, E): adapter read-through cut from the two mates' overlap, with no adapter given
     (Context.docs_trim_overlap), last, behind each mate's trims and filter; it needs two reads files and read_len="auto".
+    qc_report, qc_positions: `--qc-report FILE [--qc-positions P]`: the per-position statistics of every reads file as parsed and as it enters
+    classification (Context.docs_qc; SeqReader.set_qc with batch_reads), written to FILE as JSON (qc_report_write); P is 1 .. 512, default 256.
     -> counts {C, U, A, H}"""
     reads = [reads] if isinstance(reads, (str, bytes, os.PathLike)) else list(reads)
     if len(reads) not in (1, 2) or (refs is None) == (gidx is None):
         raise ValueError("LiME_fasta takes one or two reads files and either refs or gidx")
+    if qc_positions is not None and qc_report is None:
+        raise ValueError("LiME_fasta: qc_positions needs qc_report")
+    qc_pos = 256 if qc_positions is None else int(qc_positions)
+    if not 1 <= qc_pos <= _lib.QC_MAX_POS:
+        raise ValueError(f"LiME_fasta: qc_positions is 1 .. {_lib.QC_MAX_POS}")
+    formats = [seq_format(r) for r in reads] if qc_report is not None else None
+    qc_before, qc_after = [], []
     if trim_qual is not None:
         q5, q3 = _trim_cutoffs(trim_qual)
         if read_len != "auto":
@@ -1400,12 +1489,20 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
             if trim_qual is not None:
                 for m in mates:
                     m.set_trim(q5, q3)
+            if qc_report is not None:
+                for m in mates:
+                    m.set_qc(qc_pos)
         elif trim_qual is not None:
             mates = []
             for r in reads:
                 raw = ctx.docs_from_fastq_qual(r)
+                if qc_report is not None:
+                    qc_before.append(ctx.docs_qc(raw, qc_pos))
                 mates.append(ctx.docs_trim(raw, q5, q3)[0])
                 raw.close()
+        elif qc_report is not None:                                 # (a FASTQ file's reads keep their qualities: no later step looks at them)
+            mates = [ctx.docs_from_fastq_qual(r) if f == "fastq" else ctx.docs_from_file(r) for r, f in zip(reads, formats)]
+            qc_before = [ctx.docs_qc(m, qc_pos) for m in mates]
         else:
             mates = [ctx.docs_from_file(r) for r in reads]
         if trim_adapter is not None:
@@ -1430,6 +1527,8 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
                 mates = list(ctx.docs_trim_overlap(whole[0], whole[1], *ov)[:2])
                 for m in whole:
                     m.close()
+        if qc_report is not None and not batch_reads:               # the reads as they enter classification
+            qc_after = [ctx.docs_qc(m, qc_pos) for m in mates]
         if refs is not None:
             g = ctx.docs_from_fasta(refs)
             nd, nt = g.info()
@@ -1456,6 +1555,9 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
             v, counts, _ = ctx.classify_sample_shards(mates, gi, tx, alpha, norm, float(np.float32(beta)), ebwt, binary, trlcp)
         else:
             v, counts, _ = ctx.classify_sample(mates, gi, tx, alpha, norm, float(np.float32(beta)), ebwt, binary, 0 if refs is not None else trlcp)
+        if qc_report is not None and batch_reads:
+            qc_before = [m.qc("raw") for m in mates]
+            qc_after = [m.qc("out") for m in mates]
         for d in mates:
             d.close()
         for g in shards:
@@ -1467,6 +1569,8 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
             tx.close()
     if not batch_reads:
         write_classification(output, v)
+    if qc_report is not None:
+        qc_report_write(qc_report, [os.fspath(r) for r in reads], formats, qc_pos, qc_before, qc_after)
     return counts
 
 

@@ -3,6 +3,7 @@
 //              [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]
 //              [--trim-adapter SEQ[,SEQ2] [--adapter-overlap O] [--adapter-error E]]
 //              [--trim-polyx BASES[,T]] [--max-len K] [--min-len M] [--max-n K] [--min-complexity C] [--trim-overlap O[,E]]
+//              [--qc-report FILE [--qc-positions P]]
 // Each reads file is FASTA or four-line FASTQ, decided by its first byte ('@': FASTQ; lime_docs_from_file), the mates each on their own;
 // --refs is FASTA.  The files' bytes go to the device as they are and are parsed there; per collection (reads_1, its reverse
 // complements, reads_2, its reverse complements: the script's `seqtk seq -r`) the reads are merged into the genome index, scanned and
@@ -50,6 +51,12 @@
 // judges a read before this cut (the floor behind it is O), and a 5' quality cut (--trim-qual Q5,Q3) moves a read's anchor: such a pair is
 // judged on the strings as they are and usually has no overlap.  The reverse complements are made from the cut reads.  One line of counts
 // for the pair: the pairs with an overlap, the pairs cut, the symbols before and after.
+// --qc-report FILE: per-position statistics of the reads, by the rule at lime_read_qc in include/lime_hip.h, counted on the device
+// (lime_docs_qc_dev; with --batch-reads lime_seq_reader_set_qc) and written to FILE as JSON (lime_qc_report_write): one entry per reads file, in
+// the order given; `before` is the file as parsed (with the quality tables for FASTQ), `after` the mate's reads as they enter
+// classification, behind every stage asked for, --trim-overlap included.  --qc-positions P: the positions with a row of their own, 1 .. 512
+// (default 256); later ones are pooled.  The report is the same with and without --batch-reads, `output` is what it is without the flag, and
+// one line names FILE.  Any reads files, any --gidx / --refs, any --readlen.
 // The defaults are the script's constants (LiME_paired.sh:21-23); norm = readLen + 1 - alpha (ClusterBWT_DA.cpp:555).  The reference's
 // compile-time switches are environment variables, as for the other drop-ins: LIME_EBWT (default 1), LIME_BIN (default 1), LIME_HIGHER (0).
 #include <string.h>
@@ -202,6 +209,9 @@ int main(int argc, char **argv)
     bool filter = false;
     unsigned ov_overlap = 30, ov_err = 10;     // --trim-overlap
     bool cut_overlap = false;
+    const char *qc_report = nullptr;           // --qc-report, --qc-positions
+    unsigned qc_pos = 256;
+    bool have_qc_pos = false;
     unsigned long long window_bytes = 0;
     bool batched = false, have_window = false;
     float beta = 0.25f;
@@ -235,10 +245,13 @@ int main(int argc, char **argv)
             if (more && parse_u32(argv[i + 1], &flt.min_complexity) && flt.min_complexity && flt.min_complexity <= 100) { ++i; filter = true; } else bad = true;
         }
         else if (!strcmp(argv[i], "--trim-overlap")) { if (more && parse_overlap(argv[i + 1], &ov_overlap, &ov_err)) { ++i; cut_overlap = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--qc-report")) { if (more) qc_report = argv[++i]; else bad = true; }
+        else if (!strcmp(argv[i], "--qc-positions")) { if (more && parse_u32(argv[i + 1], &qc_pos) && qc_pos && qc_pos <= LIME_QC_MAX_POS) { ++i; have_qc_pos = true; } else bad = true; }
         else if (!strcmp(argv[i], "--window-bytes")) { if (more && sscanf(argv[i + 1], "%llu", &window_bytes) == 1 && window_bytes) { ++i; have_window = true; } else bad = true; }
         else reads.push_back(argv[i]);
     }
     if (have_window && !batched) bad = true;
+    if (have_qc_pos && !qc_report) bad = true;
     if (trim && !len_auto) bad = true;             // (a fixed norm on trimmed reads)
     const bool cut_adapter = n_adapters > 0;
     if (cut_adapter && !len_auto) bad = true;      // (the same)
@@ -254,6 +267,7 @@ int main(int argc, char **argv)
                   << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]\n"
                   << "           [--trim-adapter SEQ[,SEQ2] [--adapter-overlap 3] [--adapter-error 10]]\n"
                   << "           [--trim-polyx BASES[,10]] [--max-len K] [--min-len M] [--max-n K] [--min-complexity C] [--trim-overlap O[,E]]\n"
+                  << "           [--qc-report FILE [--qc-positions 256]]\n"
                   << "  classifies the reads of one sample (one file: single-end, two: paired-end) against the genomes of refs.fasta, or of an\n"
                   << "  index written by BuildIndex --refs, and writes only `output` (the classification file).  A reads file is FASTA or\n"
                   << "  four-line FASTQ, by its first byte ('@': FASTQ), each mate on its own; refs.fasta is FASTA.  --trlcp k: lcp values\n"
@@ -283,6 +297,9 @@ int main(int argc, char **argv)
                   << "  of them wrong (0 .. 50, default 10); both mates keep I symbols.  Two reads files and --readlen auto; FASTA or FASTQ.  It runs\n"
                   << "  last, behind each mate's trims and filter: --min-len judges a read before this cut (the floor behind it is O), and a 5'\n"
                   << "  quality cut moves a read's anchor, so such a pair usually has no overlap.  One line of counts for the pair.\n"
+                  << "  --qc-report FILE: per-position statistics of every reads file as parsed (`before`) and as it enters classification, behind\n"
+                  << "  the stages (`after`), counted on the device and written to FILE as JSON: bases, qualities (FASTQ, before), lengths, GC.\n"
+                  << "  --qc-positions P: the positions with a row of their own, 1 .. 512 (default 256); later ones are pooled.\n"
                   << "  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
@@ -313,10 +330,13 @@ int main(int argc, char **argv)
         lime_taxonomy_free(probe);
     }
 
-    for (uint32_t m = 0; m < n_mates && trim; ++m) {      // known before a device is opened, like the shards' headers
-        int format = 0;
+    int formats[2] = {0, 0};
+    std::vector<uint64_t> qc_before[2], qc_after[2];     // --qc-report: the tables of each reads file
+    for (uint32_t m = 0; m < n_mates && (trim || qc_report); ++m) {      // known before a device is opened, like the shards' headers
+        int &format = formats[m];
         if (lime_seq_format(reads[m], &format) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return -LIME_ERR_IO; }
-        if (format != 1) { std::cerr << "Error reading " << reads[m] << ": --trim-qual needs the qualities of a FASTQ file; this one is FASTA." << std::endl; return 1; }
+        if (qc_report) { qc_before[m].assign(LIME_QC_WORDS(qc_pos), 0); qc_after[m].assign(LIME_QC_WORDS(qc_pos), 0); }
+        if (trim && format != 1) { std::cerr << "Error reading " << reads[m] << ": --trim-qual needs the qualities of a FASTQ file; this one is FASTA." << std::endl; return 1; }
     }
 
     lime_ctx *ctx = nullptr;
@@ -333,6 +353,7 @@ int main(int argc, char **argv)
             std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1;
         }
         if (filter && lime_seq_reader_set_filter(readers[m], &flt) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
+        if (qc_report && lime_seq_reader_set_qc(readers[m], qc_pos) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
     }
     if (batched && cut_overlap && lime_seq_reader_set_overlap(readers[0], readers[1], ov_overlap, ov_err) != LIME_OK) {
         std::cerr << "Error reading " << reads[0] << ": " << lime_last_error() << std::endl; return 1;
@@ -343,11 +364,17 @@ int main(int argc, char **argv)
             lime_docs *raw = nullptr;
             lime_trim_info_t ti;
             if ((rc = lime_docs_from_fastq_qual(ctx, reads[m], &raw)) == LIME_OK) {
-                rc = lime_docs_trim_dev(ctx, raw, q5, q3, nullptr, &mates[m], &ti);
+                if (qc_report) rc = lime_docs_qc_dev(ctx, raw, qc_pos, nullptr, qc_before[m].data());
+                if (rc == LIME_OK) rc = lime_docs_trim_dev(ctx, raw, q5, q3, nullptr, &mates[m], &ti);
                 lime_docs_free(raw);
                 if (rc == LIME_OK) print_trim(reads[m], q5, q3, ti);
             }
-        } else rc = lime_docs_from_file(ctx, reads[m], &mates[m]);
+        } else if (qc_report && formats[m] == 1) {  // the report's quality tables: the reads keep their qualities, which no later step looks at
+            if ((rc = lime_docs_from_fastq_qual(ctx, reads[m], &mates[m])) == LIME_OK) rc = lime_docs_qc_dev(ctx, mates[m], qc_pos, nullptr, qc_before[m].data());
+        } else {
+            rc = lime_docs_from_file(ctx, reads[m], &mates[m]);
+            if (rc == LIME_OK && qc_report) rc = lime_docs_qc_dev(ctx, mates[m], qc_pos, nullptr, qc_before[m].data());
+        }
         if (rc == LIME_OK && cut_adapter) {        // the reads as parsed or as the quality trim left them, then cut at their adapters
             lime_docs *whole = mates[m];
             lime_trim_info_t ti;
@@ -375,6 +402,8 @@ int main(int argc, char **argv)
         if (rc != LIME_OK) { std::cerr << "Error reading " << reads[0] << ": " << lime_last_error() << std::endl; return 1; }
         print_overlap(reads[0], reads[1], ov_overlap, ov_err, oi);
     }
+    for (uint32_t m = 0; m < n_mates && !batched && qc_report; ++m)     // the reads as they enter classification
+        if (lime_docs_qc_dev(ctx, mates[m], qc_pos, nullptr, qc_after[m].data()) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
     if (!batched) { uint32_t nd = 0; lime_docs_info(mates[0], &nd, nullptr); numReads = nd; }
     clk.mark(batched ? "readers" : "reads (parsed on the device)");
     lime_gindex *gi = nullptr;
@@ -447,6 +476,10 @@ int main(int argc, char **argv)
             lime_seq_reader_overlap_info(readers[0], &oi);
             print_overlap(reads[0], reads[1], ov_overlap, ov_err, oi);
         }
+        for (uint32_t m = 0; m < n_mates && qc_report; ++m) {
+            lime_seq_reader_qc(readers[m], 0, qc_before[m].data());
+            lime_seq_reader_qc(readers[m], 1, qc_after[m].data());
+        }
         clk.mark("batches: reads, collections, classification");
         if (lime_classification_writer_close(sink.w, 1) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
         clk.mark("output file");
@@ -471,6 +504,11 @@ int main(int argc, char **argv)
         clk.mark("collections, classification");
         if (lime_write_classification(output, verdicts.data(), (uint32_t)numReads) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
         clk.mark("output file");
+    }
+    if (qc_report) {
+        const uint64_t *before[2] = {qc_before[0].data(), qc_before[1].data()}, *after[2] = {qc_after[0].data(), qc_after[1].data()};
+        if (lime_qc_report_write(qc_report, n_mates, reads.data(), formats, qc_pos, before, after) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
+        std::cout << "Read statistics (" << qc_pos << " positions, before and after the stages): " << qc_report << std::endl;
     }
     lime_shutdown(ctx);
     lime_taxonomy_free(tx);

@@ -247,6 +247,8 @@ struct __attribute__((visibility("hidden"))) lime_seq_reader {
     lime_filter_info_t filtered = {0, 0, 0, 0, 0, 0, 0, 0};
     lime_seq_reader *mate = nullptr; uint32_t ov_overlap = 0, ov_err = 0;       // lime_seq_reader_set_overlap: the other mate's reader; next_pair cuts
     lime_overlap_info_t overlapped = {0, 0, 0, 0, 0};      // every batch of the two at the mates' overlap, last (the sums: kept in both readers)
+    uint32_t qc_pos = 0;                    // lime_seq_reader_set_qc: n_pos, 0 without; the tables of the batches as parsed and as handed out
+    std::vector<uint64_t> qc_raw, qc_out;
     ~lime_seq_reader();
 };
 
@@ -324,6 +326,8 @@ int docs_adapter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const
 // argument checks
 int filter_check(const char *who, const lime_filter_t *f);
 int docs_filter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const lime_filter_t *f, hipStream_t st, lime_docs **out, lime_filter_info_t *info);
+// lime_docs.cpp: lime_docs_qc_dev without its argument checks
+int docs_qc_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t n_pos, hipStream_t st, uint64_t *tables);
 // lime_host.cpp: the overlap cut's refusals of its parameters (LIME_ERR_ARG with a text); lime_docs.cpp: lime_docs_trim_overlap_dev without
 // its argument checks
 int overlap_check(const char *who, uint32_t min_overlap, uint32_t max_err_pct);

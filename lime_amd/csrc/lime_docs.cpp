@@ -1,6 +1,6 @@
 // lime_docs.cpp -- document collections that stay in HBM (lime_docs: made from the raw bytes of a FASTA or FASTQ file by the kernels of
 // lime_fasta_kernel.hip / lime_fastq_kernel.hip, or copied from parsed arrays), their reverse complements, FASTQ reads with their quality strings and
-// the quality trim (lime_fqtrim_kernel.hip), the adapter trim (lime_adapter_kernel.hip), the read filter (lime_filter_kernel.hip), the overlap cut (lime_overlap_kernel.hip), and a whole sample from documents to verdicts
+// the quality trim (lime_fqtrim_kernel.hip), the adapter trim (lime_adapter_kernel.hip), the read filter (lime_filter_kernel.hip), the overlap cut (lime_overlap_kernel.hip), the per-position statistics (lime_qc_kernel.hip), and a whole sample from documents to verdicts
 // (lime_classify_sample_dev: per collection the merge into the genome index, the scan and clusterChoose, then Classify over the lists).
 // include/lime_hip.h states the contract.
 #include <hip/hip_runtime.h>
@@ -517,6 +517,36 @@ extern "C" int lime_docs_filter_dev(lime_ctx *c, const lime_docs *docs, const li
     int rc = filter_check(who, f); if (rc) return rc;
     if ((rc = check_ctx(c, who))) return rc;
     return docs_filter_impl(c, who, docs, f, (hipStream_t)stream, out, info);
+}
+
+// ---- per-position statistics (lime_qc_kernel.hip: k_qc_reads): the tables cleared on the device, the kernel, the copy back, the sum ----
+int lime_host::docs_qc_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t n_pos, hipStream_t st, uint64_t *tables)
+{
+    (void)c;
+    const uint32_t nd = docs->n_docs;
+    if (!nd) return LIME_OK;
+    const size_t n_words = LIME_QC_WORDS(n_pos);
+    DevBuf d_tables;
+    int rc = d_tables.alloc(n_words * 8);
+    if (rc) return fail(rc, "%s: no device memory for the tables of %u positions: %s", who, n_pos, lime_last_error());
+    std::vector<uint64_t> part(n_words);
+    HIP_TRY(hipMemsetAsync(d_tables.p, 0, n_words * 8, st));
+    qc_launch_reads(docs->text.p, docs->qual.p, docs->doc_off.p, nd, n_pos, static_cast<uint64_t *>(d_tables.p), st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(part.data(), d_tables.p, n_words * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                   // (the tables go back when this returns)
+    for (size_t k = 0; k < n_words; ++k) tables[k] += part[k];
+    return LIME_OK;
+}
+
+extern "C" int lime_docs_qc_dev(lime_ctx *c, const lime_docs *docs, uint32_t n_pos, void *stream, uint64_t *tables)
+{
+    const char *who = "lime_docs_qc_dev";
+    if (!c || !docs || !tables) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (docs->ctx != c) return fail(LIME_ERR_ARG, "%s: the documents belong to another context", who);
+    if (!n_pos || n_pos > LIME_QC_MAX_POS) return fail(LIME_ERR_ARG, "%s: %u positions; there are 1 .. %u", who, n_pos, LIME_QC_MAX_POS);
+    int rc = check_ctx(c, who); if (rc) return rc;
+    return docs_qc_impl(c, who, docs, n_pos, (hipStream_t)stream, tables);
 }
 
 // ---- the overlap cut (lime_overlap_kernel.hip: k_overlap_bounds): one kernel over the pairs, then per mate the trims' prefix sum and copy ----

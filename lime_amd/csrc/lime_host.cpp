@@ -3,6 +3,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
+#include <string>
 #include <vector>
 
 #include "lime_hip.h"
@@ -628,5 +630,131 @@ extern "C" int lime_seq_format(const char *path, int *format)
     const int ch = fgetc(in.f);
     if (ch == EOF && ferror(in.f)) return lime_host::fail(LIME_ERR_IO, "lime_seq_format: cannot read %s", path);
     *format = ch == '@';
+    return LIME_OK;
+}
+
+// ---- per-position read statistics: the loop form of the rule (include/lime_hip.h), the oracle of lime_docs_qc_dev ----------------
+extern "C" int lime_read_qc(const uint8_t *text, const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t n_pos, uint64_t *tables)
+{
+    const char *who = "lime_read_qc";
+    if (!doc_off || !tables) return lime_host::fail(LIME_ERR_ARG, "%s: NULL array", who);
+    if (!n_pos || n_pos > LIME_QC_MAX_POS) return lime_host::fail(LIME_ERR_ARG, "%s: %u positions; there are 1 .. %u", who, n_pos, LIME_QC_MAX_POS);
+    if (doc_off[0] != 0) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off does not start at 0", who);
+    for (uint32_t r = 0; r < n_docs; ++r)
+        if (doc_off[r + 1] < doc_off[r]) return lime_host::fail(LIME_ERR_ARG, "%s: doc_off decreases at read %u", who, r);
+    if (doc_off[n_docs] && !text) return lime_host::fail(LIME_ERR_ARG, "%s: NULL array", who);
+    uint64_t *len_hist = tables + 8u * ((size_t)n_pos + 1u), *gc_hist = len_hist + n_pos + 1u, *mq_hist = gc_hist + 101;
+    for (uint32_t r = 0; r < n_docs; ++r) {
+        const uint64_t a = doc_off[r], L = doc_off[r + 1] - a;
+        uint64_t gc = 0, acgt = 0, qs = 0;
+        for (uint64_t p = 0; p < L; ++p) {
+            uint64_t *row = tables + 8u * (p < n_pos ? p : n_pos);
+            const uint32_t c = class_of(text[a + p]);
+            ++row[c];
+            acgt += c < 4u;
+            gc += c == 1u || c == 2u;
+            if (qual) {
+                const uint32_t q = qual[a + p];
+                row[5] += q; row[6] += q >= 53u; row[7] += q >= 63u;
+                qs += q;
+            }
+        }
+        ++len_hist[L < n_pos ? L : n_pos];
+        if (acgt) ++gc_hist[100u * gc / acgt];
+        if (qual && L) ++mq_hist[qs / L];
+    }
+    return LIME_OK;
+}
+
+// ---- the report of the statistics as JSON (include/lime_hip.h: lime_qc_report_write) ----
+namespace {
+void qc_json_string(std::string &o, const char *s)
+{
+    o += '"';
+    for (; *s; ++s) {
+        const unsigned char ch = (unsigned char)*s;
+        if (ch == '"' || ch == '\\') { o += '\\'; o += (char)ch; }
+        else if (ch < 0x20) { char b[8]; snprintf(b, sizeof b, "\\u%04x", ch); o += b; }
+        else o += (char)ch;
+    }
+    o += '"';
+}
+void qc_json_u64(std::string &o, uint64_t v)
+{
+    char b[24];
+    snprintf(b, sizeof b, "%llu", (unsigned long long)v);
+    o += b;
+}
+// "key": [t[0], t[stride], ... n numbers]
+void qc_json_array(std::string &o, const char *key, const uint64_t *t, size_t n, size_t stride)
+{
+    o += '"'; o += key; o += "\": [";
+    for (size_t k = 0; k < n; ++k) { if (k) o += ", "; qc_json_u64(o, t[k * stride]); }
+    o += ']';
+}
+void qc_json_section(std::string &o, const uint64_t *t, uint32_t n_pos, bool with_qual)
+{
+    const size_t rows = (size_t)n_pos + 1u;
+    const uint64_t *len_hist = t + 8u * rows, *gc_hist = len_hist + rows, *mq_hist = gc_hist + 101;
+    uint64_t reads = 0, symbols = 0, gc = 0, q20 = 0, q30 = 0;
+    for (size_t p = 0; p < rows; ++p) {
+        reads += len_hist[p];
+        for (int c = 0; c < 5; ++c) symbols += t[8u * p + c];
+        gc += t[8u * p + 1] + t[8u * p + 2];
+        q20 += t[8u * p + 6]; q30 += t[8u * p + 7];
+    }
+    o += "{\"reads\": "; qc_json_u64(o, reads);
+    o += ", \"empty\": "; qc_json_u64(o, len_hist[0]);
+    o += ", \"symbols\": "; qc_json_u64(o, symbols);
+    o += ", \"gc\": "; qc_json_u64(o, gc);
+    o += ",\n    \"bases\": {";
+    static const char *const names[5] = {"A", "C", "G", "T", "other"};
+    for (int c = 0; c < 5; ++c) { if (c) o += ",\n      "; qc_json_array(o, names[c], t + c, rows, 8); }
+    o += "},\n    "; qc_json_array(o, "length_hist", len_hist, rows, 1);
+    o += ",\n    "; qc_json_array(o, "gc_hist", gc_hist, 101, 1);
+    if (with_qual) {
+        o += ",\n    \"q20\": "; qc_json_u64(o, q20);
+        o += ", \"q30\": "; qc_json_u64(o, q30);
+        o += ",\n    "; qc_json_array(o, "qual_sum", t + 5, rows, 8);
+        o += ",\n    "; qc_json_array(o, "qual_ge20", t + 6, rows, 8);
+        o += ",\n    "; qc_json_array(o, "qual_ge30", t + 7, rows, 8);
+        o += ",\n    "; qc_json_array(o, "mean_qual_hist", mq_hist, 256, 1);
+    }
+    o += '}';
+}
+}
+
+extern "C" int lime_qc_report_write(const char *path, uint32_t n_files, const char *const *names, const int *formats, uint32_t n_pos,
+                                    const uint64_t *const *before, const uint64_t *const *after)
+{
+    const char *who = "lime_qc_report_write";
+    if (!path || !names || !formats || !before || !after) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (!n_files) return lime_host::fail(LIME_ERR_ARG, "%s: no file to report on", who);
+    if (!n_pos || n_pos > LIME_QC_MAX_POS) return lime_host::fail(LIME_ERR_ARG, "%s: %u positions; there are 1 .. %u", who, n_pos, LIME_QC_MAX_POS);
+    for (uint32_t k = 0; k < n_files; ++k) {
+        if (!names[k] || !before[k] || !after[k]) return lime_host::fail(LIME_ERR_ARG, "%s: NULL argument (file %u)", who, k);
+        if (formats[k] != 0 && formats[k] != 1) return lime_host::fail(LIME_ERR_ARG, "%s: format %d of file %u; 0 is FASTA, 1 FASTQ", who, formats[k], k);
+    }
+    std::string o = "{\"lime_qc_report\": 1, \"positions\": ";
+    qc_json_u64(o, n_pos);
+    o += ", \"files\": [";
+    for (uint32_t k = 0; k < n_files; ++k) {
+        o += k ? ",\n  {\"file\": " : "\n  {\"file\": ";
+        qc_json_string(o, names[k]);
+        o += formats[k] ? ", \"format\": \"fastq\"" : ", \"format\": \"fasta\"";
+        o += ",\n   \"before\": "; qc_json_section(o, before[k], n_pos, formats[k] == 1);
+        o += ",\n   \"after\": "; qc_json_section(o, after[k], n_pos, false);
+        o += '}';
+    }
+    o += "]}\n";
+    const std::string tmp = std::string(path) + ".tmp" + std::to_string((long)getpid());
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) return lime_host::fail(LIME_ERR_IO, "%s: cannot write %s", who, path);
+    const bool wrote = fwrite(o.data(), 1, o.size(), f) == o.size();
+    const bool closed = fclose(f) == 0;
+    if (!wrote || !closed || rename(tmp.c_str(), path) != 0) {
+        remove(tmp.c_str());
+        return lime_host::fail(LIME_ERR_IO, "%s: cannot write %s", who, path);
+    }
     return LIME_OK;
 }

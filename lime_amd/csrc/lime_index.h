@@ -130,6 +130,11 @@ void ad_launch_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_d
 void fl_launch_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const lime_filter_t *f, uint32_t *lo32, uint32_t *len32, uint64_t *counts,
                       hipStream_t st);
 
+// ---- lime_qc_kernel.hip: per-position statistics of the reads (lime_docs.cpp) ----
+// tables[0 .. LIME_QC_WORDS(n_pos)) (device memory) += the counts of the rule (include/lime_hip.h: lime_read_qc); qual may be NULL: documents
+// without qualities.  1 <= n_pos <= LIME_QC_MAX_POS; nothing is launched for no reads
+void qc_launch_reads(const uint8_t *text, const uint8_t *qual, const uint64_t *doc_off, uint32_t n_docs, uint32_t n_pos, uint64_t *tables, hipStream_t st);
+
 // ---- lime_overlap_kernel.hip: where the two mates of a pair run into the adapter, from their overlap alone (lime_docs.cpp) ----
 // With I* of pair r by the rule (include/lime_hip.h: lime_pair_overlap_trim): lo1[r] = lo2[r] = 0, len1[r] = min(La, I*), len2[r] =
 // min(Lb, I*) (La, Lb without an I*), in fqt_launch_bounds' conventions, so that per mate the prefix sum and fqt_launch_copy follow

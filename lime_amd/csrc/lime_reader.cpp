@@ -202,7 +202,8 @@ static int reader_compact(lime_seq_reader *r, const char *who, uint64_t new_cap)
     return LIME_OK;
 }
 
-static int reader_next(lime_seq_reader *r, const char *who, uint32_t max_reads, lime_docs **docs, uint64_t *first_record)
+// out_qc: the batch handed out is added to the reader's OUT tables here (next_pair adds it behind its cut)
+static int reader_next(lime_seq_reader *r, const char *who, uint32_t max_reads, lime_docs **docs, uint64_t *first_record, bool out_qc)
 {
     for (;;) {
         int rc;
@@ -227,9 +228,14 @@ static int reader_next(lime_seq_reader *r, const char *who, uint32_t max_reads, 
         if (cut[0] > n) return fail(LIME_ERR_HIP, "%s: the cut lies behind the window", who);
         lime_docs *d = nullptr;
         const uint8_t *b = r->win.p + r->start;
-        if (r->format) rc = docs_parse_fastq_dev(r->ctx, who, b, cut[0], r->n_lines, nullptr, &d, r->trim);
+        if (r->format) rc = docs_parse_fastq_dev(r->ctx, who, b, cut[0], r->n_lines, nullptr, &d, r->trim || r->qc_pos);
         else rc = docs_parse_fasta_dev(r->ctx, who, b, cut[0], nullptr, &d);
         if (rc) return rc;
+        if (r->qc_pos) {                                 // the batch as parsed; without a trim the qualities were parsed for this alone
+            rc = docs_qc_impl(r->ctx, who, d, r->qc_pos, nullptr, r->qc_raw.data());
+            if (rc) { lime_docs_free(d); return rc; }
+            if (!r->trim) d->qual.release();
+        }
         if (r->trim) {                                   // the batch as it is handed out: trimmed, without qualities
             lime_docs *t = nullptr;
             lime_trim_info_t ti;
@@ -272,12 +278,13 @@ static int reader_next(lime_seq_reader *r, const char *who, uint32_t max_reads, 
         r->n_records += nd;
         if (r->format) r->n_lines += 4ull * nd;
         if (!nd) { lime_docs_free(d); continue; }        // (FASTA without a header line up to the file's end: no record, the next turn ends)
+        if (r->qc_pos && out_qc && (rc = docs_qc_impl(r->ctx, who, d, r->qc_pos, nullptr, r->qc_out.data()))) { lime_docs_free(d); return rc; }
         *docs = d;
         return LIME_OK;
     }
 }
 
-extern "C" int lime_seq_reader_next(lime_seq_reader *r, uint32_t max_reads, lime_docs **docs, uint64_t *first_record)
+static int seq_next(lime_seq_reader *r, uint32_t max_reads, lime_docs **docs, uint64_t *first_record, bool out_qc)
 {
     const char *who = "lime_seq_reader_next";
     if (!r || !docs) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
@@ -286,9 +293,14 @@ extern "C" int lime_seq_reader_next(lime_seq_reader *r, uint32_t max_reads, lime
     if (r->failed) return fail(r->failed, "%s", r->failure.c_str());
     int rc = check_ctx(r->ctx, who); if (rc) return rc;
     r->asked = true;
-    rc = reader_next(r, who, max_reads, docs, first_record);
+    rc = reader_next(r, who, max_reads, docs, first_record, out_qc);
     if (rc == LIME_ERR_ARG) { r->failed = rc; r->failure = lime_last_error(); }     // a refusal of the file is final
     return rc;
+}
+
+extern "C" int lime_seq_reader_next(lime_seq_reader *r, uint32_t max_reads, lime_docs **docs, uint64_t *first_record)
+{
+    return seq_next(r, max_reads, docs, first_record, true);
 }
 
 extern "C" int lime_seq_reader_set_trim(lime_seq_reader *r, uint32_t q5, uint32_t q3)
@@ -345,6 +357,29 @@ extern "C" int lime_seq_reader_filter_info(const lime_seq_reader *r, lime_filter
     return LIME_OK;
 }
 
+// ---- per-position statistics of the batches as parsed and as handed out (lime_docs_qc_dev) ----
+extern "C" int lime_seq_reader_set_qc(lime_seq_reader *r, uint32_t n_pos)
+{
+    const char *who = "lime_seq_reader_set_qc";
+    if (!r) return fail(LIME_ERR_ARG, "%s: the reader is NULL", who);
+    if (!n_pos || n_pos > LIME_QC_MAX_POS) return fail(LIME_ERR_ARG, "%s: %u positions; there are 1 .. %u", who, n_pos, LIME_QC_MAX_POS);
+    if (r->asked) return fail(LIME_ERR_ARG, "%s: the reader has handed out records already; the statistics are set before the first lime_seq_reader_next", who);
+    r->qc_pos = n_pos;
+    r->qc_raw.assign(LIME_QC_WORDS(n_pos), 0);
+    r->qc_out.assign(LIME_QC_WORDS(n_pos), 0);
+    return LIME_OK;
+}
+
+extern "C" int lime_seq_reader_qc(const lime_seq_reader *r, int which, uint64_t *tables)
+{
+    const char *who = "lime_seq_reader_qc";
+    if (!r || !tables) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
+    if (which != 0 && which != 1) return fail(LIME_ERR_ARG, "%s: tables %d; 0 is the batches as parsed, 1 as handed out", who, which);
+    if (!r->qc_pos) { memset(tables, 0, 8 * LIME_QC_WORDS(1u)); return LIME_OK; }
+    memcpy(tables, (which ? r->qc_out : r->qc_raw).data(), 8 * (size_t)LIME_QC_WORDS(r->qc_pos));
+    return LIME_OK;
+}
+
 // ---- the overlap cut over two readers' batches (lime_docs_trim_overlap_dev): the one stage that needs both mates ----
 extern "C" int lime_seq_reader_set_overlap(lime_seq_reader *r1, lime_seq_reader *r2, uint32_t min_overlap, uint32_t max_err_pct)
 {
@@ -371,8 +406,8 @@ static int next_pair_impl(const char *who, lime_seq_reader *r1, lime_seq_reader 
     DocsPair batch;
     uint64_t first = 0;
     int rc;
-    if ((rc = lime_seq_reader_next(r1, max_reads, &batch.d[0], &first))) return rc;
-    if ((rc = lime_seq_reader_next(r2, max_reads, &batch.d[1], nullptr))) return rc;
+    if ((rc = seq_next(r1, max_reads, &batch.d[0], &first, false))) return rc;      // (the batches are counted behind the cut)
+    if ((rc = seq_next(r2, max_reads, &batch.d[1], nullptr, false))) return rc;
     for (int m = 0; m < 2; ++m) if (batch.d[m]) lime_docs_info(batch.d[m], &got[m], nullptr);
     if (got[0] != got[1]) { *uneven = true; return LIME_OK; }
     if (!got[0]) return LIME_OK;                         // the end of both files
@@ -381,6 +416,14 @@ static int next_pair_impl(const char *who, lime_seq_reader *r1, lime_seq_reader 
     lime_overlap_info_t &s = r1->overlapped;
     s.n_pairs += oi.n_pairs; s.n_overlap += oi.n_overlap; s.n_cut += oi.n_cut; s.symbols_in += oi.symbols_in; s.symbols_out += oi.symbols_out;
     r2->overlapped = s;
+    lime_seq_reader *const rs[2] = {r1, r2};
+    lime_docs **const cut[2] = {docs1, docs2};
+    for (int m = 0; m < 2; ++m)
+        if (rs[m]->qc_pos && (rc = docs_qc_impl(rs[m]->ctx, who, *cut[m], rs[m]->qc_pos, nullptr, rs[m]->qc_out.data()))) {
+            lime_docs_free(*docs1); lime_docs_free(*docs2);
+            *docs1 = *docs2 = nullptr;
+            return rc;
+        }
     if (first_record) *first_record = first;
     return LIME_OK;
 }
