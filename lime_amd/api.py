@@ -1454,6 +1454,9 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
         raise ValueError(f"LiME_fasta: qc_positions is 1 .. {_lib.QC_MAX_POS}")
     formats = [seq_format(r) for r in reads] if qc_report is not None else None
     qc_before, qc_after = [], []
+    # each mate's stages in their one order (the readers': lime_seq_reader in include/lime_hip.h), per stage: set it on the reader of mate k,
+    # run it on the Docs of mate k -> (Docs, info)
+    stages = []
     if trim_qual is not None:
         q5, q3 = _trim_cutoffs(trim_qual)
         if read_len != "auto":
@@ -1461,13 +1464,15 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
         for r in reads:
             if seq_format(r) != "fastq":
                 raise ValueError(f"LiME_fasta: {os.fspath(r)}: trim_qual needs the qualities of a FASTQ file; this one is FASTA")
+        stages.append((lambda m, k: m.set_trim(q5, q3), lambda m, k: ctx.docs_trim(m, q5, q3)))
     if trim_adapter is not None:
         adapters = _adapters(trim_adapter, len(reads))
         if read_len != "auto":
             raise ValueError("LiME_fasta: trim_adapter needs read_len=\"auto\": a fixed norm does not fit trimmed reads")
         if not 1 <= int(adapter_overlap) <= min(len(a) for a in adapters) or not 0 <= int(adapter_error) <= 50:
             raise ValueError("LiME_fasta: adapter_overlap is 1 .. the adapter's length, adapter_error 0 .. 50")
-    flt = None
+        stages.append((lambda m, k: m.set_adapter(adapters[k], adapter_overlap, adapter_error),
+                       lambda m, k: ctx.docs_trim_adapter(m, adapters[k], adapter_overlap, adapter_error)))
     if trim_polyx is not None or max_len or min_len or max_n is not None or min_complexity:
         px, px_min = _polyx_arg(trim_polyx)
         if (px or max_len) and read_len != "auto":
@@ -1475,7 +1480,8 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
         if not 0 <= int(min_complexity) <= 100 or int(max_len) < 0 or int(min_len) < 0 or (max_n is not None and int(max_n) < 0):
             raise ValueError("LiME_fasta: min_complexity is 0 .. 100 percent; max_len, min_len and max_n are not negative")
         flt = dict(polyx=px, polyx_min=px_min, max_len=max_len, min_len=min_len, max_n=max_n, min_complexity=min_complexity)
-    if trim_overlap is not None:
+        stages.append((lambda m, k: m.set_filter(**flt), lambda m, k: ctx.docs_filter(m, **flt)))
+    if trim_overlap is not None:                                    # last: the one stage that needs both mates
         ov = _overlap_arg(trim_overlap)
         if read_len != "auto" or len(reads) != 2:
             raise ValueError("LiME_fasta: trim_overlap needs two reads files and read_len=\"auto\": a fixed norm does not fit trimmed reads")
@@ -1484,42 +1490,23 @@ def lime_fasta(reads, lineage, read_len, output, refs=None, gidx=None, alpha=16,
     ctx = ctx or Context()
     tx = None
     try:
-        if batch_reads:
-            mates = [ctx.seq_reader(r, window_bytes) for r in reads]
-            if trim_qual is not None:
-                for m in mates:
-                    m.set_trim(q5, q3)
-            if qc_report is not None:
-                for m in mates:
-                    m.set_qc(qc_pos)
-        elif trim_qual is not None:
-            mates = []
-            for r in reads:
-                raw = ctx.docs_from_fastq_qual(r)
+        mates = []
+        for k, r in enumerate(reads):
+            if batch_reads:
+                m = ctx.seq_reader(r, window_bytes)
+                for on_reader, _ in stages:
+                    on_reader(m, k)
                 if qc_report is not None:
-                    qc_before.append(ctx.docs_qc(raw, qc_pos))
-                mates.append(ctx.docs_trim(raw, q5, q3)[0])
-                raw.close()
-        elif qc_report is not None:                                 # (a FASTQ file's reads keep their qualities: no later step looks at them)
-            mates = [ctx.docs_from_fastq_qual(r) if f == "fastq" else ctx.docs_from_file(r) for r, f in zip(reads, formats)]
-            qc_before = [ctx.docs_qc(m, qc_pos) for m in mates]
-        else:
-            mates = [ctx.docs_from_file(r) for r in reads]
-        if trim_adapter is not None:
-            for k, m in enumerate(mates):
-                if batch_reads:
-                    m.set_adapter(adapters[k], adapter_overlap, adapter_error)
-                else:
-                    mates[k] = ctx.docs_trim_adapter(m, adapters[k], adapter_overlap, adapter_error)[0]
-                    m.close()
-        if flt is not None:
-            for k, m in enumerate(mates):
-                if batch_reads:
-                    m.set_filter(**flt)
-                else:
-                    mates[k] = ctx.docs_filter(m, **flt)[0]
-                    m.close()
-        if trim_overlap is not None:                                # last: the one stage that needs both mates
+                    m.set_qc(qc_pos)
+            else:   # with the qualities for the quality trim and for the report's quality tables (the reads then keep them: no later step looks at them)
+                m = ctx.docs_from_fastq_qual(r) if trim_qual is not None or (formats and formats[k] == "fastq") else ctx.docs_from_file(r)
+                if qc_report is not None:
+                    qc_before.append(ctx.docs_qc(m, qc_pos))
+                for _, on_docs in stages:
+                    whole, m = m, on_docs(m, k)[0]
+                    whole.close()
+            mates.append(m)
+        if trim_overlap is not None:
             if batch_reads:
                 mates[0].set_overlap(mates[1], *ov)
             else:

@@ -190,78 +190,93 @@ int batch_sink(void *user, uint64_t first_read, const lime_verdict_t *verdicts, 
     s->write_failed = rc != LIME_OK;
     return rc;
 }
-}
 
-int main(int argc, char **argv)
-{
-    CliClock clk;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<const char *> reads;
-    std::vector<const char *> gidx;
+struct StageOptions {                          // the read-preparation stages asked for
+    bool trim = false; unsigned q5 = 0, q3 = 0;                                // --trim-qual
+    std::string adapters[2]; int n_adapters = 0;   // --trim-adapter: [0] for reads_1 (and reads_2 when one is given), [1] for reads_2
+    unsigned ad_overlap = 3, ad_err = 10; bool have_ad_opt = false, cut_adapter = false;
+    lime_filter_t flt = {0, 0, 0, 0, LIME_FILTER_OFF, 0}; bool filter = false; // --trim-polyx, --max-len, --min-len, --max-n, --min-complexity
+    unsigned ov_overlap = 30, ov_err = 10; bool cut_overlap = false;           // --trim-overlap
+    const char *qc_report = nullptr; unsigned qc_pos = 256; bool have_qc_pos = false;      // --qc-report, --qc-positions
+};
+
+struct Options {                               // the command line
+    std::vector<const char *> reads, gidx;
     const char *refs = nullptr, *lineage = nullptr, *output = nullptr;
-    unsigned alpha = 16, rank = 1, trlcp = 0, batch_reads = 0, q5 = 0, q3 = 0;
-    bool trim = false;
-    std::string adapters[2];                   // --trim-adapter: [0] for reads_1 (and reads_2 when one is given), [1] for reads_2
-    int n_adapters = 0;
-    unsigned ad_overlap = 3, ad_err = 10;
-    bool have_ad_opt = false;
-    lime_filter_t flt = {0, 0, 0, 0, LIME_FILTER_OFF, 0};      // --trim-polyx, --max-len, --min-len, --max-n, --min-complexity
-    bool filter = false;
-    unsigned ov_overlap = 30, ov_err = 10;     // --trim-overlap
-    bool cut_overlap = false;
-    const char *qc_report = nullptr;           // --qc-report, --qc-positions
-    unsigned qc_pos = 256;
-    bool have_qc_pos = false;
+    unsigned alpha = 16, rank = 1, trlcp = 0, batch_reads = 0;
     unsigned long long window_bytes = 0;
-    bool batched = false, have_window = false;
+    bool batched = false, len_auto = false;    // --readlen auto: every read by its own length (LIME_NORM_PER_READ)
     float beta = 0.25f;
     unsigned char readLen = 0;                 // dataTypeSim, parsed with %hhu like ClusterBWT_DA (:519-521)
-    bool bad = false, have_len = false, len_auto = false;      // --readlen auto: every read by its own length (LIME_NORM_PER_READ)
+    StageOptions st;
+    int EBWT = env_flag("LIME_EBWT", 1), BIN = env_flag("LIME_BIN", 1), HIGHER = env_flag("LIME_HIGHER", 0);       // the reference's compile-time switches
+    uint32_t norm() const { return len_auto ? LIME_NORM_PER_READ : (uint32_t)(readLen + 1 - alpha); }                // ClusterBWT_DA.cpp:555
+    uint32_t n_mates() const { return (uint32_t)reads.size(); }
+    uint32_t n_shards() const { return refs ? 1u : (uint32_t)gidx.size(); }
+};
+
+// "Error reading FILE: text" and the program's end: with -LIME_ERR_IO where the file could not be read, with 1 for every refusal
+[[noreturn]] void reading_failed(const char *file, int rc, const char *text = lime_last_error())
+{
+    std::cerr << "Error reading " << file << ": " << text << std::endl;
+    exit(rc == LIME_ERR_IO ? -LIME_ERR_IO : 1);
+}
+
+// "Error: text" (or the text alone) and the program's end with 1
+[[noreturn]] void die(const std::string &text, const char *lead = "Error: ") { std::cerr << lead << text << std::endl; exit(1); }
+}
+
+// the command line -> the options; a line that cannot be taken prints the usage and ends the program with 1
+static Options parse_args(int argc, char **argv)
+{
+    Options o;
+    StageOptions &s = o.st;
+    bool bad = false, have_len = false, have_window = false;
     for (int i = 1; i < argc; ++i) {
         const bool more = i + 1 < argc;
-        if (!strcmp(argv[i], "--refs")) { if (more) refs = argv[++i]; else bad = true; }
-        else if (!strcmp(argv[i], "--gidx")) { if (more) gidx.push_back(argv[++i]); else bad = true; }
-        else if (!strcmp(argv[i], "--lineage")) { if (more) lineage = argv[++i]; else bad = true; }
-        else if (!strcmp(argv[i], "--out")) { if (more) output = argv[++i]; else bad = true; }
+        if (!strcmp(argv[i], "--refs")) { if (more) o.refs = argv[++i]; else bad = true; }
+        else if (!strcmp(argv[i], "--gidx")) { if (more) o.gidx.push_back(argv[++i]); else bad = true; }
+        else if (!strcmp(argv[i], "--lineage")) { if (more) o.lineage = argv[++i]; else bad = true; }
+        else if (!strcmp(argv[i], "--out")) { if (more) o.output = argv[++i]; else bad = true; }
         else if (!strcmp(argv[i], "--readlen")) {
-            if (more && !strcmp(argv[i + 1], "auto")) { ++i; have_len = true; len_auto = true; }
-            else if (more && sscanf(argv[i + 1], "%hhu", &readLen) == 1) { ++i; have_len = true; len_auto = false; }
+            if (more && !strcmp(argv[i + 1], "auto")) { ++i; have_len = true; o.len_auto = true; }
+            else if (more && sscanf(argv[i + 1], "%hhu", &o.readLen) == 1) { ++i; have_len = true; o.len_auto = false; }
             else bad = true;
         }
-        else if (!strcmp(argv[i], "--alpha")) { if (more && sscanf(argv[i + 1], "%u", &alpha) == 1) ++i; else bad = true; }
-        else if (!strcmp(argv[i], "--beta")) { if (more && sscanf(argv[i + 1], "%f", &beta) == 1) ++i; else bad = true; }
-        else if (!strcmp(argv[i], "--rank")) { if (more && sscanf(argv[i + 1], "%u", &rank) == 1) ++i; else bad = true; }
-        else if (!strcmp(argv[i], "--trlcp")) { if (more && sscanf(argv[i + 1], "%u", &trlcp) == 1) ++i; else bad = true; }
-        else if (!strcmp(argv[i], "--batch-reads")) { if (more && sscanf(argv[i + 1], "%u", &batch_reads) == 1 && batch_reads) { ++i; batched = true; } else bad = true; }
-        else if (!strcmp(argv[i], "--trim-qual")) { if (more && parse_trim(argv[i + 1], &q5, &q3)) { ++i; trim = true; } else bad = true; }
-        else if (!strcmp(argv[i], "--trim-adapter")) { if (more && parse_adapters(argv[i + 1], adapters, &n_adapters)) ++i; else bad = true; }
-        else if (!strcmp(argv[i], "--adapter-overlap")) { if (more && sscanf(argv[i + 1], "%u", &ad_overlap) == 1 && ad_overlap) { ++i; have_ad_opt = true; } else bad = true; }
-        else if (!strcmp(argv[i], "--adapter-error")) { if (more && sscanf(argv[i + 1], "%u", &ad_err) == 1 && ad_err <= 50) { ++i; have_ad_opt = true; } else bad = true; }
-        else if (!strcmp(argv[i], "--trim-polyx")) { if (more && parse_polyx(argv[i + 1], &flt)) { ++i; filter = true; } else bad = true; }
-        else if (!strcmp(argv[i], "--max-len")) { if (more && parse_u32(argv[i + 1], &flt.max_len) && flt.max_len) { ++i; filter = true; } else bad = true; }
-        else if (!strcmp(argv[i], "--min-len")) { if (more && parse_u32(argv[i + 1], &flt.min_len) && flt.min_len) { ++i; filter = true; } else bad = true; }
-        else if (!strcmp(argv[i], "--max-n")) { if (more && parse_u32(argv[i + 1], &flt.max_n)) { ++i; filter = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--alpha")) { if (more && sscanf(argv[i + 1], "%u", &o.alpha) == 1) ++i; else bad = true; }
+        else if (!strcmp(argv[i], "--beta")) { if (more && sscanf(argv[i + 1], "%f", &o.beta) == 1) ++i; else bad = true; }
+        else if (!strcmp(argv[i], "--rank")) { if (more && sscanf(argv[i + 1], "%u", &o.rank) == 1) ++i; else bad = true; }
+        else if (!strcmp(argv[i], "--trlcp")) { if (more && sscanf(argv[i + 1], "%u", &o.trlcp) == 1) ++i; else bad = true; }
+        else if (!strcmp(argv[i], "--batch-reads")) { if (more && sscanf(argv[i + 1], "%u", &o.batch_reads) == 1 && o.batch_reads) { ++i; o.batched = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--trim-qual")) { if (more && parse_trim(argv[i + 1], &s.q5, &s.q3)) { ++i; s.trim = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--trim-adapter")) { if (more && parse_adapters(argv[i + 1], s.adapters, &s.n_adapters)) ++i; else bad = true; }
+        else if (!strcmp(argv[i], "--adapter-overlap")) { if (more && sscanf(argv[i + 1], "%u", &s.ad_overlap) == 1 && s.ad_overlap) { ++i; s.have_ad_opt = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--adapter-error")) { if (more && sscanf(argv[i + 1], "%u", &s.ad_err) == 1 && s.ad_err <= 50) { ++i; s.have_ad_opt = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--trim-polyx")) { if (more && parse_polyx(argv[i + 1], &s.flt)) { ++i; s.filter = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--max-len")) { if (more && parse_u32(argv[i + 1], &s.flt.max_len) && s.flt.max_len) { ++i; s.filter = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--min-len")) { if (more && parse_u32(argv[i + 1], &s.flt.min_len) && s.flt.min_len) { ++i; s.filter = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--max-n")) { if (more && parse_u32(argv[i + 1], &s.flt.max_n)) { ++i; s.filter = true; } else bad = true; }
         else if (!strcmp(argv[i], "--min-complexity")) {
-            if (more && parse_u32(argv[i + 1], &flt.min_complexity) && flt.min_complexity && flt.min_complexity <= 100) { ++i; filter = true; } else bad = true;
+            if (more && parse_u32(argv[i + 1], &s.flt.min_complexity) && s.flt.min_complexity && s.flt.min_complexity <= 100) { ++i; s.filter = true; } else bad = true;
         }
-        else if (!strcmp(argv[i], "--trim-overlap")) { if (more && parse_overlap(argv[i + 1], &ov_overlap, &ov_err)) { ++i; cut_overlap = true; } else bad = true; }
-        else if (!strcmp(argv[i], "--qc-report")) { if (more) qc_report = argv[++i]; else bad = true; }
-        else if (!strcmp(argv[i], "--qc-positions")) { if (more && parse_u32(argv[i + 1], &qc_pos) && qc_pos && qc_pos <= LIME_QC_MAX_POS) { ++i; have_qc_pos = true; } else bad = true; }
-        else if (!strcmp(argv[i], "--window-bytes")) { if (more && sscanf(argv[i + 1], "%llu", &window_bytes) == 1 && window_bytes) { ++i; have_window = true; } else bad = true; }
-        else reads.push_back(argv[i]);
+        else if (!strcmp(argv[i], "--trim-overlap")) { if (more && parse_overlap(argv[i + 1], &s.ov_overlap, &s.ov_err)) { ++i; s.cut_overlap = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--qc-report")) { if (more) s.qc_report = argv[++i]; else bad = true; }
+        else if (!strcmp(argv[i], "--qc-positions")) { if (more && parse_u32(argv[i + 1], &s.qc_pos) && s.qc_pos && s.qc_pos <= LIME_QC_MAX_POS) { ++i; s.have_qc_pos = true; } else bad = true; }
+        else if (!strcmp(argv[i], "--window-bytes")) { if (more && sscanf(argv[i + 1], "%llu", &o.window_bytes) == 1 && o.window_bytes) { ++i; have_window = true; } else bad = true; }
+        else o.reads.push_back(argv[i]);
     }
-    if (have_window && !batched) bad = true;
-    if (have_qc_pos && !qc_report) bad = true;
-    if (trim && !len_auto) bad = true;             // (a fixed norm on trimmed reads)
-    const bool cut_adapter = n_adapters > 0;
-    if (cut_adapter && !len_auto) bad = true;      // (the same)
-    if (have_ad_opt && !cut_adapter) bad = true;
-    if ((flt.polyx_mask || flt.max_len) && !len_auto) bad = true;          // (the same; the three filters only empty reads)
-    if (cut_overlap && (!len_auto || reads.size() != 2)) bad = true;       // (the same; and a pair is two files)
-    if (n_adapters == 2 && reads.size() != 2) bad = true;
-    for (int k = 0; k < n_adapters; ++k) if (ad_overlap > adapters[k].size()) bad = true;
-    if (n_adapters == 1) adapters[1] = adapters[0];
-    if (reads.empty() || reads.size() > 2 || !refs == gidx.empty() || !lineage || !output || !have_len) bad = true;
+    if (have_window && !o.batched) bad = true;
+    if (s.have_qc_pos && !s.qc_report) bad = true;
+    if (s.trim && !o.len_auto) bad = true;         // (a fixed norm on trimmed reads)
+    s.cut_adapter = s.n_adapters > 0;
+    if (s.cut_adapter && !o.len_auto) bad = true;  // (the same)
+    if (s.have_ad_opt && !s.cut_adapter) bad = true;
+    if ((s.flt.polyx_mask || s.flt.max_len) && !o.len_auto) bad = true;        // (the same; the three filters only empty reads)
+    if (s.cut_overlap && (!o.len_auto || o.reads.size() != 2)) bad = true;     // (the same; and a pair is two files)
+    if (s.n_adapters == 2 && o.reads.size() != 2) bad = true;
+    for (int k = 0; k < s.n_adapters; ++k) if (s.ad_overlap > s.adapters[k].size()) bad = true;
+    if (s.n_adapters == 1) s.adapters[1] = s.adapters[0];
+    if (o.reads.empty() || o.reads.size() > 2 || !o.refs == o.gidx.empty() || !o.lineage || !o.output || !have_len) bad = true;
     if (bad) {
         std::cerr << "Error usage " << argv[0] << " reads_1.fasta [reads_2.fasta] (--refs refs.fasta | --gidx file.gidx [--gidx next.gidx ...]) --lineage LineageFile --readlen (L | auto) --out output\n"
                   << "           [--alpha 16] [--beta 0.25] [--rank 1] [--trlcp k] [--batch-reads N [--window-bytes W]] [--trim-qual (Q | Q5,Q3)]\n"
@@ -303,218 +318,270 @@ int main(int argc, char **argv)
                   << "  LIME_EBWT, LIME_BIN, LIME_HIGHER as for ClusterBWT_DA / Classify." << std::endl;
         exit(1);
     }
-    const int EBWT = env_flag("LIME_EBWT", 1), BIN = env_flag("LIME_BIN", 1), HIGHER = env_flag("LIME_HIGHER", 0);
-    const uint32_t norm = len_auto ? LIME_NORM_PER_READ : (uint32_t)(readLen + 1 - alpha);        // ClusterBWT_DA.cpp:555
-    const uint32_t n_mates = (uint32_t)reads.size();
-    const uint32_t n_shards = refs ? 1u : (uint32_t)gidx.size();
-    if (n_shards > 1) {                        // the shards must agree and the lineage must hold their genomes: known before a device is opened
-        uint64_t total = 0;
-        uint32_t cap0 = 0; uint8_t term0 = 0;
-        for (uint32_t s = 0; s < n_shards; ++s) {
-            uint32_t nd = 0, cap = 0; uint8_t term = 0;
-            if (lime_gindex_probe(gidx[s], &nd, nullptr, &cap, &term) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
-            if (s == 0) { cap0 = cap; term0 = term; }
-            else if (cap != cap0 || term != term0) {
-                std::cerr << "Error: " << gidx[s] << " was built with --trlcp " << cap << " and terminator " << (unsigned)term << ", " << gidx[0] << " with --trlcp "
-                          << cap0 << " and terminator " << (unsigned)term0 << ": the shards of one database are built alike." << std::endl;
-                exit(1);
-            }
-            total += nd;
-        }
-        if (total > 0xFFFFFFFFull) { std::cerr << "Error: the index shards hold " << total << " genomes; ids are 32 bits." << std::endl; exit(1); }
-        lime_taxonomy *probe = nullptr;
-        if (lime_taxonomy_load(lineage, (int)rank, env_flag("LIME_HIGHER", 0), (uint32_t)total, &probe) != LIME_OK) {
-            std::cerr << "Error: " << lineage << " does not describe the " << total << " genomes of the " << n_shards << " index shards: " << lime_classify_error() << std::endl;
-            exit(1);
-        }
-        lime_taxonomy_free(probe);
-    }
+    return o;
+}
 
-    int formats[2] = {0, 0};
+namespace {
+struct StageInfo { lime_trim_info_t trim; lime_filter_info_t filter; };        // a mate stage's counts: the member of its kind
+
+// One stage of one mate, both modes side by side: is it asked for, set it on a reader (--batch-reads), run it on whole documents, its counts
+// from a reader, its line.  THE TABLE'S ORDER IS THE STAGES' ORDER, the one of lime_seq_reader (include/lime_hip.h): a new stage is one entry
+struct MateStage {
+    bool StageOptions::*on;
+    int (*set)(lime_seq_reader *, const StageOptions &, uint32_t m);
+    int (*run)(lime_ctx *, const StageOptions &, uint32_t m, const lime_docs *in, lime_docs **out, StageInfo *);
+    int (*fetch)(const lime_seq_reader *, StageInfo *);
+    void (*print)(const char *file, const StageOptions &, uint32_t m, const StageInfo &);
+};
+const MateStage MATE_STAGES[] = {
+    {   // --trim-qual: the raw reads with their qualities, then the trimmed reads alone
+        &StageOptions::trim,
+        [](lime_seq_reader *r, const StageOptions &s, uint32_t) { return lime_seq_reader_set_trim(r, s.q5, s.q3); },
+        [](lime_ctx *c, const StageOptions &s, uint32_t, const lime_docs *in, lime_docs **out, StageInfo *i) {
+            return lime_docs_trim_dev(c, in, s.q5, s.q3, nullptr, out, &i->trim); },
+        [](const lime_seq_reader *r, StageInfo *i) { return lime_seq_reader_trim_info(r, &i->trim); },
+        [](const char *file, const StageOptions &s, uint32_t, const StageInfo &i) { print_trim(file, s.q5, s.q3, i.trim); } },
+    {   // --trim-adapter: the reads as parsed or as the quality trim left them, cut at their mate's adapter
+        &StageOptions::cut_adapter,
+        [](lime_seq_reader *r, const StageOptions &s, uint32_t m) {
+            return lime_seq_reader_set_adapter(r, (const uint8_t *)s.adapters[m].data(), (uint32_t)s.adapters[m].size(), s.ad_overlap, s.ad_err); },
+        [](lime_ctx *c, const StageOptions &s, uint32_t m, const lime_docs *in, lime_docs **out, StageInfo *i) {
+            return lime_docs_trim_adapter_dev(c, in, (const uint8_t *)s.adapters[m].data(), (uint32_t)s.adapters[m].size(), s.ad_overlap, s.ad_err, nullptr, out, &i->trim); },
+        [](const lime_seq_reader *r, StageInfo *i) { return lime_seq_reader_adapter_info(r, &i->trim); },
+        [](const char *file, const StageOptions &s, uint32_t m, const StageInfo &i) { print_adapter(file, s.adapters[m], s.ad_overlap, s.ad_err, i.trim); } },
+    {   // the read filter: what the trims left, filtered
+        &StageOptions::filter,
+        [](lime_seq_reader *r, const StageOptions &s, uint32_t) { return lime_seq_reader_set_filter(r, &s.flt); },
+        [](lime_ctx *c, const StageOptions &s, uint32_t, const lime_docs *in, lime_docs **out, StageInfo *i) {
+            return lime_docs_filter_dev(c, in, &s.flt, nullptr, out, &i->filter); },
+        [](const lime_seq_reader *r, StageInfo *i) { return lime_seq_reader_filter_info(r, &i->filter); },
+        [](const char *file, const StageOptions &s, uint32_t, const StageInfo &i) { print_filter(file, s.flt, i.filter); } },
+};
+
+struct Sample {                                // the reads: whole documents, or readers with --batch-reads
+    lime_docs *mates[2] = {nullptr, nullptr}; lime_seq_reader *readers[2] = {nullptr, nullptr};
+    int formats[2] = {0, 0}; uint64_t numReads = 0;
     std::vector<uint64_t> qc_before[2], qc_after[2];     // --qc-report: the tables of each reads file
-    for (uint32_t m = 0; m < n_mates && (trim || qc_report); ++m) {      // known before a device is opened, like the shards' headers
-        int &format = formats[m];
-        if (lime_seq_format(reads[m], &format) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return -LIME_ERR_IO; }
-        if (qc_report) { qc_before[m].assign(LIME_QC_WORDS(qc_pos), 0); qc_after[m].assign(LIME_QC_WORDS(qc_pos), 0); }
-        if (trim && format != 1) { std::cerr << "Error reading " << reads[m] << ": --trim-qual needs the qualities of a FASTQ file; this one is FASTA." << std::endl; return 1; }
-    }
+};
 
-    lime_ctx *ctx = nullptr;
-    if (lime_init(pick_device(), &ctx) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(EXIT_FAILURE); }
-    clk.mark("lime_init (HIP runtime)");
-    lime_docs *mates[2] = {nullptr, nullptr};
-    lime_seq_reader *readers[2] = {nullptr, nullptr};
-    uint64_t numReads = 0;
-    for (uint32_t m = 0; m < n_mates && batched; ++m) {
-        const int rc = lime_seq_reader_open(ctx, reads[m], window_bytes, &readers[m]);
-        if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
-        if (trim && lime_seq_reader_set_trim(readers[m], q5, q3) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
-        if (cut_adapter && lime_seq_reader_set_adapter(readers[m], (const uint8_t *)adapters[m].data(), (uint32_t)adapters[m].size(), ad_overlap, ad_err) != LIME_OK) {
-            std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1;
-        }
-        if (filter && lime_seq_reader_set_filter(readers[m], &flt) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
-        if (qc_report && lime_seq_reader_set_qc(readers[m], qc_pos) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
+struct Index { std::vector<lime_gindex *> shards; uint32_t numTarg = 0; lime_taxonomy *tx = nullptr; };    // the genome index, whole or in shards
+}
+
+// the shards must agree and the lineage must hold their genomes: known before a device is opened
+static void probe_shards(const Options &o)
+{
+    uint64_t total = 0;
+    uint32_t cap0 = 0; uint8_t term0 = 0;
+    for (uint32_t s = 0; s < o.n_shards(); ++s) {
+        uint32_t nd = 0, cap = 0; uint8_t term = 0;
+        if (lime_gindex_probe(o.gidx[s], &nd, nullptr, &cap, &term) != LIME_OK) die(lime_last_error());
+        if (s == 0) { cap0 = cap; term0 = term; }
+        else if (cap != cap0 || term != term0)
+            die(std::string(o.gidx[s]) + " was built with --trlcp " + std::to_string(cap) + " and terminator " + std::to_string((unsigned)term) + ", " + o.gidx[0] +
+                " with --trlcp " + std::to_string(cap0) + " and terminator " + std::to_string((unsigned)term0) + ": the shards of one database are built alike.");
+        total += nd;
     }
-    if (batched && cut_overlap && lime_seq_reader_set_overlap(readers[0], readers[1], ov_overlap, ov_err) != LIME_OK) {
-        std::cerr << "Error reading " << reads[0] << ": " << lime_last_error() << std::endl; return 1;
+    if (total > 0xFFFFFFFFull) die("the index shards hold " + std::to_string(total) + " genomes; ids are 32 bits.");
+    lime_taxonomy *probe = nullptr;
+    if (lime_taxonomy_load(o.lineage, (int)o.rank, env_flag("LIME_HIGHER", 0), (uint32_t)total, &probe) != LIME_OK)
+        die(std::string(o.lineage) + " does not describe the " + std::to_string(total) + " genomes of the " + std::to_string(o.n_shards()) + " index shards: " +
+            lime_classify_error());
+    lime_taxonomy_free(probe);
+}
+
+// the reads files' formats, where a stage asks for them: known before a device is opened, like the shards' headers
+static void probe_reads(const Options &o, Sample &sm)
+{
+    const StageOptions &s = o.st;
+    for (uint32_t m = 0; m < o.n_mates() && (s.trim || s.qc_report); ++m) {
+        const int rc = lime_seq_format(o.reads[m], &sm.formats[m]);
+        if (rc != LIME_OK) reading_failed(o.reads[m], rc);
+        if (s.qc_report) { sm.qc_before[m].assign(LIME_QC_WORDS(s.qc_pos), 0); sm.qc_after[m].assign(LIME_QC_WORDS(s.qc_pos), 0); }
+        if (s.trim && sm.formats[m] != 1) reading_failed(o.reads[m], LIME_ERR_ARG, "--trim-qual needs the qualities of a FASTQ file; this one is FASTA.");
     }
-    for (uint32_t m = 0; m < n_mates && !batched; ++m) {
-        int rc;
-        if (trim) {                                // the raw reads with their qualities, then the trimmed reads alone
-            lime_docs *raw = nullptr;
-            lime_trim_info_t ti;
-            if ((rc = lime_docs_from_fastq_qual(ctx, reads[m], &raw)) == LIME_OK) {
-                if (qc_report) rc = lime_docs_qc_dev(ctx, raw, qc_pos, nullptr, qc_before[m].data());
-                if (rc == LIME_OK) rc = lime_docs_trim_dev(ctx, raw, q5, q3, nullptr, &mates[m], &ti);
-                lime_docs_free(raw);
-                if (rc == LIME_OK) print_trim(reads[m], q5, q3, ti);
-            }
-        } else if (qc_report && formats[m] == 1) {  // the report's quality tables: the reads keep their qualities, which no later step looks at
-            if ((rc = lime_docs_from_fastq_qual(ctx, reads[m], &mates[m])) == LIME_OK) rc = lime_docs_qc_dev(ctx, mates[m], qc_pos, nullptr, qc_before[m].data());
-        } else {
-            rc = lime_docs_from_file(ctx, reads[m], &mates[m]);
-            if (rc == LIME_OK && qc_report) rc = lime_docs_qc_dev(ctx, mates[m], qc_pos, nullptr, qc_before[m].data());
-        }
-        if (rc == LIME_OK && cut_adapter) {        // the reads as parsed or as the quality trim left them, then cut at their adapters
-            lime_docs *whole = mates[m];
-            lime_trim_info_t ti;
-            mates[m] = nullptr;
-            rc = lime_docs_trim_adapter_dev(ctx, whole, (const uint8_t *)adapters[m].data(), (uint32_t)adapters[m].size(), ad_overlap, ad_err, nullptr, &mates[m], &ti);
-            lime_docs_free(whole);
-            if (rc == LIME_OK) print_adapter(reads[m], adapters[m], ad_overlap, ad_err, ti);
-        }
-        if (rc == LIME_OK && filter) {             // what the trims left, filtered
-            lime_docs *whole = mates[m];
-            lime_filter_info_t fi;
-            mates[m] = nullptr;
-            rc = lime_docs_filter_dev(ctx, whole, &flt, nullptr, &mates[m], &fi);
-            lime_docs_free(whole);
-            if (rc == LIME_OK) print_filter(reads[m], flt, fi);
-        }
-        if (rc != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
+}
+
+// --batch-reads: a reader per reads file with every stage set on it, in the table's order; the pair's overlap cut last
+static void open_readers(lime_ctx *ctx, const Options &o, Sample &sm)
+{
+    const StageOptions &s = o.st;
+    for (uint32_t m = 0; m < o.n_mates(); ++m) {
+        int rc = lime_seq_reader_open(ctx, o.reads[m], o.window_bytes, &sm.readers[m]);
+        for (const MateStage &stage : MATE_STAGES)
+            if (rc == LIME_OK && (s.*stage.on)) rc = stage.set(sm.readers[m], s, m);
+        if (rc == LIME_OK && s.qc_report) rc = lime_seq_reader_set_qc(sm.readers[m], s.qc_pos);
+        if (rc != LIME_OK) reading_failed(o.reads[m], rc);
     }
-    if (!batched && cut_overlap) {                 // last: what each mate's stages left, cut at the mates' overlap
-        lime_docs *whole[2] = {mates[0], mates[1]};
+    if (s.cut_overlap) {
+        const int rc = lime_seq_reader_set_overlap(sm.readers[0], sm.readers[1], s.ov_overlap, s.ov_err);
+        if (rc != LIME_OK) reading_failed(o.reads[0], rc);
+    }
+}
+
+// the whole files: parsed, counted as parsed, each mate's stages in the table's order with a line each, the overlap cut last, counted again
+static void read_whole(lime_ctx *ctx, const Options &o, Sample &sm)
+{
+    const StageOptions &s = o.st;
+    for (uint32_t m = 0; m < o.n_mates(); ++m) {
+        lime_docs *&d = sm.mates[m];
+        // with the qualities for the quality trim and for the report's quality tables (the reads then keep them: no later step looks at them)
+        int rc = s.trim || (s.qc_report && sm.formats[m] == 1) ? lime_docs_from_fastq_qual(ctx, o.reads[m], &d) : lime_docs_from_file(ctx, o.reads[m], &d);
+        if (rc == LIME_OK && s.qc_report) rc = lime_docs_qc_dev(ctx, d, s.qc_pos, nullptr, sm.qc_before[m].data());
+        for (const MateStage &stage : MATE_STAGES) {
+            if (rc != LIME_OK || !(s.*stage.on)) continue;
+            lime_docs *in = d;
+            StageInfo info;
+            d = nullptr;
+            rc = stage.run(ctx, s, m, in, &d, &info);
+            lime_docs_free(in);
+            if (rc == LIME_OK) stage.print(o.reads[m], s, m, info);
+        }
+        if (rc != LIME_OK) reading_failed(o.reads[m], rc);
+    }
+    if (s.cut_overlap) {
+        lime_docs *whole[2] = {sm.mates[0], sm.mates[1]};
         lime_overlap_info_t oi;
-        mates[0] = mates[1] = nullptr;
-        const int rc = lime_docs_trim_overlap_dev(ctx, whole[0], whole[1], ov_overlap, ov_err, nullptr, nullptr, &mates[0], &mates[1], &oi);
+        sm.mates[0] = sm.mates[1] = nullptr;
+        const int rc = lime_docs_trim_overlap_dev(ctx, whole[0], whole[1], s.ov_overlap, s.ov_err, nullptr, nullptr, &sm.mates[0], &sm.mates[1], &oi);
         lime_docs_free(whole[0]); lime_docs_free(whole[1]);
-        if (rc != LIME_OK) { std::cerr << "Error reading " << reads[0] << ": " << lime_last_error() << std::endl; return 1; }
-        print_overlap(reads[0], reads[1], ov_overlap, ov_err, oi);
+        if (rc != LIME_OK) reading_failed(o.reads[0], rc);
+        print_overlap(o.reads[0], o.reads[1], s.ov_overlap, s.ov_err, oi);
     }
-    for (uint32_t m = 0; m < n_mates && !batched && qc_report; ++m)     // the reads as they enter classification
-        if (lime_docs_qc_dev(ctx, mates[m], qc_pos, nullptr, qc_after[m].data()) != LIME_OK) { std::cerr << "Error reading " << reads[m] << ": " << lime_last_error() << std::endl; return 1; }
-    if (!batched) { uint32_t nd = 0; lime_docs_info(mates[0], &nd, nullptr); numReads = nd; }
-    clk.mark(batched ? "readers" : "reads (parsed on the device)");
+    for (uint32_t m = 0; m < o.n_mates() && s.qc_report; ++m) {
+        const int rc = lime_docs_qc_dev(ctx, sm.mates[m], s.qc_pos, nullptr, sm.qc_after[m].data());
+        if (rc != LIME_OK) reading_failed(o.reads[m], rc);
+    }
+    uint32_t nd = 0;
+    lime_docs_info(sm.mates[0], &nd, nullptr);
+    sm.numReads = nd;
+}
+
+// the genome index: built from --refs in the process, or every --gidx loaded
+static void load_index(lime_ctx *ctx, const Options &o, Index &ix)
+{
     lime_gindex *gi = nullptr;
-    std::vector<lime_gindex *> shards;
-    if (refs) {
+    if (o.refs) {
         lime_docs *g = nullptr;
-        const int rc = lime_docs_from_fasta(ctx, refs, &g);
-        if (rc != LIME_OK) { std::cerr << "Error reading " << refs << ": " << lime_last_error() << std::endl; return rc == LIME_ERR_IO ? -LIME_ERR_IO : 1; }
+        const int rc = lime_docs_from_fasta(ctx, o.refs, &g);
+        if (rc != LIME_OK) reading_failed(o.refs, rc);
         uint32_t nd = 0; uint64_t nt = 0;
         const uint8_t *d_text = nullptr; const uint64_t *d_off = nullptr;
         lime_docs_info(g, &nd, &nt);
         lime_docs_device(g, &d_text, &d_off);
-        if (lime_gindex_build_dev(ctx, d_text, d_off, nd, nt, 0, trlcp, nullptr, &gi) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
+        if (lime_gindex_build_dev(ctx, d_text, d_off, nd, nt, 0, o.trlcp, nullptr, &gi) != LIME_OK) die(lime_last_error());
         lime_docs_free(g);
+        ix.shards.push_back(gi);
     } else {
-        for (uint32_t s = 0; s < n_shards; ++s) {
-            if (lime_gindex_load(ctx, gidx[s], &gi) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
-            shards.push_back(gi);
+        for (const char *file : o.gidx) {
+            if (lime_gindex_load(ctx, file, &gi) != LIME_OK) die(lime_last_error());
+            ix.shards.push_back(gi);
         }
-        gi = shards[0];
     }
-    if (shards.empty()) shards.push_back(gi);
-    uint32_t numTarg = 0;
-    for (lime_gindex *x : shards) { uint32_t nd = 0; lime_gindex_info(x, &nd, nullptr, nullptr, nullptr); numTarg += nd; }
-    clk.mark("genome index");
-    if (batched) std::cout << "numGenomes: " << numTarg << std::endl;        // (numReads is known after the last batch)
-    else std::cout << "numReads: " << numReads << "\nnumGenomes: " << numTarg << std::endl;
+    for (lime_gindex *x : ix.shards) { uint32_t nd = 0; lime_gindex_info(x, &nd, nullptr, nullptr, nullptr); ix.numTarg += nd; }
+}
 
-    lime_taxonomy *tx = nullptr;
-    std::cout << "Reading " << lineage << std::endl;
-    if (lime_taxonomy_load(lineage, (int)rank, HIGHER, numTarg, &tx) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
-    uint64_t counts[4] = {0, 0, 0, 0};
-    if (batched) {
-        BatchSink sink;
-        sink.n_coll = 2 * n_mates; sink.n_shards = n_shards;
-        if (lime_classification_writer_open(output, &sink.w) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
-        std::cerr << "Start comparing..." << std::endl;
-        uint64_t n_batches = 0;
-        const int rc = n_shards == 1 ? lime_classify_sample_stream(ctx, n_mates, readers, gi, tx, alpha, norm, beta, EBWT, BIN, refs ? 0 : trlcp, batch_reads, batch_sink,
-                                                                   &sink, counts, &numReads, &n_batches, nullptr)
-                                     : lime_classify_sample_stream_shards(ctx, n_mates, readers, n_shards, shards.data(), tx, alpha, norm, beta, EBWT, BIN, trlcp,
-                                                                          batch_reads, batch_sink, &sink, counts, &numReads, &n_batches, nullptr);
-        if (rc != LIME_OK) {
-            std::cerr << "Error: " << (sink.write_failed ? lime_classify_error() : lime_last_error()) << std::endl;
-            lime_classification_writer_close(sink.w, 0);
-            lime_shutdown(ctx);
-            return 1;
-        }
-        std::cout << "numReads: " << numReads << " (" << n_batches << " batches of at most " << batch_reads << ")" << std::endl;
-        for (uint32_t k = 0; k < 2 * n_mates; ++k)
-            std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << sink.n_clusters[k] << " clusters summed over the batches"
-                      << (n_shards > 1 ? " and shards" : "") << ", maximum length " << sink.max_len[k] << " in a batch" << (n_shards > 1 ? " and shard" : "") << "." << std::endl;
-        for (uint32_t m = 0; m < n_mates && trim; ++m) {
-            lime_trim_info_t ti;
-            lime_seq_reader_trim_info(readers[m], &ti);
-            print_trim(reads[m], q5, q3, ti);
-        }
-        for (uint32_t m = 0; m < n_mates && cut_adapter; ++m) {
-            lime_trim_info_t ti;
-            lime_seq_reader_adapter_info(readers[m], &ti);
-            print_adapter(reads[m], adapters[m], ad_overlap, ad_err, ti);
-        }
-        for (uint32_t m = 0; m < n_mates && filter; ++m) {
-            lime_filter_info_t fi;
-            lime_seq_reader_filter_info(readers[m], &fi);
-            print_filter(reads[m], flt, fi);
-        }
-        if (cut_overlap) {
-            lime_overlap_info_t oi;
-            lime_seq_reader_overlap_info(readers[0], &oi);
-            print_overlap(reads[0], reads[1], ov_overlap, ov_err, oi);
-        }
-        for (uint32_t m = 0; m < n_mates && qc_report; ++m) {
-            lime_seq_reader_qc(readers[m], 0, qc_before[m].data());
-            lime_seq_reader_qc(readers[m], 1, qc_after[m].data());
-        }
-        clk.mark("batches: reads, collections, classification");
-        if (lime_classification_writer_close(sink.w, 1) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
-        clk.mark("output file");
-    } else {
-        std::vector<lime_verdict_t> verdicts(numReads ? numReads : 1);
-        std::vector<lime_stats_t> stats((size_t)n_shards * 4);
-        std::cerr << "Start comparing..." << std::endl;
-        const int rc = n_shards == 1 ? lime_classify_sample_dev(ctx, n_mates, mates, gi, tx, alpha, norm, beta, EBWT, BIN, refs ? 0 : trlcp, verdicts.data(), counts,
-                                                                stats.data(), nullptr)
-                                     : lime_classify_sample_shards_dev(ctx, n_mates, mates, n_shards, shards.data(), tx, alpha, norm, beta, EBWT, BIN, trlcp, verdicts.data(),
-                                                                       counts, stats.data(), nullptr);
-        if (rc != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
-        for (uint32_t k = 0; k < 2 * n_mates; ++k) {
-            uint64_t nc = 0, ml = 0;
-            for (uint32_t s = 0; s < n_shards; ++s) { const lime_stats_t &x = stats[(size_t)s * 2 * n_mates + k]; nc += x.n_clusters; if (x.max_len > ml) ml = x.max_len; }
-            if (n_shards == 1)
-                std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << nc << " clusters, maximum length " << ml << "." << std::endl;
-            else
-                std::cout << reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << nc << " clusters summed over the shards, maximum length " << ml
-                          << " in a shard." << std::endl;
-        }
-        clk.mark("collections, classification");
-        if (lime_write_classification(output, verdicts.data(), (uint32_t)numReads) != LIME_OK) { std::cerr << lime_classify_error() << std::endl; exit(1); }
-        clk.mark("output file");
+// --batch-reads: the sample batch by batch into the output file, then the collections' lines, each stage's line for every mate, the pair's
+static void classify_batched(lime_ctx *ctx, const Options &o, const Index &ix, Sample &sm, uint64_t counts[4], CliClock &clk)
+{
+    const StageOptions &s = o.st;
+    const uint32_t n_mates = o.n_mates(), n_shards = o.n_shards();
+    BatchSink sink;
+    sink.n_coll = 2 * n_mates; sink.n_shards = n_shards;
+    if (lime_classification_writer_open(o.output, &sink.w) != LIME_OK) die(lime_classify_error(), "");
+    std::cerr << "Start comparing..." << std::endl;
+    uint64_t n_batches = 0;
+    const int rc = n_shards == 1 ? lime_classify_sample_stream(ctx, n_mates, sm.readers, ix.shards[0], ix.tx, o.alpha, o.norm(), o.beta, o.EBWT, o.BIN, o.refs ? 0 : o.trlcp,
+                                                               o.batch_reads, batch_sink, &sink, counts, &sm.numReads, &n_batches, nullptr)
+                                 : lime_classify_sample_stream_shards(ctx, n_mates, sm.readers, n_shards, ix.shards.data(), ix.tx, o.alpha, o.norm(), o.beta, o.EBWT, o.BIN,
+                                                                      o.trlcp, o.batch_reads, batch_sink, &sink, counts, &sm.numReads, &n_batches, nullptr);
+    if (rc != LIME_OK) {
+        std::cerr << "Error: " << (sink.write_failed ? lime_classify_error() : lime_last_error()) << std::endl;
+        lime_classification_writer_close(sink.w, 0);
+        lime_shutdown(ctx);
+        exit(1);
     }
-    if (qc_report) {
-        const uint64_t *before[2] = {qc_before[0].data(), qc_before[1].data()}, *after[2] = {qc_after[0].data(), qc_after[1].data()};
-        if (lime_qc_report_write(qc_report, n_mates, reads.data(), formats, qc_pos, before, after) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(1); }
-        std::cout << "Read statistics (" << qc_pos << " positions, before and after the stages): " << qc_report << std::endl;
+    std::cout << "numReads: " << sm.numReads << " (" << n_batches << " batches of at most " << o.batch_reads << ")" << std::endl;
+    for (uint32_t k = 0; k < 2 * n_mates; ++k)
+        std::cout << o.reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << sink.n_clusters[k] << " clusters summed over the batches"
+                  << (n_shards > 1 ? " and shards" : "") << ", maximum length " << sink.max_len[k] << " in a batch" << (n_shards > 1 ? " and shard" : "") << "." << std::endl;
+    for (const MateStage &stage : MATE_STAGES)
+        for (uint32_t m = 0; m < n_mates && (s.*stage.on); ++m) {
+            StageInfo info;
+            stage.fetch(sm.readers[m], &info);
+            stage.print(o.reads[m], s, m, info);
+        }
+    if (s.cut_overlap) {
+        lime_overlap_info_t oi;
+        lime_seq_reader_overlap_info(sm.readers[0], &oi);
+        print_overlap(o.reads[0], o.reads[1], s.ov_overlap, s.ov_err, oi);
+    }
+    for (uint32_t m = 0; m < n_mates && s.qc_report; ++m) {
+        lime_seq_reader_qc(sm.readers[m], 0, sm.qc_before[m].data());
+        lime_seq_reader_qc(sm.readers[m], 1, sm.qc_after[m].data());
+    }
+    clk.mark("batches: reads, collections, classification");
+    if (lime_classification_writer_close(sink.w, 1) != LIME_OK) die(lime_classify_error(), "");
+    clk.mark("output file");
+}
+
+// the whole sample in one call, the collections' lines, the output file
+static void classify_whole(lime_ctx *ctx, const Options &o, const Index &ix, const Sample &sm, uint64_t counts[4], CliClock &clk)
+{
+    const uint32_t n_mates = o.n_mates(), n_shards = o.n_shards();
+    std::vector<lime_verdict_t> verdicts(sm.numReads ? sm.numReads : 1);
+    std::vector<lime_stats_t> stats((size_t)n_shards * 4);
+    std::cerr << "Start comparing..." << std::endl;
+    const int rc = n_shards == 1 ? lime_classify_sample_dev(ctx, n_mates, sm.mates, ix.shards[0], ix.tx, o.alpha, o.norm(), o.beta, o.EBWT, o.BIN, o.refs ? 0 : o.trlcp,
+                                                            verdicts.data(), counts, stats.data(), nullptr)
+                                 : lime_classify_sample_shards_dev(ctx, n_mates, sm.mates, n_shards, ix.shards.data(), ix.tx, o.alpha, o.norm(), o.beta, o.EBWT, o.BIN, o.trlcp,
+                                                                   verdicts.data(), counts, stats.data(), nullptr);
+    if (rc != LIME_OK) die(lime_last_error());
+    for (uint32_t k = 0; k < 2 * n_mates; ++k) {
+        uint64_t nc = 0, ml = 0;
+        for (uint32_t s = 0; s < n_shards; ++s) { const lime_stats_t &x = stats[(size_t)s * 2 * n_mates + k]; nc += x.n_clusters; if (x.max_len > ml) ml = x.max_len; }
+        std::cout << o.reads[k >> 1] << (k & 1u ? " (reverse complements)" : "") << ": " << nc << (n_shards == 1 ? " clusters" : " clusters summed over the shards")
+                  << ", maximum length " << ml << (n_shards == 1 ? "." : " in a shard.") << std::endl;
+    }
+    clk.mark("collections, classification");
+    if (lime_write_classification(o.output, verdicts.data(), (uint32_t)sm.numReads) != LIME_OK) die(lime_classify_error(), "");
+    clk.mark("output file");
+}
+
+int main(int argc, char **argv)
+{
+    CliClock clk;
+    const auto t0 = std::chrono::steady_clock::now();
+    const Options o = parse_args(argc, argv);
+    const StageOptions &s = o.st;
+    if (o.n_shards() > 1) probe_shards(o);
+    Sample sm;
+    probe_reads(o, sm);
+    lime_ctx *ctx = nullptr;
+    if (lime_init(pick_device(), &ctx) != LIME_OK) { std::cerr << "Error: " << lime_last_error() << std::endl; exit(EXIT_FAILURE); }
+    clk.mark("lime_init (HIP runtime)");
+    if (o.batched) open_readers(ctx, o, sm);
+    else read_whole(ctx, o, sm);
+    clk.mark(o.batched ? "readers" : "reads (parsed on the device)");
+    Index ix;
+    load_index(ctx, o, ix);
+    clk.mark("genome index");
+    if (o.batched) std::cout << "numGenomes: " << ix.numTarg << std::endl;        // (numReads is known after the last batch)
+    else std::cout << "numReads: " << sm.numReads << "\nnumGenomes: " << ix.numTarg << std::endl;
+    std::cout << "Reading " << o.lineage << std::endl;
+    if (lime_taxonomy_load(o.lineage, (int)o.rank, o.HIGHER, ix.numTarg, &ix.tx) != LIME_OK) die(lime_classify_error(), "");
+    uint64_t counts[4] = {0, 0, 0, 0};
+    if (o.batched) classify_batched(ctx, o, ix, sm, counts, clk);
+    else classify_whole(ctx, o, ix, sm, counts, clk);
+    if (s.qc_report) {
+        const uint64_t *before[2] = {sm.qc_before[0].data(), sm.qc_before[1].data()}, *after[2] = {sm.qc_after[0].data(), sm.qc_after[1].data()};
+        if (lime_qc_report_write(s.qc_report, o.n_mates(), o.reads.data(), sm.formats, s.qc_pos, before, after) != LIME_OK) die(lime_last_error());
+        std::cout << "Read statistics (" << s.qc_pos << " positions, before and after the stages): " << s.qc_report << std::endl;
     }
     lime_shutdown(ctx);
-    lime_taxonomy_free(tx);
-    std::cout << "Classification process at level " << rank << " completed.\nNumber of successfully classified reads: "
-              << counts[0] << "/" << numReads << ";" << std::endl;
-    if (HIGHER) std::cout << "\tClassified at higher taxonomic ranks: " << counts[3] << "." << std::endl;
+    lime_taxonomy_free(ix.tx);
+    std::cout << "Classification process at level " << o.rank << " completed.\nNumber of successfully classified reads: "
+              << counts[0] << "/" << sm.numReads << ";" << std::endl;
+    if (o.HIGHER) std::cout << "\tClassified at higher taxonomic ranks: " << counts[3] << "." << std::endl;
     std::cout << "\tAmbiguously classified reads: " << counts[2] << "." << std::endl;
     std::cout << "\tNot classified reads: " << counts[1] << "." << std::endl;
     fprintf(stdout, "Time: %.6lf\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());

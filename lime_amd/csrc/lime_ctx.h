@@ -93,6 +93,34 @@ template <typename T> struct DevWords {
     ~DevWords() { if (p) dev_release(p); }
     int alloc(size_t bytes) { HIP_TRY(hipMalloc(&p, bytes)); return LIME_OK; }
 };
+
+// One mate's read-preparation stages (lime_docs.cpp: docs_stages runs them, in its one order): what the lime_seq_reader_set_* calls asked
+// for, each stage's counts summed over the batches handed out, and the statistics of the batches as parsed and as handed out
+struct MateStages {
+    bool trim = false; uint32_t q5 = 0, q3 = 0;            // lime_seq_reader_set_trim
+    bool adapter = false; uint64_t ad_masks[4] = {0, 0, 0, 0}; uint32_t ad_m = 0, ad_overlap = 0, ad_err = 0;     // lime_seq_reader_set_adapter
+    bool filter = false; lime_filter_t fl = {0, 0, 0, 0, LIME_FILTER_OFF, 0};      // lime_seq_reader_set_filter
+    uint32_t n_pos = 0;                                    // lime_seq_reader_set_qc; 0 without
+    lime_trim_info_t trimmed = {0, 0, 0, 0, 0}, ad_trimmed = {0, 0, 0, 0, 0};
+    lime_filter_info_t filtered = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<uint64_t> qc_raw, qc_out;
+    bool needs_qual() const { return trim || n_pos; }      // does any stage read the qualities of a FASTQ batch?
+};
+
+// a stage's counts for one batch added to the sum over the batches
+inline void add_info(lime_trim_info_t &s, const lime_trim_info_t &x)
+{
+    s.n_reads += x.n_reads; s.n_changed += x.n_changed; s.n_empty += x.n_empty; s.symbols_in += x.symbols_in; s.symbols_out += x.symbols_out;
+}
+inline void add_info(lime_filter_info_t &s, const lime_filter_info_t &x)
+{
+    s.n_reads += x.n_reads; s.n_polyx += x.n_polyx; s.n_capped += x.n_capped; s.n_short += x.n_short; s.n_many_n += x.n_many_n;
+    s.n_low_complexity += x.n_low_complexity; s.symbols_in += x.symbols_in; s.symbols_out += x.symbols_out;
+}
+inline void add_info(lime_overlap_info_t &s, const lime_overlap_info_t &x)
+{
+    s.n_pairs += x.n_pairs; s.n_overlap += x.n_overlap; s.n_cut += x.n_cut; s.symbols_in += x.symbols_in; s.symbols_out += x.symbols_out;
+}
 }
 
 struct __attribute__((visibility("hidden"))) lime_ctx {              // (hidden: its implicit destructor is no export of the library)
@@ -239,16 +267,9 @@ struct __attribute__((visibility("hidden"))) lime_seq_reader {
     uint64_t n_records = 0, n_lines = 0, n_bytes = 0;      // handed out so far
     int failed = 0; std::string failure;    // a refusal is final: later calls repeat it
     bool asked = false;                     // lime_seq_reader_next has been called
-    bool trim = false; uint32_t q5 = 0, q3 = 0;            // lime_seq_reader_set_trim: every batch is parsed with its qualities and trimmed
-    lime_trim_info_t trimmed = {0, 0, 0, 0, 0};            // summed over the batches handed out
-    bool adapter = false; uint64_t ad_masks[4] = {0, 0, 0, 0}; uint32_t ad_m = 0, ad_overlap = 0, ad_err = 0;     // lime_seq_reader_set_adapter: every
-    lime_trim_info_t ad_trimmed = {0, 0, 0, 0, 0};         // batch is cut at its reads' adapters (behind the quality trim, where both are set)
-    bool filter = false; lime_filter_t fl = {0, 0, 0, 0, LIME_FILTER_OFF, 0};      // lime_seq_reader_set_filter: every batch is filtered, behind the trims
-    lime_filter_info_t filtered = {0, 0, 0, 0, 0, 0, 0, 0};
+    lime_host::MateStages stages;           // what every batch goes through before it is handed out
     lime_seq_reader *mate = nullptr; uint32_t ov_overlap = 0, ov_err = 0;       // lime_seq_reader_set_overlap: the other mate's reader; next_pair cuts
     lime_overlap_info_t overlapped = {0, 0, 0, 0, 0};      // every batch of the two at the mates' overlap, last (the sums: kept in both readers)
-    uint32_t qc_pos = 0;                    // lime_seq_reader_set_qc: n_pos, 0 without; the tables of the batches as parsed and as handed out
-    std::vector<uint64_t> qc_raw, qc_out;
     ~lime_seq_reader();
 };
 
@@ -315,24 +336,19 @@ int build_index_impl(lime_ctx *c, const char *who, const uint8_t *d_text, const 
 int docs_parse_fasta_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, hipStream_t st, lime_docs **out);
 int docs_parse_fastq_dev(lime_ctx *c, const char *who, const uint8_t *d_bytes, uint64_t n, uint64_t line_base, hipStream_t st, lime_docs **out,
                          bool with_qual = false);
-// lime_docs.cpp: lime_docs_trim_dev without its argument checks
-int docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t q5, uint32_t q3, hipStream_t st, lime_docs **out, lime_trim_info_t *info);
-// lime_docs.cpp: the adapter's refusals (LIME_ERR_ARG with a text) and its four masks, bit j of masks[b] set where symbol j is "ACGT"[b];
-// lime_docs_trim_adapter_dev without its argument checks
+// lime_docs.cpp: the adapter's refusals (LIME_ERR_ARG with a text) and its four masks, bit j of masks[b] set where symbol j is "ACGT"[b]
 int adapter_masks(const char *who, const uint8_t *adapter, uint32_t m, uint32_t min_overlap, uint32_t max_err_pct, uint64_t masks[4]);
-int docs_adapter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const uint64_t masks[4], uint32_t m, uint32_t min_overlap, uint32_t max_err_pct,
-                      hipStream_t st, lime_docs **out, lime_trim_info_t *info);
-// lime_host.cpp: the filter's refusals of its parameters (LIME_ERR_ARG with a text); lime_docs.cpp: lime_docs_filter_dev without its
-// argument checks
+// lime_host.cpp: the filter's refusals of its parameters (LIME_ERR_ARG with a text)
 int filter_check(const char *who, const lime_filter_t *f);
-int docs_filter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const lime_filter_t *f, hipStream_t st, lime_docs **out, lime_filter_info_t *info);
-// lime_docs.cpp: lime_docs_qc_dev without its argument checks
-int docs_qc_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t n_pos, hipStream_t st, uint64_t *tables);
 // lime_host.cpp: the overlap cut's refusals of its parameters (LIME_ERR_ARG with a text); lime_docs.cpp: lime_docs_trim_overlap_dev without
 // its argument checks
 int overlap_check(const char *who, uint32_t min_overlap, uint32_t max_err_pct);
 int docs_overlap_impl(lime_ctx *c, const char *who, const lime_docs *docs1, const lime_docs *docs2, uint32_t min_overlap, uint32_t max_err_pct,
                       uint32_t *d_insert, hipStream_t st, lime_docs **out1, lime_docs **out2, lime_overlap_info_t *info);
+// lime_docs.cpp: one mate's stages on a batch as parsed (*docs is replaced by what they leave; NULL and nothing allocated on an error), and
+// a batch as it is handed out added to the mate's OUT tables (on an error the batch, and the pair's other batch if given, are freed and NULL)
+int docs_stages(lime_ctx *c, const char *who, MateStages &s, lime_docs **docs);
+int docs_count_out(lime_ctx *c, const char *who, MateStages &s, lime_docs **batch, lime_docs **other = nullptr);
 // lime_docs.cpp: the genome side's refusals of the sample calls, with one index or with shards (the read sets' own come between the two)
 int sample_check_shards(const char *who, lime_ctx *c, uint32_t n_shards, const lime_gindex *const *shards);
 int sample_check_rules(const char *who, uint32_t n_shards, const lime_gindex *const *shards, const lime_taxonomy *tx, uint32_t alpha,

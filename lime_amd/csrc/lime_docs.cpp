@@ -435,8 +435,8 @@ static int trim_finish(lime_ctx *c, const char *who, const lime_docs *docs, Trim
     return LIME_OK;
 }
 
-int lime_host::docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t q5, uint32_t q3, hipStream_t st, lime_docs **out,
-                              lime_trim_info_t *info)
+// lime_docs_trim_dev without its argument checks (the three stages' impl functions are called by their public wrappers and by docs_stages)
+static int docs_trim_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t q5, uint32_t q3, hipStream_t st, lime_docs **out, lime_trim_info_t *info)
 {
     const uint32_t nd = docs->n_docs;
     TrimScratch ts;
@@ -463,8 +463,8 @@ int lime_host::adapter_masks(const char *who, const uint8_t *adapter, uint32_t m
     return LIME_OK;
 }
 
-int lime_host::docs_adapter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const uint64_t masks[4], uint32_t m, uint32_t min_overlap,
-                                 uint32_t max_err_pct, hipStream_t st, lime_docs **out, lime_trim_info_t *info)
+static int docs_adapter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const uint64_t masks[4], uint32_t m, uint32_t min_overlap,
+                             uint32_t max_err_pct, hipStream_t st, lime_docs **out, lime_trim_info_t *info)
 {
     const uint32_t nd = docs->n_docs;
     TrimScratch ts;
@@ -490,8 +490,7 @@ extern "C" int lime_docs_trim_adapter_dev(lime_ctx *c, const lime_docs *docs, co
 }
 
 // ---- the read filter (lime_filter_kernel.hip: k_filter_bounds), through the trims' prefix sum and copy ----
-int lime_host::docs_filter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const lime_filter_t *f, hipStream_t st, lime_docs **out,
-                                lime_filter_info_t *info)
+static int docs_filter_impl(lime_ctx *c, const char *who, const lime_docs *docs, const lime_filter_t *f, hipStream_t st, lime_docs **out, lime_filter_info_t *info)
 {
     const uint32_t nd = docs->n_docs;
     TrimScratch ts;
@@ -520,7 +519,7 @@ extern "C" int lime_docs_filter_dev(lime_ctx *c, const lime_docs *docs, const li
 }
 
 // ---- per-position statistics (lime_qc_kernel.hip: k_qc_reads): the tables cleared on the device, the kernel, the copy back, the sum ----
-int lime_host::docs_qc_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t n_pos, hipStream_t st, uint64_t *tables)
+static int docs_qc_impl(lime_ctx *c, const char *who, const lime_docs *docs, uint32_t n_pos, hipStream_t st, uint64_t *tables)
 {
     (void)c;
     const uint32_t nd = docs->n_docs;
@@ -601,6 +600,54 @@ extern "C" int lime_docs_trim_dev(lime_ctx *c, const lime_docs *docs, uint32_t q
     if (!docs->qual.p) return fail(LIME_ERR_ARG, "%s: the documents hold no qualities (lime_docs_from_fastq_qual* keeps them)", who);
     int rc = check_ctx(c, who); if (rc) return rc;
     return docs_trim_impl(c, who, docs, q5, q3, (hipStream_t)stream, out, info);
+}
+
+// ---- one mate's stages, in their one order (lime_reader.cpp runs every batch through this) ----
+// The documents replaced by a stage's output and the stage's counts added to their sum; the input goes back either way (NULL behind a failure)
+template <typename Info, typename Stage> static int through(lime_docs *&d, Info &sum, Stage stage)
+{
+    lime_docs *next = nullptr;
+    Info info;
+    const int rc = stage(d, &next, &info);
+    lime_docs_free(d);
+    d = next;
+    if (!rc) add_info(sum, info);
+    return rc;
+}
+
+// THE ORDER OF A MATE'S STAGES.  A batch as parsed (with its qualities where s.needs_qual()) becomes the batch as it is handed out:
+//   1. the `before` tables (s.n_pos): the batch as parsed; qualities that were parsed for the tables alone go back here
+//   2. the quality trim (s.trim): its output holds no qualities
+//   3. the adapter trim (s.adapter): second, as an outside trimmer does it
+//   4. the read filter (s.filter): what the trims left
+// The overlap cut comes behind this, on the pair (next_pair_impl), and the `after` tables behind that (docs_count_out).  Every stage costs
+// what its public call costs: no stage is fused with its neighbour and no bounds are composed to save a copy.
+int lime_host::docs_stages(lime_ctx *c, const char *who, MateStages &s, lime_docs **docs)
+{
+    lime_docs *d = *docs;
+    *docs = nullptr;
+    int rc;
+    if (s.n_pos) {
+        if ((rc = docs_qc_impl(c, who, d, s.n_pos, nullptr, s.qc_raw.data()))) { lime_docs_free(d); return rc; }
+        if (!s.trim) d->qual.release();
+    }
+    if (s.trim && (rc = through(d, s.trimmed, [&](const lime_docs *in, lime_docs **out, lime_trim_info_t *ti) {
+                       return docs_trim_impl(c, who, in, s.q5, s.q3, nullptr, out, ti); }))) return rc;
+    if (s.adapter && (rc = through(d, s.ad_trimmed, [&](const lime_docs *in, lime_docs **out, lime_trim_info_t *ti) {
+                          return docs_adapter_impl(c, who, in, s.ad_masks, s.ad_m, s.ad_overlap, s.ad_err, nullptr, out, ti); }))) return rc;
+    if (s.filter && (rc = through(d, s.filtered, [&](const lime_docs *in, lime_docs **out, lime_filter_info_t *fi) {
+                         return docs_filter_impl(c, who, in, &s.fl, nullptr, out, fi); }))) return rc;
+    *docs = d;
+    return LIME_OK;
+}
+
+int lime_host::docs_count_out(lime_ctx *c, const char *who, MateStages &s, lime_docs **batch, lime_docs **other)
+{
+    if (!s.n_pos) return LIME_OK;
+    const int rc = docs_qc_impl(c, who, *batch, s.n_pos, nullptr, s.qc_out.data());
+    if (rc) { lime_docs_free(*batch); *batch = nullptr; }
+    if (rc && other) { lime_docs_free(*other); *other = nullptr; }
+    return rc;
 }
 
 extern "C" void lime_docs_free(lime_docs *d)

@@ -228,45 +228,10 @@ static int reader_next(lime_seq_reader *r, const char *who, uint32_t max_reads, 
         if (cut[0] > n) return fail(LIME_ERR_HIP, "%s: the cut lies behind the window", who);
         lime_docs *d = nullptr;
         const uint8_t *b = r->win.p + r->start;
-        if (r->format) rc = docs_parse_fastq_dev(r->ctx, who, b, cut[0], r->n_lines, nullptr, &d, r->trim || r->qc_pos);
+        if (r->format) rc = docs_parse_fastq_dev(r->ctx, who, b, cut[0], r->n_lines, nullptr, &d, r->stages.needs_qual());
         else rc = docs_parse_fasta_dev(r->ctx, who, b, cut[0], nullptr, &d);
         if (rc) return rc;
-        if (r->qc_pos) {                                 // the batch as parsed; without a trim the qualities were parsed for this alone
-            rc = docs_qc_impl(r->ctx, who, d, r->qc_pos, nullptr, r->qc_raw.data());
-            if (rc) { lime_docs_free(d); return rc; }
-            if (!r->trim) d->qual.release();
-        }
-        if (r->trim) {                                   // the batch as it is handed out: trimmed, without qualities
-            lime_docs *t = nullptr;
-            lime_trim_info_t ti;
-            rc = docs_trim_impl(r->ctx, who, d, r->q5, r->q3, nullptr, &t, &ti);
-            lime_docs_free(d);
-            if (rc) return rc;
-            d = t;
-            r->trimmed.n_reads += ti.n_reads; r->trimmed.n_changed += ti.n_changed; r->trimmed.n_empty += ti.n_empty;
-            r->trimmed.symbols_in += ti.symbols_in; r->trimmed.symbols_out += ti.symbols_out;
-        }
-        if (r->adapter) {                                // second, as an outside trimmer does it: the quality trim's output holds no qualities
-            lime_docs *t = nullptr;
-            lime_trim_info_t ti;
-            rc = docs_adapter_impl(r->ctx, who, d, r->ad_masks, r->ad_m, r->ad_overlap, r->ad_err, nullptr, &t, &ti);
-            lime_docs_free(d);
-            if (rc) return rc;
-            d = t;
-            r->ad_trimmed.n_reads += ti.n_reads; r->ad_trimmed.n_changed += ti.n_changed; r->ad_trimmed.n_empty += ti.n_empty;
-            r->ad_trimmed.symbols_in += ti.symbols_in; r->ad_trimmed.symbols_out += ti.symbols_out;
-        }
-        if (r->filter) {                                 // third: what the trims left, filtered
-            lime_docs *t = nullptr;
-            lime_filter_info_t fi;
-            rc = docs_filter_impl(r->ctx, who, d, &r->fl, nullptr, &t, &fi);
-            lime_docs_free(d);
-            if (rc) return rc;
-            d = t;
-            lime_filter_info_t &s = r->filtered;
-            s.n_reads += fi.n_reads; s.n_polyx += fi.n_polyx; s.n_capped += fi.n_capped; s.n_short += fi.n_short; s.n_many_n += fi.n_many_n;
-            s.n_low_complexity += fi.n_low_complexity; s.symbols_in += fi.symbols_in; s.symbols_out += fi.symbols_out;
-        }
+        if ((rc = docs_stages(r->ctx, who, r->stages, &d))) return rc;         // the batch as it is handed out
         uint32_t nd = 0;
         lime_docs_info(d, &nd, nullptr);
         if (r->n_records + nd > 0xFFFFFFFFull) {
@@ -278,7 +243,7 @@ static int reader_next(lime_seq_reader *r, const char *who, uint32_t max_reads, 
         r->n_records += nd;
         if (r->format) r->n_lines += 4ull * nd;
         if (!nd) { lime_docs_free(d); continue; }        // (FASTA without a header line up to the file's end: no record, the next turn ends)
-        if (r->qc_pos && out_qc && (rc = docs_qc_impl(r->ctx, who, d, r->qc_pos, nullptr, r->qc_out.data()))) { lime_docs_free(d); return rc; }
+        if (out_qc && (rc = docs_count_out(r->ctx, who, r->stages, &d))) return rc;
         *docs = d;
         return LIME_OK;
     }
@@ -310,14 +275,14 @@ extern "C" int lime_seq_reader_set_trim(lime_seq_reader *r, uint32_t q5, uint32_
     if (!r->format) return fail(LIME_ERR_ARG, "%s: the reader's file is FASTA; only FASTQ holds qualities", who);
     if (q5 > 93 || q3 > 93) return fail(LIME_ERR_ARG, "%s: cutoffs %u,%u; a Phred+33 quality is 0 .. 93", who, q5, q3);
     if (r->asked) return fail(LIME_ERR_ARG, "%s: the reader has handed out records already; the trim is set before the first lime_seq_reader_next", who);
-    r->trim = true; r->q5 = q5; r->q3 = q3;
+    r->stages.trim = true; r->stages.q5 = q5; r->stages.q3 = q3;
     return LIME_OK;
 }
 
 extern "C" int lime_seq_reader_trim_info(const lime_seq_reader *r, lime_trim_info_t *info)
 {
     if (!r || !info) return fail(LIME_ERR_ARG, "lime_seq_reader_trim_info: NULL argument");
-    *info = r->trimmed;
+    *info = r->stages.trimmed;
     return LIME_OK;
 }
 
@@ -328,15 +293,16 @@ extern "C" int lime_seq_reader_set_adapter(lime_seq_reader *r, const uint8_t *ad
     uint64_t masks[4];
     int rc = adapter_masks(who, adapter, m, min_overlap, max_err_pct, masks); if (rc) return rc;
     if (r->asked) return fail(LIME_ERR_ARG, "%s: the reader has handed out records already; the adapter is set before the first lime_seq_reader_next", who);
-    r->adapter = true; r->ad_m = m; r->ad_overlap = min_overlap; r->ad_err = max_err_pct;
-    memcpy(r->ad_masks, masks, sizeof masks);
+    MateStages &s = r->stages;
+    s.adapter = true; s.ad_m = m; s.ad_overlap = min_overlap; s.ad_err = max_err_pct;
+    memcpy(s.ad_masks, masks, sizeof masks);
     return LIME_OK;
 }
 
 extern "C" int lime_seq_reader_adapter_info(const lime_seq_reader *r, lime_trim_info_t *info)
 {
     if (!r || !info) return fail(LIME_ERR_ARG, "lime_seq_reader_adapter_info: NULL argument");
-    *info = r->ad_trimmed;
+    *info = r->stages.ad_trimmed;
     return LIME_OK;
 }
 
@@ -346,14 +312,14 @@ extern "C" int lime_seq_reader_set_filter(lime_seq_reader *r, const lime_filter_
     if (!r) return fail(LIME_ERR_ARG, "%s: the reader is NULL", who);
     int rc = filter_check(who, filter); if (rc) return rc;
     if (r->asked) return fail(LIME_ERR_ARG, "%s: the reader has handed out records already; the filter is set before the first lime_seq_reader_next", who);
-    r->filter = true; r->fl = *filter;
+    r->stages.filter = true; r->stages.fl = *filter;
     return LIME_OK;
 }
 
 extern "C" int lime_seq_reader_filter_info(const lime_seq_reader *r, lime_filter_info_t *info)
 {
     if (!r || !info) return fail(LIME_ERR_ARG, "lime_seq_reader_filter_info: NULL argument");
-    *info = r->filtered;
+    *info = r->stages.filtered;
     return LIME_OK;
 }
 
@@ -364,9 +330,9 @@ extern "C" int lime_seq_reader_set_qc(lime_seq_reader *r, uint32_t n_pos)
     if (!r) return fail(LIME_ERR_ARG, "%s: the reader is NULL", who);
     if (!n_pos || n_pos > LIME_QC_MAX_POS) return fail(LIME_ERR_ARG, "%s: %u positions; there are 1 .. %u", who, n_pos, LIME_QC_MAX_POS);
     if (r->asked) return fail(LIME_ERR_ARG, "%s: the reader has handed out records already; the statistics are set before the first lime_seq_reader_next", who);
-    r->qc_pos = n_pos;
-    r->qc_raw.assign(LIME_QC_WORDS(n_pos), 0);
-    r->qc_out.assign(LIME_QC_WORDS(n_pos), 0);
+    r->stages.n_pos = n_pos;
+    r->stages.qc_raw.assign(LIME_QC_WORDS(n_pos), 0);
+    r->stages.qc_out.assign(LIME_QC_WORDS(n_pos), 0);
     return LIME_OK;
 }
 
@@ -375,8 +341,9 @@ extern "C" int lime_seq_reader_qc(const lime_seq_reader *r, int which, uint64_t 
     const char *who = "lime_seq_reader_qc";
     if (!r || !tables) return fail(LIME_ERR_ARG, "%s: NULL argument", who);
     if (which != 0 && which != 1) return fail(LIME_ERR_ARG, "%s: tables %d; 0 is the batches as parsed, 1 as handed out", who, which);
-    if (!r->qc_pos) { memset(tables, 0, 8 * LIME_QC_WORDS(1u)); return LIME_OK; }
-    memcpy(tables, (which ? r->qc_out : r->qc_raw).data(), 8 * (size_t)LIME_QC_WORDS(r->qc_pos));
+    const MateStages &s = r->stages;
+    if (!s.n_pos) { memset(tables, 0, 8 * LIME_QC_WORDS(1u)); return LIME_OK; }
+    memcpy(tables, (which ? s.qc_out : s.qc_raw).data(), 8 * (size_t)LIME_QC_WORDS(s.n_pos));
     return LIME_OK;
 }
 
@@ -413,17 +380,10 @@ static int next_pair_impl(const char *who, lime_seq_reader *r1, lime_seq_reader 
     if (!got[0]) return LIME_OK;                         // the end of both files
     lime_overlap_info_t oi;
     if ((rc = docs_overlap_impl(r1->ctx, who, batch.d[0], batch.d[1], r1->ov_overlap, r1->ov_err, nullptr, nullptr, docs1, docs2, &oi))) return rc;
-    lime_overlap_info_t &s = r1->overlapped;
-    s.n_pairs += oi.n_pairs; s.n_overlap += oi.n_overlap; s.n_cut += oi.n_cut; s.symbols_in += oi.symbols_in; s.symbols_out += oi.symbols_out;
-    r2->overlapped = s;
-    lime_seq_reader *const rs[2] = {r1, r2};
-    lime_docs **const cut[2] = {docs1, docs2};
-    for (int m = 0; m < 2; ++m)
-        if (rs[m]->qc_pos && (rc = docs_qc_impl(rs[m]->ctx, who, *cut[m], rs[m]->qc_pos, nullptr, rs[m]->qc_out.data()))) {
-            lime_docs_free(*docs1); lime_docs_free(*docs2);
-            *docs1 = *docs2 = nullptr;
-            return rc;
-        }
+    add_info(r1->overlapped, oi);
+    r2->overlapped = r1->overlapped;
+    if ((rc = docs_count_out(r1->ctx, who, r1->stages, docs1, docs2))) return rc;     // the batches as they are handed out, behind the cut
+    if ((rc = docs_count_out(r2->ctx, who, r2->stages, docs2, docs1))) return rc;
     if (first_record) *first_record = first;
     return LIME_OK;
 }

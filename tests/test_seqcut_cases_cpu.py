@@ -176,7 +176,9 @@ def test_symbols_exist():
     assert not re.search(r"\b\w*(WG|LANE)\s*=[^=]", kernel)           # no workgroup size or bytes per lane of its own: lime_bytes.h's
     assert "asm" not in kernel and "asm" not in shared
     make = open(os.path.join(ROOT, "lime_amd", "csrc", "Makefile")).read()
-    assert "lime_seqcut_kernel.hip -o $$d/lime_seqcut.s" in make and "seqcut_kres.txt" in make
+    # the resources target takes every file of KERNELS but lime_index_sort through kres.py, the spill gate and the lint, in one loop
+    assert "lime_seqcut_kernel" in re.search(r"^KERNELS = (.+)$", make, re.M).group(1).split() and "LINTED = $(filter-out lime_index_sort,$(KERNELS))" in make
+    assert "for f in $(LINTED)" in make and "$$f.hip -o $$d/$$b.s" in make and "_kres.txt && cat" in make
 
 
 def test_the_usage_text_states_what_the_batched_counters_are(tmp_path):

@@ -158,7 +158,9 @@ def test_symbols_exist():
     kernel = open(os.path.join(ROOT, "lime_amd", "csrc", "lime_listcat_kernel.hip")).read()
     assert "k_lc_rows" in kernel and "k_lc_copy" in kernel and "asm" not in kernel
     make = open(os.path.join(ROOT, "lime_amd", "csrc", "Makefile")).read()
-    assert "lime_listcat_kernel.hip -o $$d/lime_listcat.s" in make and "listcat_kres.txt" in make
+    # the resources target takes every file of KERNELS but lime_index_sort through kres.py, the spill gate and the lint, in one loop
+    assert "lime_listcat_kernel" in re.search(r"^KERNELS = (.+)$", make, re.M).group(1).split() and "LINTED = $(filter-out lime_index_sort,$(KERNELS))" in make
+    assert "for f in $(LINTED)" in make and "$$f.hip -o $$d/$$b.s" in make and "_kres.txt && cat" in make
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "**f11" in design and "per-shard figures" in design
 
