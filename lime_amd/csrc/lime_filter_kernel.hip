@@ -1,9 +1,9 @@
 // lime_filter_kernel.hip -- what the read filter keeps of every read (include/lime_hip.h states the rule at lime_read_filter, the oracle;
 // lime_docs.cpp sequences the passes: this kernel, the prefix sum over the new lengths and lime_fqtrim_kernel.hip's k_trim_copy).
 //   k_filter_bounds  per read lo32[r] = 0 and len32[r] = n, what the poly-X tail and the cap leave of it, or 0 where a filter fails it.
-//                    One wave on a read, 64 symbols a word, in k_adapter_bounds' conventions: lane i loads symbol 64 w + i where it lies
-//                    in the read, four ballots of (byte & 0xDF) == b give the words R_b[w], b in A C G T, with 0 bits behind the read's
-//                    end; the fifth class "other" is what is valid and in none of them.
+//                    One wave on a read, 64 symbols a word, in lime_reads.h's conventions: lane i loads symbol 64 w + i where it lies in
+//                    the read, and base_words gives the words R_b[w], b in A C G T, with 0 bits behind the read's end; the fifth class
+//                    "other" is what is valid and in none of them.
 //                    The tail: the words from the last one down.  For a base X of the mask, lane j's mm_X is the set bits of
 //                    ~R_X & valid at and above bit j plus the misses carried from the words behind; a lane is admissible when its
 //                    symbol is X, its tail holds T symbols or more and 8 mm_X <= t.  A ballot of "admissible" (over every X of the mask)
@@ -16,8 +16,7 @@
 //                    wave-uniform: this pass is scalar work but for the loads.
 //                    A read of up to 128 symbols is loaded once and its two words serve both passes; a longer one's tail walk loads
 //                    from the end and its forward pass loads again, one word ahead each.
-//                    A wave strides over its reads and runs two ahead, as k_adapter_bounds does: the first 128 symbols of read
-//                    r + stride and the offsets of read r + 2 stride are on their way while read r is worked on.
+//                    A wave strides over its reads and runs two ahead (walk_reads, lime_reads.h).
 // wave64.  The loops over the reads and over a read's words are wave-uniform (blockIdx, the wave's index and the read's length made
 // scalar), and every ballot sits in them with the lanes outside the read taking part with no value.  No inline assembly, plain vector
 // stores, no LDS.  No byte outside text[doc_off[r] .. doc_off[r + 1]) is loaded.
@@ -25,51 +24,20 @@
 #include <stdint.h>
 #include "lime_hip.h"
 #include "lime_index.h"
-#include "lime_wave.h"
+#include "lime_reads.h"
 
 namespace lime {
 
 namespace {
 
-constexpr int FL_WG = 256;
-constexpr uint32_t FL_WAVES = FL_WG / 64;        // reads a workgroup handles per trip
-constexpr uint32_t FL_BLOCKS = 2048;             // eight workgroups a CU: the grid is capped and the waves stride
-
-struct FlWords { uint64_t b[4]; };               // R_A, R_C, R_G, R_T of 64 symbols
-
 struct FlArgs { uint32_t polyx_mask, polyx_min, max_len, min_len, max_n, min_complexity; };
-
-__device__ __forceinline__ uint64_t fl_uniform64(uint64_t v)
-{
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
-
-// symbol `at` of the read s[0 .. L) as it is, 0 (no base) outside it
-__device__ __forceinline__ uint32_t fl_load(const uint8_t *s, uint64_t L, uint64_t at)
-{
-    return at < L ? (uint32_t)s[at] : 0u;
-}
-
-__device__ __forceinline__ FlWords fl_words(uint32_t c)
-{
-    FlWords w;
-    c &= 0xDFu;                                  // (lower case is its base)
-    w.b[0] = __ballot(c == 'A'); w.b[1] = __ballot(c == 'C'); w.b[2] = __ballot(c == 'G'); w.b[3] = __ballot(c == 'T');
-    return w;
-}
-
-// the k lowest bits, k in 0 .. 64 and above
-__device__ __forceinline__ uint64_t fl_low(uint64_t k)
-{
-    return k >= 64u ? ~0ull : (1ull << k) - 1u;
-}
 
 // word w of the read: c0, c1 where they hold it, a load of its own otherwise (w is wave-uniform)
 __device__ __forceinline__ uint32_t fl_fetch(const uint8_t *s, uint64_t L, uint64_t w, uint32_t c0, uint32_t c1, uint32_t lane)
 {
     if (w == 0u) return c0;
     if (w == 1u) return c1;
-    return fl_load(s, L, w * 64u + lane);
+    return read_load(s, L, w * 64u + lane);
 }
 
 // t* of the read s[0 .. L), L >= 1: the longest admissible tail over the bases of `mask`, 0 without one.  Wave-uniform but for c0, c1
@@ -84,8 +52,8 @@ __device__ __forceinline__ uint64_t fl_tail(const uint8_t *s, uint64_t L, uint32
     for (uint64_t w = n_words; w-- > 0u && live;) {
         const uint32_t cur = nxt;
         if (w) nxt = fl_fetch(s, L, w - 1u, c0, c1, lane);                 // (on its way while this word is worked on)
-        const FlWords R = fl_words(cur);
-        const uint64_t valid = fl_low(L - w * 64u);
+        const BaseWords R = base_words(cur);
+        const uint64_t valid = low_bits(L - w * 64u);
         const uint64_t p = w * 64u + lane;
         const uint64_t t = p < L ? L - p : 0u;                             // (a lane behind the read: t = 0 < T)
         bool adm = false;
@@ -110,71 +78,59 @@ __device__ __forceinline__ void fl_counts(const uint8_t *s, uint64_t L, uint64_t
 {
     const uint32_t lane = lane_id();
     const uint64_t n_words = (n + 63u) >> 6;
-    FlWords cur = fl_words(c0), nxt = fl_words(c1);
+    BaseWords cur = base_words(c0), nxt = base_words(c1);
     uint64_t other = 0u, equal = 0u;
     for (uint64_t w = 0; w < n_words; ++w) {
         uint32_t c2 = 0u;
-        if (w + 2u < n_words) c2 = fl_load(s, L, (w + 2u) * 64u + lane);   // (on its way while this word is worked on; a word the counts need)
+        if (w + 2u < n_words) c2 = read_load(s, L, (w + 2u) * 64u + lane);   // (on its way while this word is worked on; a word the counts need)
         const uint64_t o_cur = ~(cur.b[0] | cur.b[1] | cur.b[2] | cur.b[3]), o_nxt = ~(nxt.b[0] | nxt.b[1] | nxt.b[2] | nxt.b[3]);
         const uint64_t below = n - w * 64u;                                // the places of this word in front of n, 1 and more
-        other += (uint64_t)__builtin_popcountll(o_cur & fl_low(below));
+        other += (uint64_t)__builtin_popcountll(o_cur & low_bits(below));
         uint64_t eq = o_cur & ((o_cur >> 1) | (o_nxt << 63));
 #pragma unroll
         for (int b = 0; b < 4; ++b) eq |= cur.b[b] & ((cur.b[b] >> 1) | (nxt.b[b] << 63));
-        equal += (uint64_t)__builtin_popcountll(eq & fl_low(below - 1u));  // the pairs j, j + 1 with j + 1 < n
+        equal += (uint64_t)__builtin_popcountll(eq & low_bits(below - 1u));  // the pairs j, j + 1 with j + 1 < n
         cur = nxt;
-        nxt = fl_words(c2);
+        nxt = base_words(c2);
     }
     *n_other = other; *n_equal = equal;
 }
 
 // lo32[r], len32[r] of every read (len32[n_docs] stays as the caller zeroed it); counts[0 .. 5) += the reads with a poly-X tail, the reads
 // the cap shortened, and the reads emptied as short, for their N's and for their complexity
-__global__ void __launch_bounds__(FL_WG) k_filter_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, FlArgs f, uint32_t *lo32, uint32_t *len32,
+__global__ void __launch_bounds__(RD_WG) k_filter_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, FlArgs f, uint32_t *lo32, uint32_t *len32,
                                                          unsigned long long *counts)
 {
     const uint32_t lane = lane_id();
-    const uint64_t stride = (uint64_t)gridDim.x * FL_WAVES;
-    uint64_t r = (uint64_t)blockIdx.x * FL_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // two reads ahead, as in k_adapter_bounds: at the top of a trip (a1, L1) are the bounds of read r, whose first two words are asked for
-    // there, and (a0, L0, c0, c1) is read r - stride with those words; the bounds of read r + stride are asked for too
-    uint64_t a0 = 0u, L0 = 0u, a1 = 0u, L1 = 0u;
-    uint32_t c0 = 0u, c1 = 0u;
-    if (r < n_docs) { a1 = fl_uniform64(doc_off[r]); L1 = fl_uniform64(doc_off[r + 1]) - a1; }
     uint32_t n_polyx = 0u, n_capped = 0u, n_short = 0u, n_many = 0u, n_low = 0u;
     const bool count = f.max_n != LIME_FILTER_OFF || f.min_complexity != 0u;
-    for (bool first = true;; first = false, r += stride) {
-        const bool more = r < n_docs;                                      // (L1 is 0 behind the last read: nothing is loaded)
-        const uint32_t n0 = fl_load(text + a1, L1, lane), n1 = fl_load(text + a1, L1, 64u + lane);
-        uint64_t a2 = 0u, L2 = 0u;
-        if (r + stride < n_docs) { a2 = doc_off[r + stride]; L2 = doc_off[r + stride + 1]; }
-        if (!first) {
-            uint64_t keep = 0u;
-            if (L0) {                                                      // (a read that came in empty is counted nowhere)
-                uint64_t n = L0;
-                if (f.polyx_mask) {
-                    const uint64_t t = fl_tail(text + a0, L0, c0, c1, f.polyx_mask, f.polyx_min);
-                    n_polyx += (uint32_t)(t != 0u);
-                    n -= t;
-                }
-                if (f.max_len && n > f.max_len) { n = f.max_len; ++n_capped; }
-                bool pass = true;
-                if (n < f.min_len) { pass = false; ++n_short; }
-                else if (count && n) {
-                    uint64_t other, equal;
-                    fl_counts(text + a0, L0, n, c0, c1, &other, &equal);
-                    const uint64_t d = n - 1u - equal;
-                    if (f.max_n != LIME_FILTER_OFF && other > f.max_n) { pass = false; ++n_many; }
-                    else if (n >= 2u && 100u * d < (uint64_t)f.min_complexity * (n - 1u)) { pass = false; ++n_low; }
-                }
-                keep = pass ? n : 0u;
+    walk_reads<false>(text, nullptr, doc_off, n_docs, [&](uint64_t r, uint64_t a, uint64_t L, uint32_t c0, uint32_t c1) {
+        uint64_t keep = 0u;
+        if (L) {                                                           // (a read that came in empty is counted nowhere)
+            uint64_t n = L;
+            if (f.polyx_mask) {
+                const uint64_t t = fl_tail(text + a, L, c0, c1, f.polyx_mask, f.polyx_min);
+                n_polyx += (uint32_t)(t != 0u);
+                n -= t;
             }
-            if (lane == 0u) { lo32[r - stride] = 0u; len32[r - stride] = (uint32_t)keep; }      // (a read holds fewer than 2^32 symbols)
+            if (f.max_len && n > f.max_len) { n = f.max_len; ++n_capped; }
+            // this read's share of three counts, added behind the branches: increments of the captured counters in branches that exclude
+            // one another are merged into one increment through a chosen address, and the counters then live in scratch
+            uint32_t d_short = 0u, d_many = 0u, d_low = 0u;
+            bool pass = true;
+            if (n < f.min_len) { pass = false; ++d_short; }
+            else if (count && n) {
+                uint64_t other, equal;
+                fl_counts(text + a, L, n, c0, c1, &other, &equal);
+                const uint64_t d = n - 1u - equal;
+                if (f.max_n != LIME_FILTER_OFF && other > f.max_n) { pass = false; ++d_many; }
+                else if (n >= 2u && 100u * d < (uint64_t)f.min_complexity * (n - 1u)) { pass = false; ++d_low; }
+            }
+            n_short += d_short; n_many += d_many; n_low += d_low;
+            keep = pass ? n : 0u;
         }
-        if (!more) break;
-        a0 = a1; L0 = L1; c0 = n0; c1 = n1;
-        a1 = fl_uniform64(a2); L1 = fl_uniform64(L2) - a1;
-    }
+        if (lane == 0u) { lo32[r] = 0u; len32[r] = (uint32_t)keep; }       // (a read holds fewer than 2^32 symbols)
+    });
     if (lane == 0u) {
         if (n_polyx) atomicAdd(&counts[0], (unsigned long long)n_polyx);
         if (n_capped) atomicAdd(&counts[1], (unsigned long long)n_capped);
@@ -189,10 +145,9 @@ __global__ void __launch_bounds__(FL_WG) k_filter_bounds(const uint8_t *text, co
 void fl_launch_bounds(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs, const lime_filter_t *f, uint32_t *lo32, uint32_t *len32, uint64_t *counts,
                       hipStream_t st)
 {
-    const uint64_t nb = ((uint64_t)n_docs + FL_WAVES - 1u) / FL_WAVES;
+    const uint32_t grid = rd_grid(n_docs);
     const FlArgs a = {f->polyx_mask, f->polyx_min, f->max_len, f->min_len, f->max_n, f->min_complexity};
-    if (nb)
-        k_filter_bounds<<<nb < FL_BLOCKS ? (uint32_t)nb : FL_BLOCKS, FL_WG, 0, st>>>(text, doc_off, n_docs, a, lo32, len32, (unsigned long long *)counts);
+    if (grid) k_filter_bounds<<<grid, RD_WG, 0, st>>>(text, doc_off, n_docs, a, lo32, len32, (unsigned long long *)counts);
 }
 
 } // namespace lime

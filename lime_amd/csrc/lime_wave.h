@@ -1,6 +1,6 @@
 // lime_wave.h -- wave64 and lane primitives of the kernels (gfx950): lane reads and writes, ballot ranks, wave sums and the DPP
 // prefix sum, the may_alias types LDS is read and written through, the kernel-argument re-read (cold) and the exact byte add on the
-// table.  Device code only; shared by lime_kernels.hip, lime_partition.hip, lime_apply.hip, lime_adapter_kernel.hip, lime_overlap_kernel.hip and lime_bytes.h's users.
+// table.  Device code only; shared by lime_kernels.hip, lime_partition.hip, lime_apply.hip, lime_bytes.h's users, and lime_reads.h with lime_{adapter,filter,overlap,qc}_kernel.hip on it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

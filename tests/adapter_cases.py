@@ -11,7 +11,7 @@ from tests.trim_cases import bases, records      # (the same helpers)
 SEED = 20314
 FUZZ_CASES = 400
 WORD = 64                                       # symbols a wave handles per step
-READS_PER_TRIP = 2048 * 4                       # AD_BLOCKS workgroups of AD_WAVES reads: the grid cap
+READS_PER_TRIP = 2048 * 4                       # RD_BLOCKS workgroups of RD_WAVES reads (lime_reads.h): the grid cap
 LONG = 70_001
 ADAPTER_LENGTHS = (1, 2, 31, 32, 33, 63, 64)
 TRUSEQ_R1 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"

@@ -13,7 +13,7 @@ from tests.trim_cases import bases, records
 SEED = 20315
 FUZZ_CASES = 400
 WORD = 64                                       # symbols a wave handles per step
-READS_PER_TRIP = 2048 * 4                       # FL_BLOCKS workgroups of FL_WAVES reads: the grid cap
+READS_PER_TRIP = 2048 * 4                       # RD_BLOCKS workgroups of RD_WAVES reads (lime_reads.h): the grid cap
 LONG = 70_001
 OFF = None                                      # max_n without a limit (LIME_FILTER_OFF)
 A_, C_, G_, T_ = 1, 2, 4, 8                     # polyx_mask bits

@@ -13,7 +13,7 @@ from tests.trim_cases import bases, records                                     
 SEED = 20316
 FUZZ_CASES = 400
 WORD = 64                                       # candidates a wave handles per step, symbols per word
-PAIRS_PER_TRIP = 2048 * 4                       # OV_BLOCKS workgroups of OV_WAVES pairs: the grid cap
+PAIRS_PER_TRIP = 2048 * 4                       # RD_BLOCKS workgroups of RD_WAVES pairs (lime_reads.h): the grid cap
 KEPT = 512                                      # OV_CAP * 64: the symbols of a mate whose words stay in LDS; beyond, they are made again
 LENGTHS = lambda O: sorted({0, 1, O - 1, O, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 1000})      # noqa: E731
 INFO_KEYS = ("n_pairs", "n_overlap", "n_cut", "symbols_in", "symbols_out")

@@ -13,7 +13,7 @@ from tests.trim_cases import records                    # noqa: F401
 SEED = 20317
 FUZZ_CASES = 400
 WORD = 64                                       # symbols a wave handles per step
-READS_PER_TRIP = 2048 * 4                       # QC_BLOCKS workgroups of QC_WAVES reads: the grid cap
+READS_PER_TRIP = 2048 * 4                       # RD_BLOCKS workgroups of RD_WAVES reads (lime_reads.h): the grid cap
 MAX_POS = 512
 N_POS = (1, 2, 63, 64, 65, 100, 255, 256, 511, 512)
 LENGTHS = (0, 1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1000, 5000)

@@ -142,7 +142,7 @@ def test_collections_of_1_to_65_reads(ctx, n):
 
 @pytest.mark.parametrize("n", [16384 + 5, 6 * A.READS_PER_TRIP + 37], ids=["16389 reads", "49189 reads, past the grid cap"])
 def test_many_reads(ctx, n):
-    """whoever changes AD_BLOCKS or AD_WAVES in lime_adapter_kernel.hip changes adapter_cases.READS_PER_TRIP: the larger collection takes a
+    """whoever changes RD_BLOCKS or RD_WAVES in lime_reads.h changes adapter_cases.READS_PER_TRIP: the larger collection takes a
     seventh trip.  The numpy model on the first and last 300 reads, lime_adapter_trim on all"""
     from lime_amd import api
     assert A.READS_PER_TRIP == 8192 and 6 * A.READS_PER_TRIP + 37 == 49189

@@ -223,7 +223,7 @@ def test_collections_of_1_to_65_reads(ctx, n):
 
 @pytest.mark.parametrize("n", [F.READS_PER_TRIP + 1, 2 * F.READS_PER_TRIP + 3], ids=["8193 reads", "16387 reads"])
 def test_many_reads(ctx, n):
-    """whoever changes FL_BLOCKS or FL_WAVES in lime_filter_kernel.hip changes filter_cases.READS_PER_TRIP: one read more than a trip of the
+    """whoever changes RD_BLOCKS or RD_WAVES in lime_reads.h changes filter_cases.READS_PER_TRIP: one read more than a trip of the
     capped grid, and three more than two trips.  The numpy model on the first and last 300 reads, lime_read_filter on all"""
     from lime_amd import api
     assert F.READS_PER_TRIP == 8192

@@ -149,7 +149,7 @@ def test_collections_of_1_to_65_pairs(ctx, n):
 
 @pytest.mark.parametrize("n", [V.PAIRS_PER_TRIP + 1, V.PAIRS_PER_TRIP + 2], ids=["one over a trip", "two over a trip"])
 def test_past_the_grids_pairs_per_trip(ctx, n):
-    """whoever changes OV_BLOCKS or OV_WAVES in lime_overlap_kernel.hip changes overlap_cases.PAIRS_PER_TRIP: the last one or two pairs are
+    """whoever changes RD_BLOCKS or RD_WAVES in lime_reads.h changes overlap_cases.PAIRS_PER_TRIP: the last one or two pairs are
     a wave's second.  The numpy model on the first and last 200 pairs, lime_pair_overlap_trim on all"""
     assert V.PAIRS_PER_TRIP == 8192
     r1, r2 = _collection(n, n, top=50, O=8, errs=1)                           # (no errors: three in four pairs are planted within the candidates)
